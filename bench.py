@@ -16,8 +16,13 @@ One "step" = one pass of the hot path over one batch per GPU, inputs already res
 One process per GPU.  With N > 1 the frozen .tflite bytes are broadcast from rank 0 over RCCL (torch.distributed "nccl"),
 frames are sharded per GPU and no data-path collective exists (frames are independent): "scaling": "weak".
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, timed live with HIP events on the launch stream) and, at
-N = 1, `cpu_baseline` (the C oracle on the host cores — a *port*: the reference's TFLite path cannot be built here).
+A plain run sets up, warms up, times the K steps once and prints ONE JSON line on rank 0 (`metric`, `value`, `unit`,
+`ms_per_step`, ...).  With --full that line also carries what takes runs of its own: repeated timing windows, the
+one-batch-in-flight figure, `roofline` (dominant kernel, timed live with HIP events on the launch stream), configs 1 / 3 / 5
+as `secondary_configs`, the host-fed variant, the single-image latencies and, at N = 1, `cpu_baseline` (the C oracle on the
+host cores — a *port*: the reference's TFLite path cannot be built here).
+
+    python bench.py --dump-outputs DIR   # also writes the last timed step's outputs as DIR/<name>.npy (float32)
 """
 import argparse
 import hashlib
@@ -454,6 +459,19 @@ def rehearse(args, rank, world):
     dist.destroy_process_group()
 
 
+def dump_outputs(outdir, outputs):
+    """What the timed path handed its caller in the last timed step, as float32 .npy files under `outdir`: the detection rows
+    past a frame's count (slots the device path leaves untouched, mi_face.h) are written as zeros."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {name: t.detach().cpu().numpy() for name, t in outputs.items()}
+    if "detections" in arrays:
+        det, cnt = arrays["detections"], arrays["counts"]
+        det[np.arange(det.shape[1])[None, :] >= cnt[:, None]] = 0.0
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a.astype(np.float32))
+
+
 def run_rank(args):
     import numpy as np
     import torch
@@ -524,7 +542,8 @@ def run_rank(args):
             cnt = torch.zeros((B,), dtype=torch.int32, device=device)
             def step_k(spp, h=fd.h, op=C.c_void_p(out.data_ptr()), cp=C.c_void_p(cnt.data_ptr())):
                 check(L.mi_fd_infer_tensor(h, xp, B, None, op, cap, cp, mi.MI_MEM_DEVICE, spp))
-            workers.append(dict(step=step_k, keep=(fd, out, cnt), counts=cnt, found=lambda cnt=cnt: int((cnt > 0).sum().item())))
+            workers.append(dict(step=step_k, keep=(fd, out, cnt), counts=cnt, found=lambda cnt=cnt: int((cnt > 0).sum().item()),
+                                outputs=dict(detections=out, counts=cnt)))
         fd = workers[0]["keep"][0]
         counts = workers[0]["counts"]
         if args.config == 2:
@@ -550,7 +569,8 @@ def run_rank(args):
             flags = torch.zeros((B,), dtype=torch.float32, device=device)
             def step_k(spp, h=fl.h, a=C.c_void_p(lm.data_ptr()), b=C.c_void_p(present.data_ptr()), c=C.c_void_p(flags.data_ptr())):
                 check(L.mi_fl_infer_tensor(h, xp, B, None, None, a, b, c, mi.MI_MEM_DEVICE, spp))
-            workers.append(dict(step=step_k, keep=(fl, lm, present, flags), found=lambda present=present: int(present.sum().item())))
+            workers.append(dict(step=step_k, keep=(fl, lm, present, flags), found=lambda present=present: int(present.sum().item()),
+                                outputs=dict(landmarks=lm, present=present, flags=flags)))
         metric, unit = "ROIs/sec, FaceLandmark 192x192 at batch=512 per GPU (configs[2])", "ROIs/s"
         workload = "FaceLandmark 192x192, batch=%d ROIs/GPU, net + face flag + landmark projection (configs[2]); 50%% noise / 50%% face crops, inputs resident in HBM" % B
         models = [(workers[0]["keep"][0].model, x)]
@@ -570,7 +590,7 @@ def run_rank(args):
             ptrs = [C.c_void_p(o[n].data_ptr()) for n in ("faces", "face_counts", "landmarks", "present", "eyes")]
             def step_k(spp, h=pipe.h, ptrs=ptrs):
                 check(L.mi_pipeline_run(h, fp, B, 192, 192, 3 * 192, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], mi.MI_MEM_DEVICE, spp))
-            workers.append(dict(step=step_k, keep=(pipe, o), found=lambda o=o: int(o["present"].sum().item())))
+            workers.append(dict(step=step_k, keep=(pipe, o), found=lambda o=o: int(o["present"].sum().item()), outputs=o))
         pipe = workers[0]["keep"][0]
         metric, unit = "frames/sec, full_range detection -> face_landmark -> 2 x iris_landmark at 128 frames per GPU (configs[4])", "frames/s"
         workload = ("full_range 192x192 -> faces[0] ROI -> face_landmark 192x192 -> eye ROIs -> 2 x iris_landmark 64x64, batch=%d RGB frames/GPU, "
@@ -629,7 +649,8 @@ def run_rank(args):
     # by kernel symbol like rocprofv3 --stats does), every rank alike.  The W warm-up steps and the K timed steps follow it directly.
     # (two passes: this one, whose figures are discarded — the chip comes out of the host-side set-up idle and its clocks are still ramping —
     # and the recorded one behind the timed windows, on a chip in the state the windows were measured in)
-    if not (args.no_event_profile and world == 1):
+    event_profile = args.full and not (args.no_event_profile and world == 1)
+    if event_profile:
         for m, xin in models:
             m.profile(xin, reps=3)
     torch.cuda.synchronize()
@@ -648,12 +669,14 @@ def run_rank(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     elapsed = mdist.max_over_ranks(elapsed, dist, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, workers[(state["i"] - 1) % NW]["outputs"])
     n_found = found()
     # ---- the same K-step window again until >= MIN_TIMED_S of device time has been sampled (the first window above stays the
     # reported one: `ms_per_step` and `value`); median / min over all windows go into extra keys.  The number of windows is
     # decided from rank 0's clock and shared, so every rank runs the same count.
     windows = [elapsed]
-    n_extra = max(4, int(MIN_TIMED_S / max(elapsed, 1e-6)) + 1) if not args.single_window else 0
+    n_extra = max(4, int(MIN_TIMED_S / max(elapsed, 1e-6)) + 1) if args.full and not args.single_window else 0
     n_extra = int(mdist.max_over_ranks(float(min(n_extra, 2000)), dist, device))
     for _ in range(n_extra):
         if dist:
@@ -670,7 +693,7 @@ def run_rank(args):
 
     # the same K steps with ONE batch in flight (one handle, one stream), for comparison (extra key, never `value`)
     one_in_flight_ms = None
-    if NW > 1:
+    if args.full and NW > 1:
         if args.config in (1, 2):
             # ... with the band sizes that are best for one batch in flight (the automatic ones); the recorded per-launch pass for `roofline`
             # below runs on this handle too: it describes every kernel running alone, like the rocprofv3 passes (--in-flight 1)
@@ -689,7 +712,7 @@ def run_rank(args):
         gathered = [int((p > 0).sum().item()) for p in parts]
     if rank == 0:
         recs = []
-        if not (args.no_event_profile and world == 1):
+        if event_profile:
             for m, xin in models:
                 # per launch: the median of three passes of five executions each (one pass read a single launch 30 % long once in a while — a
                 # neighbouring process's burst on the box — and the dominant symbol's figure with it; the rocprofv3 average beside it did not move)
@@ -702,7 +725,7 @@ def run_rank(args):
         result = {
             "metric": metric, "value": round(value, 1), "unit": unit,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             # the in-flight setting beside the headline, and the one-handle figure (the measurement of rounds 1 - 4, and what `roofline`
             # and every profile under profiles/ describe) as a first-class field — round-over-round comparisons are like for like
             "batches_in_flight": NW,
@@ -723,7 +746,9 @@ def run_rank(args):
                                           "band sizes (every kernel running alone); --in-flight 1 gives the one-handle figure" % (NW, NW, len(cand) - 1)) if NW > 1 else None,
                        "note": "ms_per_step / value = the first window (the driver's K steps, directly behind the W warm-up steps); the others repeat it. "
                                "Before the warm-up steps a per-launch HIP-event pass over the plan runs once (figures discarded; the recorded pass "
-                               "for `roofline` runs behind the windows)"},
+                               "for `roofline` runs behind the windows)" if event_profile else
+                               "ms_per_step / value = the K timed steps, directly behind the W warm-up steps, timed once (--full repeats the window "
+                               "and adds the per-launch event passes)"},
             "config": {"workload": workload, "global_batch": world * B, "batches_in_flight": NW, "frames_with_faces": n_found,
                        "parallelism": "frames sharded %d/GPU, one process per GPU, no data-path collective" % B,
                        "weight_broadcast_ms": round(bcast_ms, 3), "weight_broadcast_bytes": sum(len(b) for b in blobs),
@@ -731,9 +756,12 @@ def run_rank(args):
                        "plan": " | ".join(m.describe().splitlines()[0] for m, _ in models)},
             "roofline": roofline_of(recs, tag) if recs else None,
         }
-        if not recs:  # --no-event-profile (rocprofv3 kernel-trace runs: the dispatch sequence stays one step after the other)
+        if not recs:  # a plain run, or --no-event-profile (rocprofv3 kernel-trace runs: the dispatch sequence stays one step after the other)
             print(json.dumps(result), flush=True)
             close_workers()
+            if dist:
+                dist.barrier()
+                dist.destroy_process_group()
             return
         # the whole step against the same roofs (algorithmic FLOPs / bytes of all launches over ms_per_step)
         sa = result["roofline"].pop("step_algorithmic")
@@ -810,7 +838,7 @@ def run_secondary_configs(args):
         key = "config %d" % c
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", str(c), "--steps", str(args.steps), "--warmup", str(args.warmup),
-                                "--no-cpu-baseline", "--no-latency", "--no-secondary", "--no-host-feed"], capture_output=True, text=True, timeout=300)
+                                "--full", "--no-cpu-baseline", "--no-latency", "--no-secondary", "--no-host-feed"], capture_output=True, text=True, timeout=300)
             lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if r.returncode != 0 or not lines:
                 out[key] = {"error": "child exited with status %d: %s" % (r.returncode, (r.stderr or r.stdout)[-300:].replace("\n", " | "))}
@@ -853,13 +881,20 @@ def main():
     ap.add_argument("--lanes", type=int, default=None)
     ap.add_argument("--heads", type=int, default=None)
     ap.add_argument("--opt", action="append", default=[], help="engine option key=value (development), every model of the configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: repeated windows, one batch in flight, roofline (per-launch event pass), "
+                         "configs 1 / 3 / 5, host feed, single-image latency, CPU baseline (the --no-* options switch these off one by one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32; rank 0's shard)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.rehearse or args.spawn):
         sys.exit(launch_ranks(args, sys.argv[1:]))
     args.secondary_results = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.config == 2 and not args.no_secondary and not args.rehearse:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.config == 2 and not args.no_secondary and not args.rehearse:
         args.secondary_results = run_secondary_configs(args)
     run_rank(args)
 

@@ -18,6 +18,9 @@ def _declared_functions():
 
 
 def test_library_exports_every_declared_symbol(mi):
+    # through mi.lib() first: it loads torch before libmiface.so, so that the two share one HIP runtime; a bare CDLL as the
+    # session's first load would leave torch's HIP without devices for every GPU test that follows in the same process
+    mi.lib()
     L = ctypes.CDLL(mi.LIB_PATH)
     names = _declared_functions()
     assert len(names) >= 35

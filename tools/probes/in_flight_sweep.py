@@ -6,7 +6,7 @@ for c in [int(v) for v in sys.argv[1:]] or [2]:
     for n in (2, 3):
         for env_extra in ({}, {"GPU_MAX_HW_QUEUES": "8"}) if n == 3 else ({},):
             env = dict(os.environ, **env_extra)
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(c), "--in-flight", str(n), "--no-secondary", "--no-cpu-baseline",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", str(c), "--in-flight", str(n), "--no-secondary", "--no-cpu-baseline",
                                 "--no-latency", "--no-host-feed", "--no-event-profile"], capture_output=True, text=True, env=env, timeout=600)
             lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if not lines:

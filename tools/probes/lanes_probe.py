@@ -3,7 +3,7 @@ python tools/probes/lanes_probe.py  (this process never touches the GPU)"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def run(config, opts):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(config), "--in-flight", "1", "--no-secondary", "--no-cpu-baseline", "--no-latency",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", str(config), "--in-flight", "1", "--no-secondary", "--no-cpu-baseline", "--no-latency",
                         "--no-host-feed", "--no-event-profile"] + [x for o in opts for x in ("--opt", o)], capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not lines:

@@ -16,5 +16,5 @@ done > $O/stamps.txt 2>&1
 echo stamps done
 timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "pipe_band or two_batches_in_flight" > $O/pytest.txt 2>&1; echo "pytest rc $?"
 tail -3 $O/pytest.txt
-timeout -k 10 300 python bench.py --no-secondary --no-cpu-baseline --no-latency --no-host-feed > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout -k 10 300 python bench.py --full --no-secondary --no-cpu-baseline --no-latency --no-host-feed > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 cat $O/ablation.txt

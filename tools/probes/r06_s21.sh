@@ -3,7 +3,7 @@ O=gpurun_out/r06_s21; mkdir -p $O
 for c in 3 2; do
  for ch in 0 64 128 256; do
   for fl in 1 2; do
-   python bench.py --config $c --no-secondary --no-latency --no-cpu-baseline --no-host-feed --no-event-profile --in-flight $fl --chunk $ch > $O/b_${c}_${ch}_${fl}.json 2> $O/b_${c}_${ch}_${fl}.err
+   python bench.py --full --config $c --no-secondary --no-latency --no-cpu-baseline --no-host-feed --no-event-profile --in-flight $fl --chunk $ch > $O/b_${c}_${ch}_${fl}.json 2> $O/b_${c}_${ch}_${fl}.err
    python - "$O/b_${c}_${ch}_${fl}.json" $c $ch $fl <<'PY'
 import json,sys
 try:

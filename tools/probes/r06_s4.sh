@@ -5,7 +5,7 @@ cd /tmp 2>/dev/null; cd - >/dev/null
 export TMPDIR=/tmp
 O=gpurun_out/r06_s4; rm -rf $O; mkdir -p $O
 for c in 2 5 3; do
-  rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $O/gui_c$c -- python3 bench.py --config $c --steps 30 --warmup 5 --no-cpu-baseline --no-latency --no-host-feed --no-secondary --no-event-profile --single-window --in-flight 1 > $O/gui_c$c.log 2>&1; echo "pmc $c rc $?"
+  rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $O/gui_c$c -- python3 bench.py --full --config $c --steps 30 --warmup 5 --no-cpu-baseline --no-latency --no-host-feed --no-secondary --no-event-profile --single-window --in-flight 1 > $O/gui_c$c.log 2>&1; echo "pmc $c rc $?"
 done
 python3 - <<'PY'
 import csv, glob, collections, os

@@ -4,7 +4,7 @@
 set -o pipefail
 O=gpurun_out/r06_s5; mkdir -p $O
 for v in "" -onebar -nobar -nohand_onebar ""; do
-  MIFACE_LIB=$PWD/rs-face-detection-tflite_amd/libmiface$v.so timeout -k 10 300 python bench.py --config 2 --steps 200 --warmup 10 --no-secondary --no-cpu-baseline --no-latency --no-host-feed --in-flight 1 > $O/bench$v.json 2> $O/bench$v.err; echo "bench '$v' rc $?"
+  MIFACE_LIB=$PWD/rs-face-detection-tflite_amd/libmiface$v.so timeout -k 10 300 python bench.py --full --config 2 --steps 200 --warmup 10 --no-secondary --no-cpu-baseline --no-latency --no-host-feed --in-flight 1 > $O/bench$v.json 2> $O/bench$v.err; echo "bench '$v' rc $?"
   python3 - "$O/bench$v.json" "$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

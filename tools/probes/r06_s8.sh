@@ -7,7 +7,7 @@ for nf in 1 2; do
   ( for i in $(seq 1 44); do rocm-smi --showclocks --showpower 2>&1 | grep -E "sclk|Power" ; sleep 0.25; done ) > $O/smi_nf$nf.txt 2>&1 &
   SMI=$!
   sleep 1.5
-  timeout -k 10 300 python bench.py --config 2 --steps 6000 --warmup 10 --no-secondary --no-cpu-baseline --no-latency --no-host-feed --no-event-profile --single-window --in-flight $nf > $O/bench_nf$nf.json 2> $O/bench_nf$nf.err; echo "bench in-flight $nf rc $?"
+  timeout -k 10 300 python bench.py --full --config 2 --steps 6000 --warmup 10 --no-secondary --no-cpu-baseline --no-latency --no-host-feed --no-event-profile --single-window --in-flight $nf > $O/bench_nf$nf.json 2> $O/bench_nf$nf.err; echo "bench in-flight $nf rc $?"
   wait $SMI
   python3 -c "
 import json,re,sys
