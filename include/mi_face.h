@@ -126,6 +126,9 @@ size_t mi_model_describe(const mi_model *m, char *buf, size_t cap);
  * block pair behind it, from 32 f32 pictures on), "pair_fuse" (0 = two plain BlazeBlocks in a row keep a launch each where one launch has a form for
  * both: the face mesh's 48x48x32 blocks), "mdb_band" (rows per band of those launches, 0 = chosen per launch), "stem_mfma" (0 = the detectors' 5x5 first
  * convolution (f32 tensors) stays on the packed-FMA kernel instead of the matrix cores; bit-identical results).
+ * Test hook "test_poison" (0 = off, the default; 1 = 0xFF bytes, a NaN; 2 = 0x7F bytes, 3.39e38): before every run the handle fills its activation
+ * arena, its small-batch scratch, its output buffers and, in mi_model_run with host input, its input stage beyond the call's frames — a kernel that
+ * reads a byte it did not write first turns up in the results. Weights, programs and the single-launch plan's workspace are never touched.
  * Takes effect on the next run. */
 int mi_model_set_option(mi_model *m, const char *key, int value);
 /* Reads an option back (same keys), plus the state the engine keeps about the single-launch plan: "band" reads 0 once three single launches in a

@@ -68,6 +68,10 @@ void Model::invalidate_graphs() {
 }
 
 void Model::set_option(const std::string& key, int value) {
+    if (key == "test_poison") {   // test hook: fill the scratch and output buffers before every run (poison_scratch); no re-layout, no new graphs
+        test_poison_ = (value == 1 || value == 2) ? value : 0;
+        return;
+    }
     if (key == "chunk") chunk_ = std::max(0, value);
     else if (key == "graph") use_graph_ = value != 0;
     else if (key == "fuse") { fuse_level_ = std::min(5, std::max(0, value)); dirty_ = true; }
@@ -129,6 +133,7 @@ int Model::get_option(const std::string& key) const {
     if (key == "heads") return head_streams_opt_;
     if (key == "reuse") return reuse_;
     if (key == "lanes") return lanes_;
+    if (key == "test_poison") return test_poison_;
     throw std::runtime_error("unknown option '" + key + "'");
 }
 
@@ -2236,12 +2241,25 @@ bool Model::takes_u8_input() {
     return readers == 1 && stem;
 }
 
+// Test hook (option "test_poison"): every buffer a run may only read after writing it gets bytes no kernel should ever see — 0xFF (NaN) or 0x7F
+// (3.39e38: survives max / ReLU, which drop a NaN). Enqueued on the run's stream, outside any graph, so it precedes the whole run on every lane and head
+// stream (they all start behind an event on that stream). Left alone on purpose: weights, stage / tail / band programs, band constants, the band
+// workspace and its generation (packet tags start from a cleared workspace: band_before_launch) — state by design, not scratch.
+void Model::poison_scratch(hipStream_t s) {
+    const int byte = test_poison_ == 1 ? 0xFF : 0x7F;
+    if (d_arena_) hip_check(hipMemsetAsync(d_arena_, byte, std::max<size_t>(arena_floats_, 64) * sizeof(float), s), "hipMemsetAsync poison arena");
+    if (d_small_) hip_check(hipMemsetAsync(d_small_, byte, small_floats_ * sizeof(float), s), "hipMemsetAsync poison small-batch scratch");
+    for (int k = 0; k < static_cast<int>(d_out_.size()); k++)
+        if (d_out_[k]) hip_check(hipMemsetAsync(d_out_[k], byte, output_elems(k) * sizeof(float) * batch_cap_, s), "hipMemsetAsync poison outputs");
+}
+
 void Model::run_device_u8(const uint8_t* frames, long frame_bytes, int row_bytes, const float* lut, int batch, hipStream_t stream) {
     if (batch <= 0) throw std::runtime_error("batch must be positive");
     if (!frames || !lut) throw std::runtime_error("null tensor pointer");
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (!takes_u8_input()) throw std::runtime_error("plan: this graph has no u8 input form");
     ensure_capacity(batch);
+    if (test_poison_) poison_scratch(stream ? stream : stream_);
     u8_.frames = frames; u8_.lut = lut; u8_.frame_bytes = frame_bytes; u8_.row_bytes = row_bytes;
     try {
         // the graph input tensor itself is never read: `in` only has to be a stable non-null key
@@ -2263,6 +2281,7 @@ void Model::run_device(const float* in, int batch, hipStream_t stream, bool one_
     GraphKey key{in, batch, 0, 0};
     key.band = band_use_;
     hipStream_t s = stream ? stream : stream_;
+    if (test_poison_) poison_scratch(s);
     if (band_use_) band_before_launch(s);
     try {
         run_graph_or_eager(in, batch, s, key);
@@ -2389,6 +2408,8 @@ void Model::run(const float* in, int batch, float* const* outs, int mem, hipStre
             in_stage_floats_ = need;
         }
         hip_check(hipMemcpyAsync(d_in_stage_, in, need * sizeof(float), hipMemcpyHostToDevice, s), "H2D input");
+        if (test_poison_ && in_stage_floats_ > need)   // the stage beyond this call's frames (a larger earlier call's)
+            hip_check(hipMemsetAsync(d_in_stage_ + need, test_poison_ == 1 ? 0xFF : 0x7F, (in_stage_floats_ - need) * sizeof(float), s), "hipMemsetAsync poison stage");
         din = d_in_stage_;
     }
     run_device(din, batch, s);

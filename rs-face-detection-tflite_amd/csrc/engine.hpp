@@ -73,6 +73,7 @@ class Model {
     void free_bandnet();
     bool band_usable(int batch) const;
     void band_before_launch(hipStream_t s);
+    void poison_scratch(hipStream_t s);   // option "test_poison"
     void ensure_capacity(int batch);
     void enqueue_chunk(const float* in, int chunk_start, int frames, hipStream_t s, std::vector<hipEvent_t>* marks = nullptr,
                        std::vector<std::string>* labels = nullptr);
@@ -136,6 +137,7 @@ class Model {
     bool band_ran_ = false;         // the last run_device took it
     bool band_test_fail_ = false;   // option "band_test_fail"
     int band_test_absent_ = 0;      // option "band_test_absent"
+    int test_poison_ = 0;           // option "test_poison": 0 off, 1 = 0xFF bytes (NaN), 2 = 0x7F bytes (3.39e38) in scratch and outputs before every run
     int band_fail_streak_ = 0;      // single launches in a row that gave up; at 3 the handle stops using the plan (band_ = 0)
     bool band_disabled_ = false;    // ... which it did
     unsigned band_gen_ = 0;         // band launches since the workspace was last cleared (tags wrap at 2^26: band_before_launch)

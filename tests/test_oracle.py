@@ -187,3 +187,134 @@ def test_synthetic_graphs_oracles_agree_and_lower(tmp_path):
             np.testing.assert_allclose(np.asarray(a).reshape(np.asarray(b).shape), np.asarray(b), rtol=0, atol=2e-5 * max(1.0, float(np.abs(b).max())))
         sizes = [int(mi.plan_describe(blob, lvl).splitlines()[0].split()[2].split("=")[1]) for lvl in range(6)]
         assert sizes == sorted(sizes, reverse=True) and sizes[5] < sizes[0], (name, sizes)
+
+
+# ---------------------------------------------------------------- non-finite inputs, pinned against the reference's source line by line
+# Anchors at (0, 0) and scale 1: decode_boxes (face_detection.rs:274-293) then leaves the raw centre, size and keypoints as they are, so every
+# expected value below is a short f32 expression of the raw numbers.  Letterbox removal with zero padding divides by 1 (transform.rs:135-136).
+
+_F = np.float32
+
+
+def _sig(x):
+    """get_sigmoid_score (face_detection.rs:300-314): clamp to +-80 (NaN passes both comparisons), then 1 / (1 + exp(-x)) in f32."""
+    x = _F(x)
+    if x < -80:
+        x = _F(-80)
+    elif x > 80:
+        x = _F(80)
+    return _F(1) / (_F(1) + _F(np.exp(-np.float64(x))))
+
+
+def _raw(cx, cy, w, h, kp=0.25):
+    r = np.full(16, kp, np.float32)
+    r[:4] = cx, cy, w, h
+    return r
+
+
+def _dec(r):
+    """decode_boxes (face_detection.rs:274-293) at anchor (0, 0), scale 1."""
+    d = r.astype(np.float32).copy()
+    half_x, half_y = d[2] / _F(2), d[3] / _F(2)
+    c_x, c_y = d[0], d[1]
+    d[0], d[1], d[2], d[3] = c_x - half_x, c_y - half_y, c_x + half_x, c_y + half_y
+    return d
+
+
+def _merge(dets_scores):
+    """The weighted average of nms.rs:94-110 over candidates in sorted order: w += d * score, total += score, w / total, all f32."""
+    w = np.zeros(16, np.float32)
+    total = _F(0)
+    for d, s in dets_scores:
+        total = _F(total + s)
+        w = (w + d * s).astype(np.float32)
+    return (w / total).astype(np.float32)
+
+
+def _post(oracle, raws, logits):
+    rb = np.stack(raws).astype(np.float32)
+    return oracle.fd_postprocess(rb, np.asarray(logits, np.float32), np.zeros((len(raws), 2), np.float32), 1.0)
+
+
+def _row(d, s):
+    return np.append(d, s).astype(np.float32)
+
+
+def test_oracle_pin_nan_score_is_dropped(oracle):
+    """A NaN logit survives the clamp (face_detection.rs:302-306 compare false both ways), its sigmoid is NaN and `score > MIN_SCORE` is false
+    (326): the detection never reaches the sort (whose partial_cmp().unwrap() would panic on it, nms.rs:137)."""
+    a, b = _raw(0.5, 0.5, 0.2, 0.2), _raw(0.5, 0.5, 0.2, 0.2, kp=0.75)
+    got = _post(oracle, [a, b], [np.nan, 3.0])
+    s = _sig(3.0)
+    np.testing.assert_array_equal(got, [_row(_merge([(_dec(b), s)]), s)])
+
+
+def test_oracle_pin_nan_corner_is_rejected(oracle):
+    """is_valid (face_detection.rs:318-323) is `x1 > x0` for both rows: a NaN centre or size makes a comparison false and drops the box,
+    whatever its score."""
+    a = _raw(np.nan, 0.5, 0.2, 0.2)
+    b = _raw(0.5, 0.5, 0.2, np.nan)
+    c = _raw(0.3, 0.3, 0.1, 0.1)
+    got = _post(oracle, [a, b, c], [5.0, 4.0, 2.0])
+    s = _sig(2.0)
+    np.testing.assert_array_equal(got, [_row(_merge([(_dec(c), s)]), s)])
+
+
+def test_oracle_pin_nan_keypoint_propagates_into_its_cluster_only(oracle):
+    """Keypoints take no part in the IoU (types.rs:219-225 reads features 0-3): the NaN keypoint's detection merges with its neighbour
+    (nms.rs:83-92) and the NaN lands in that one feature of that one output (102-109); the disjoint cluster behind it stays finite."""
+    a = _raw(0.5, 0.5, 0.2, 0.2)
+    a[9] = np.nan
+    b = _raw(0.51, 0.5, 0.2, 0.2, kp=0.5)
+    c = _raw(0.1, 0.1, 0.05, 0.05)
+    got = _post(oracle, [a, b, c], [4.0, 3.0, 2.0])
+    sa, sb, sc = _sig(4.0), _sig(3.0), _sig(2.0)
+    want0 = _merge([(_dec(a), sa), (_dec(b), sb)])
+    assert np.isnan(want0[9]) and np.isfinite(np.delete(want0, 9)).all()
+    np.testing.assert_array_equal(got, [_row(want0, sa), _row(_merge([(_dec(c), sc)]), sc)])
+
+
+def test_oracle_pin_infinite_box_after_the_head_stops_the_loop(oracle):
+    """An infinite-size box is valid (-Inf < Inf).  Against a finite head it has IoU 0 (den = a + Inf - a = Inf, nms.rs:8-10); as head its
+    self-IoU is 0 too (den = Inf + Inf - Inf = NaN, and `NaN > 0.0` is false), so its candidate set is empty: it is output as a clone (81, 112
+    not reached) and, nothing having left `remaining`, the loop stops (117-119) — the finite box behind it is never output."""
+    a = _raw(0.5, 0.5, 0.2, 0.2)
+    inf = _raw(0.5, 0.5, np.inf, np.inf, kp=0.125)
+    c = _raw(0.1, 0.1, 0.05, 0.05)
+    got = _post(oracle, [a, inf, c], [4.0, 3.0, 2.0])
+    sa, si = _sig(4.0), _sig(3.0)
+    d_inf = _dec(inf)
+    assert d_inf[0] == -np.inf and d_inf[2] == np.inf
+    np.testing.assert_array_equal(got, [_row(_merge([(_dec(a), sa)]), sa), _row(d_inf, si)])
+
+
+def test_oracle_pin_infinite_head_hides_every_finite_box(oracle):
+    """The infinite box as the head: the finite boxes behind it (one of which overlaps another) never become candidates of it, its own
+    candidate set is empty, it is output as a clone and the loop ends (nms.rs:81, 117-119): one output."""
+    inf = _raw(0.5, 0.5, np.inf, 0.3)
+    b = _raw(0.5, 0.5, 0.2, 0.2)
+    c = _raw(0.52, 0.5, 0.2, 0.2)
+    got = _post(oracle, [b, inf, c], [4.0, 5.0, 3.0])
+    np.testing.assert_array_equal(got, [_row(_dec(inf), _sig(5.0))])
+
+
+def test_oracle_pin_tied_scores_keep_anchor_order(oracle):
+    """sort_by is stable (nms.rs:137): equal scores keep the anchor order, so the first of three tied detections is the head, the overlapping
+    third is merged into it in that order and the disjoint second comes out next."""
+    a = _raw(0.5, 0.5, 0.2, 0.2)
+    b = _raw(0.1, 0.1, 0.05, 0.05, kp=0.5)
+    c = _raw(0.5, 0.52, 0.2, 0.2, kp=0.75)
+    got = _post(oracle, [a, b, c], [3.0, 3.0, 3.0])
+    s = _sig(3.0)
+    np.testing.assert_array_equal(got, [_row(_merge([(_dec(a), s), (_dec(c), s)]), s), _row(_merge([(_dec(b), s)]), s)])
+
+
+def test_oracle_pin_infinite_logits_clamp_to_80(oracle):
+    """+-Inf logits clamp to +-80 (face_detection.rs:302-306): +Inf scores exactly 1.0 (ties with a logit of 80; the stable sort keeps the
+    anchor order), -Inf scores ~1.8e-35 and is dropped."""
+    a = _raw(0.5, 0.5, 0.2, 0.2)
+    b = _raw(0.5, 0.5, 0.2, 0.2, kp=0.5)
+    c = _raw(0.1, 0.1, 0.05, 0.05)
+    got = _post(oracle, [a, b, c], [np.inf, -np.inf, 80.0])
+    assert _sig(np.inf) == 1.0 and _sig(-np.inf) < 1e-30
+    np.testing.assert_array_equal(got, [_row(_dec(a), 1.0), _row(_dec(c), 1.0)])
