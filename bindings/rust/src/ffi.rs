@@ -1,7 +1,7 @@
 //! Raw declarations of `include/mi_face.h` (the drop-in boundary).  One `extern "C"` item per C entry point the three
 //! `infer` paths and their helpers use; layouts are `#[repr(C)]` mirrors of `mi_detection`, `mi_rect`, `mi_landmark`.
 #![allow(non_camel_case_types)]
-use std::os::raw::{c_char, c_double, c_float, c_int, c_void};
+use std::os::raw::{c_char, c_double, c_float, c_int, c_long, c_void};
 
 pub const MI_OK: c_int = 0;
 pub const MI_MEM_HOST: c_int = 0;
@@ -37,6 +37,53 @@ pub struct mi_landmark {
     pub x: c_double,
     pub y: c_double,
     pub z: c_double,
+}
+
+/// `Color` as the bytes `render_to_image` writes — render.rs:6-26,431
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct mi_color {
+    pub r: u8,
+    pub g: u8,
+    pub b: u8,
+    pub a: u8,
+}
+
+pub const MI_ANN_POINTS: c_int = 0;
+pub const MI_ANN_LINES: c_int = 1;
+pub const MI_ANN_RECTS: c_int = 2;
+pub const MI_ANN_FILLED_RECTS: c_int = 3;
+
+/// `Annotation` — render.rs:207-213: `count` items whose doubles start at index `first` of a frame's coordinate block
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mi_annotation {
+    pub kind: c_int,
+    pub first: c_int,
+    pub count: c_int,
+    pub thickness: c_double,
+    pub color: mi_color,
+    pub normalized: c_int,
+}
+
+/// arguments of `detections_to_render_data` / `face_landmarks_to_render_data` / `eye_landmarks_to_render_data`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mi_render_style {
+    pub draw_bounds: c_int,
+    pub bounds_color: mi_color,
+    pub line_width: c_int,
+    pub draw_keypoints: c_int,
+    pub keypoint_color: mi_color,
+    pub point_width: c_int,
+    pub draw_mesh: c_int,
+    pub mesh_landmark_color: mi_color,
+    pub mesh_connection_color: mi_color,
+    pub mesh_thickness: c_float,
+    pub draw_eyes: c_int,
+    pub eye_landmark_color: mi_color,
+    pub eye_connection_color: mi_color,
+    pub eye_thickness: c_float,
 }
 
 #[repr(C)] pub struct mi_fd { _private: [u8; 0] }
@@ -120,4 +167,13 @@ extern "C" {
     pub fn mi_pipeline_run(p: *mut mi_pipeline, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,
                            faces: *mut mi_detection, face_counts: *mut c_int, landmarks: *mut c_float, present: *mut c_int,
                            eyes: *mut c_float, mem: c_int, stream: *mut c_void) -> c_int;
+
+    // render.rs:262-479 on the device
+    pub fn mi_render_annotations(device: c_int, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,
+                                 anns: *const mi_annotation, n_anns: c_int, coords: *const c_double, coords_per_frame: c_long, out: *mut u8,
+                                 out_channels: c_int, out_stride: c_int, skipped: *mut c_int, mem: c_int, stream: *mut c_void) -> c_int;
+    pub fn mi_render_faces(device: c_int, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,
+                           faces: *const mi_detection, face_counts: *const c_int, faces_per_frame: c_int, landmarks: *const c_float,
+                           present: *const c_int, eyes: *const c_float, style: *const mi_render_style, out: *mut u8, out_channels: c_int,
+                           out_stride: c_int, skipped: *mut c_int, mem: c_int, stream: *mut c_void) -> c_int;
 }

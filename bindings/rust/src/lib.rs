@@ -7,7 +7,7 @@
 //!
 //! Reference files mirrored (paths relative to the reference's `src/face_detection_lite/`):
 //! `types.rs` -> [`types`], `face_detection.rs:117-267` -> [`face_detection`], `face_landmark.rs:168-306` ->
-//! [`face_landmark`], `iris_landmark.rs:115-292,380-398` -> [`iris_landmark`], `utils.rs:8-21` -> [`utils`].
+//! [`face_landmark`], `iris_landmark.rs:115-292,380-398` -> [`iris_landmark`], `utils.rs:8-21` -> [`utils`], `render.rs` -> [`render`].
 //!
 //! Concurrency: the reference's handles are immutable after `new`, and `infer(&self)` may run on several threads.  The
 //! handles here own device state (activation arena, replay graphs), so libmiface serialises the calls made on one handle
@@ -18,10 +18,12 @@ pub mod types;
 pub mod face_detection;
 pub mod face_landmark;
 pub mod iris_landmark;
+pub mod render;
 pub mod utils;
 
 pub use face_detection::{FaceDetection, FaceDetectionModel};
 pub use face_landmark::{face_detection_to_roi, FaceLandmark};
+pub use render::{detections_to_render_data, landmarks_to_render_data, render_to_image, Annotation, AnnotationData, Color, Colors};
 pub use iris_landmark::{iris_roi_from_face_landmarks, update_face_landmarks_with_iris_results, IrisLandmark};
 pub use types::{BBox, Detection, Image, IrisResults, Landmark, Rect};
 

@@ -361,6 +361,104 @@ int mi_image_to_tensor(int device, const uint8_t *rgb, int width, int height, in
                        int flip_horizontal, float *out, double padding_out[4], int mem, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * render.rs — annotations drawn on the device (render.rs:262-479, face_landmark.rs:35-166,324-339,
+ * iris_landmark.rs:44-62,312-331; the three imageproc 0.25.0 primitives render_to_image draws through)
+ * ---------------------------------------------------------------------------------------------------------------- */
+
+/* Color { r, g, b, a } — render.rs:6-26, as the bytes render_to_image writes (`color.r as u8`, `color.a.unwrap_or(255) as u8`,
+ * render.rs:431).  The MI_COLOR_* initialisers are Colors::{BLACK, RED, GREEN, BLUE, PINK, WHITE} (render.rs:28-68) with the
+ * alpha render_to_image gives them: `mi_color c = MI_COLOR_RED;`. */
+typedef struct mi_color {
+    uint8_t r, g, b, a;
+} mi_color;
+#define MI_COLOR_BLACK {0, 0, 0, 255}
+#define MI_COLOR_RED {255, 0, 0, 255}
+#define MI_COLOR_GREEN {0, 255, 0, 255}
+#define MI_COLOR_BLUE {0, 0, 255, 255}
+#define MI_COLOR_PINK {255, 0, 255, 255}
+#define MI_COLOR_WHITE {255, 255, 255, 255}
+
+/* AnnotationData variants — render.rs:186-192: doubles per item 2 (x, y), 4 (x_start, y_start, x_end, y_end),
+ * 4 (left, top, right, bottom), 4 (the same). */
+enum { MI_ANN_POINTS = 0, MI_ANN_LINES = 1, MI_ANN_RECTS = 2, MI_ANN_FILLED_RECTS = 3 };
+
+/* Annotation { data, normalized_positions, thickness, color } — render.rs:207-213.  `data` is `count` items of one kind whose
+ * doubles start at index `first` of a frame's coordinate block: first + count * (doubles per item) <= coords_per_frame. */
+typedef struct mi_annotation {
+    int kind;
+    int first, count;
+    double thickness;
+    mi_color color;
+    int normalized;
+} mi_annotation;
+
+/* render_to_image(annotations, image, blend_mode) — render.rs:361-479, over `batch` equally sized frames: the same annotation
+ * list for every frame, each frame with its own positions (coords [batch][coords_per_frame] f64).
+ *   canvas   to_rgba8 of the RGB frame, alpha 255 (render.rs:365).  out_channels 4: `out` is that RGBA picture; 3: alpha is
+ *            dropped, and `out` may then BE `frames` (in place) when out_stride == stride; any other overlap of the two is
+ *            MI_EINVAL.  Rows of `out` are out_stride bytes, frames out_stride*height bytes apart; the bytes of a row beyond
+ *            out_channels*width are never written.
+ *   order    annotations in list order, items in list order; a later draw overwrites an earlier one (no blending: blend_mode is
+ *            read and never used, render.rs:362), the colour's alpha byte is written as it is.
+ *   casts    normalised positions are multiplied by (width, height) in f64 (render.rs:368-406); every cast is Rust's `as`:
+ *            truncation toward zero, saturation, NaN -> 0.
+ *   points   render.rs:423-433: half = max(thickness as u32 / 2, 1); the filled square of side 2*half at
+ *            ((x - half) as i32, (y - half) as i32), x = px as u32 (u32 wrapping subtraction), clipped to the canvas.
+ *   lines    render.rs:434-445 + imageproc's BresenhamLineIter on the (as i32 as f32) end points; the thickness is ignored.
+ *   rects    render.rs:446-462 (rectangle and "oval" draw the same): Rect::at(left as i32, top as i32).of_size((right - left)
+ *            as u32, (bottom - top) as u32), four segments with right = left + w - 1, bottom = top + h - 1.
+ *   filled   render.rs:463-473: the same rectangle, filled, clipped to the canvas.  Its colour is the annotation's: a
+ *            FilledRectOrOval's own `fill` (render.rs:466) makes a caller split an annotation where the fill changes.
+ * Two deviations, because nothing panics or spins across this ABI; both are counted per frame in skipped[batch] (may be NULL):
+ *   1. a rectangle whose of_size width or height is 0 (imageproc panics) is not drawn;
+ *   2. a line is walked for at most max(width, height) steps, whatever its length: the part of the walk in front of the canvas
+ *      is skipped in closed form (integer arithmetic on 2*error), which is exact while every f32 value of the walk is exact.
+ *      That holds for |coordinate| <= 2^20 after the i32 cast; a line with an end point beyond that bound — or a hollow
+ *      rectangle with an edge beyond it — is not drawn (the reference would walk up to 2^32 steps).
+ * anns is HOST memory whatever `mem` says (structure, not data); frames / coords / out / skipped follow `mem`.  The call
+ * returns after its work has finished (the annotation list is staged per call). */
+int mi_render_annotations(int device, const uint8_t *frames, int batch, int width, int height, int stride,
+                          const mi_annotation *anns, int n_anns, const double *coords, long coords_per_frame, uint8_t *out,
+                          int out_channels, int out_stride, int *skipped, int mem, void *stream);
+
+/* The arguments of detections_to_render_data (render.rs:262-265), face_landmarks_to_render_data (face_landmark.rs:324-339) and
+ * eye_landmarks_to_render_data (iris_landmark.rs:312-331).  draw_* = 0 is the reference's `None` colour (render.rs:272,284) /
+ * a group the caller leaves out; bounds and keypoints are also gated by line_width > 0 / point_width > 0 (render.rs:273,285).
+ * The thicknesses of the landmark groups are f32 as the reference's Option<f32> (render.rs:317,322). */
+typedef struct mi_render_style {
+    int draw_bounds;
+    mi_color bounds_color;
+    int line_width;
+    int draw_keypoints;
+    mi_color keypoint_color;
+    int point_width;
+    int draw_mesh;
+    mi_color mesh_landmark_color, mesh_connection_color;
+    float mesh_thickness;
+    int draw_eyes;
+    mi_color eye_landmark_color, eye_connection_color;
+    float eye_thickness;
+} mi_render_style;
+
+/* detections_to_render_data + face_landmarks_to_render_data + 2 x eye_landmarks_to_render_data + render_to_image (lib.rs:42-83)
+ * on what mi_pipeline_run / mi_fd_infer_images left in memory; with MI_MEM_DEVICE no coordinate visits the host.  Canvas
+ * arguments, drawing rules and skipped[] as mi_render_annotations.  Any of the three groups may be NULL; the annotations are
+ * built on the device in this order (all positions normalised, f32 widened to f64 before the multiply as Detection::bbox —
+ * types.rs:219-225 — and Landmark do):
+ *   faces      [batch][faces_per_frame] + face_counts [batch] (min(count, faces_per_frame) faces, none when negative):
+ *              the bounds annotation (hollow rectangles, thickness line_width), then the keypoints annotation: all 8 rows of
+ *              `data` of every face, the two box corners included (render.rs:289-299), thickness point_width.
+ *   landmarks  f32 [batch][468][3], drawn where present[b] != 0 (present NULL: everywhere): the 124 lines of
+ *              FACE_LANDMARK_CONNECTIONS (face_landmark.rs:35-166), then the 468 points.
+ *   eyes       f32 [batch][2][76][3], gated like the mesh: for the left eye, then the right eye, the 15 lines of
+ *              EYE_LANDMARK_CONNECTIONS (iris_landmark.rs:44-60) over the first 15 contour points, then those 15 points.
+ * With MI_MEM_DEVICE and a caller stream the call is asynchronous. */
+int mi_render_faces(int device, const uint8_t *frames, int batch, int width, int height, int stride, const mi_detection *faces,
+                    const int *face_counts, int faces_per_frame, const float *landmarks, const int *present, const float *eyes,
+                    const mi_render_style *style, uint8_t *out, int out_channels, int out_stride, int *skipped, int mem,
+                    void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU: the one exchange of the sharded path — the frozen .tflite bytes go once from `root` to
  * every rank over RCCL (ncclBroadcast, ncclUint8, xGMI inside a node); every rank then builds its handles with
  * mi_*_create_from_bytes (the counterpart of FlatBufferModel::build_from_file, face_detection.rs:188, on ranks that have no

@@ -325,4 +325,36 @@ inline std::vector<Landmark> update_face_landmarks_with_iris_results(const std::
     return out;
 }
 
+// render.rs on the device (include/mi_face.h, "render.rs").  Colors::{BLACK, ...} (render.rs:28-68) as the bytes render_to_image writes.
+struct Colors {
+    static constexpr mi_color BLACK = MI_COLOR_BLACK, RED = MI_COLOR_RED, GREEN = MI_COLOR_GREEN, BLUE = MI_COLOR_BLUE, PINK = MI_COLOR_PINK,
+                              WHITE = MI_COLOR_WHITE;
+};
+// One picture of render_to_image's result: RGBA rows of 4 * width bytes; `skipped` = items the C entry did not draw (empty
+// rectangles, lines beyond 2^20 px).
+struct RgbaImage {
+    std::vector<std::uint8_t> rgba;
+    int width = 0, height = 0, skipped = 0;
+};
+// render_to_image(annotations, image, blend_mode) (render.rs:361-479) for one picture in host memory: `annotations` index into `coords`
+inline RgbaImage render_to_image(const std::vector<mi_annotation>& annotations, const std::vector<double>& coords, const Image& image, int device = 0) {
+    RgbaImage o;
+    o.width = image.width;
+    o.height = image.height;
+    o.rgba.resize(static_cast<std::size_t>(4) * image.width * image.height);
+    detail::check(mi_render_annotations(device, image.rgb, 1, image.width, image.height, image.stride, annotations.data(),
+                                        static_cast<int>(annotations.size()), coords.data(), static_cast<long>(coords.size()), o.rgba.data(), 4,
+                                        4 * image.width, &o.skipped, MI_MEM_HOST, nullptr));
+    return o;
+}
+// detections_to_render_data / face_landmarks_to_render_data / eye_landmarks_to_render_data + render_to_image (lib.rs:42-83) on the raw
+// results of mi_pipeline_run / mi_fd_infer_images, wherever they live (`mem`); any of the three groups may be null.
+inline void render_faces(const std::uint8_t* frames, int batch, int width, int height, int stride, const mi_detection* faces, const int* face_counts,
+                         int faces_per_frame, const float* landmarks, const int* present, const float* eyes, const mi_render_style& style,
+                         std::uint8_t* out, int out_channels, int out_stride, int* skipped = nullptr, int mem = MI_MEM_HOST, void* stream = nullptr,
+                         int device = 0) {
+    detail::check(mi_render_faces(device, frames, batch, width, height, stride, faces, face_counts, faces_per_frame, landmarks, present, eyes, &style,
+                                  out, out_channels, out_stride, skipped, mem, stream));
+}
+
 }  // namespace mi_face

@@ -40,6 +40,7 @@ EXPORTS = [
     "mi_iris_infer_image",
     "mi_pipeline_create", "mi_pipeline_create_from_bytes", "mi_pipeline_model", "mi_pipeline_free", "mi_pipeline_set_option", "mi_pipeline_run",
     "mi_bbox_to_roi", "mi_bbox_from_landmarks", "mi_face_detection_to_roi", "mi_iris_roi_from_face_landmarks", "mi_update_face_landmarks_with_iris_results", "mi_image_to_tensor", "mi_jpeg_info", "mi_jpeg_decode_rgb",
+    "mi_render_annotations", "mi_render_faces",
 ]
 
 
@@ -65,6 +66,60 @@ class Rect(C.Structure):
 
 class CLandmark(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double)]
+
+
+class Color(C.Structure):
+    """render.rs:6-26 as the four bytes render_to_image writes (alpha None -> 255, render.rs:431)."""
+    _fields_ = [("r", C.c_uint8), ("g", C.c_uint8), ("b", C.c_uint8), ("a", C.c_uint8)]
+
+    def __init__(self, r=0, g=0, b=0, a=255):
+        super().__init__(int(r), int(g), int(b), 255 if a is None else int(a))
+
+    def as_tuple(self):
+        return self.r, self.g, self.b, self.a
+
+    def __repr__(self):
+        return "Color(%d, %d, %d, %d)" % self.as_tuple()
+
+
+class Colors:
+    """render.rs:28-68."""
+    BLACK = Color(0, 0, 0)
+    RED = Color(255, 0, 0)
+    GREEN = Color(0, 255, 0)
+    BLUE = Color(0, 0, 255)
+    PINK = Color(255, 0, 255)
+    WHITE = Color(255, 255, 255)
+
+
+ANN_POINTS, ANN_LINES, ANN_RECTS, ANN_FILLED_RECTS = 0, 1, 2, 3     # AnnotationData variants, render.rs:186-192
+_ANN_DOUBLES = {ANN_POINTS: 2, ANN_LINES: 4, ANN_RECTS: 4, ANN_FILLED_RECTS: 4}
+
+
+class Annotation(C.Structure):
+    """mi_annotation (render.rs:207-213): `count` items of one kind whose doubles start at index `first` of a frame's coordinate block."""
+    _fields_ = [("kind", C.c_int), ("first", C.c_int), ("count", C.c_int), ("thickness", C.c_double), ("color", Color), ("normalized", C.c_int)]
+
+    def __init__(self, kind=ANN_POINTS, first=0, count=0, thickness=1.0, color=None, normalized=True):
+        super().__init__(int(kind), int(first), int(count), float(thickness), color if color is not None else Colors.RED, int(bool(normalized)))
+
+
+class RenderStyle(C.Structure):
+    """mi_render_style: the arguments of detections_to_render_data (render.rs:262-265), face_landmarks_to_render_data
+    (face_landmark.rs:324-339) and eye_landmarks_to_render_data (iris_landmark.rs:312-331).  A colour of None is the reference's None
+    (bounds / keypoints not drawn); mesh / eyes say whether those groups are drawn at all."""
+    _fields_ = [("draw_bounds", C.c_int), ("bounds_color", Color), ("line_width", C.c_int),
+                ("draw_keypoints", C.c_int), ("keypoint_color", Color), ("point_width", C.c_int),
+                ("draw_mesh", C.c_int), ("mesh_landmark_color", Color), ("mesh_connection_color", Color), ("mesh_thickness", C.c_float),
+                ("draw_eyes", C.c_int), ("eye_landmark_color", Color), ("eye_connection_color", Color), ("eye_thickness", C.c_float)]
+
+    def __init__(self, bounds_color=None, keypoint_color=None, line_width=1, point_width=1, mesh=False, mesh_landmark_color=None,
+                 mesh_connection_color=None, mesh_thickness=1.0, eyes=False, eye_landmark_color=None, eye_connection_color=None, eye_thickness=1.0):
+        red = lambda c: c if c is not None else Colors.RED      # landmark_color.unwrap_or(Colors::RED), render.rs:320-321
+        super().__init__(int(bounds_color is not None), bounds_color or Colors.BLACK, int(line_width),
+                         int(keypoint_color is not None), keypoint_color or Colors.BLACK, int(point_width),
+                         int(bool(mesh)), red(mesh_landmark_color), red(mesh_connection_color), float(mesh_thickness),
+                         int(bool(eyes)), red(eye_landmark_color), red(eye_connection_color), float(eye_thickness))
 
 
 class FaceDetectionModel(enum.IntEnum):
@@ -247,6 +302,10 @@ def lib():
     L.mi_jpeg_decode_rgb.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]
     L.mi_image_to_tensor.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, C.c_int, C.c_int,
                                      C.c_double, C.c_double, C.c_int, vp, dp, C.c_int, vp]
+    L.mi_render_annotations.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Annotation), C.c_int, vp, C.c_long, vp, C.c_int,
+                                        C.c_int, vp, C.c_int, vp]
+    L.mi_render_faces.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.POINTER(RenderStyle), vp, C.c_int,
+                                  C.c_int, vp, C.c_int, vp]
     _lib = L
     return L
 
@@ -888,6 +947,105 @@ class Pipeline:
         _check(self.L.mi_pipeline_run(self.h, p, B, W, H, stride, _ptr(out["faces"])[0], _ptr(out["face_counts"])[0],
                                       _ptr(out["landmarks"])[0], _ptr(out["present"])[0], _ptr(out["eyes"])[0], mem, C.c_void_p(stream or 0)))
         return out
+
+
+def _picture(x, channels, what):
+    """(pointer, mem, B, H, W, row stride in bytes) of a batch of pictures: uint8 [B,H,W,channels], numpy or a torch CUDA tensor; rows may be
+    padded (a view of a wider buffer) as long as the pixels of a row are dense and frames lie stride * H bytes apart."""
+    if x.ndim != 4 or x.shape[3] != channels or str(x.dtype).split(".")[-1] != "uint8":
+        raise ValueError("%s must be uint8 [B,H,W,%d]" % (what, channels))
+    B, H, W = (int(v) for v in x.shape[:3])
+    if _is_torch(x):
+        st, mem = [int(v) for v in x.stride()], (MI_MEM_DEVICE if x.is_cuda else MI_MEM_HOST)
+        p = C.c_void_p(x.data_ptr())
+    else:
+        st, mem, p = [int(v) for v in x.strides], MI_MEM_HOST, C.c_void_p(x.ctypes.data)
+    if st[3] != 1 or st[2] != channels or (B > 1 and st[0] != st[1] * H):
+        raise ValueError("%s: pixels must be dense and frames stride * H bytes apart" % what)
+    return p, mem, B, H, W, st[1]
+
+
+def _render_out(frames, mem, B, H, W, out, out_channels):
+    if out is None:
+        if mem == MI_MEM_DEVICE:
+            import torch
+            out = torch.empty((B, H, W, out_channels), dtype=torch.uint8, device=frames.device)
+        else:
+            out = np.empty((B, H, W, out_channels), np.uint8)
+    po, memo, Bo, Ho, Wo, ostride = _picture(out, out_channels, "out")
+    if memo != mem or (Bo, Ho, Wo) != (B, H, W):
+        raise ValueError("out must live where frames live and have their batch and size")
+    return out, po, ostride
+
+
+def _render_operand(x, mem, device, dtype, what):
+    """pointer of an operand that follows `mem` (None stays None); host operands are made contiguous arrays of `dtype`"""
+    if x is None:
+        return None, None
+    if mem == MI_MEM_DEVICE:
+        if not (_is_torch(x) and x.is_cuda and x.is_contiguous() and str(x.dtype) == "torch." + dtype):
+            raise ValueError("%s must be a contiguous %s CUDA tensor when the frames are" % (what, dtype))
+        return C.c_void_p(x.data_ptr()), x
+    x = np.ascontiguousarray(x, getattr(np, dtype))
+    return C.c_void_p(x.ctypes.data), x
+
+
+def _skipped_buffer(mem, B, frames):
+    if mem == MI_MEM_DEVICE:
+        import torch
+        return torch.zeros((B,), dtype=torch.int32, device=frames.device)
+    return np.zeros((B,), np.int32)
+
+
+def render_annotations(frames, annotations, coords, out=None, out_channels=4, device=0, stream=None):
+    """render_to_image (render.rs:361-479) over a batch, on the GPU: frames uint8 [B,H,W,3] (numpy or a torch CUDA tensor), `annotations` a
+    sequence of Annotation (the same list for every frame), coords float64 [B, coords_per_frame] in the memory of the frames.  out: None (a new
+    [B,H,W,out_channels] picture), a buffer of that shape, or `frames` itself with out_channels 3 (in place).
+    -> (out, skipped int32 [B]: rectangles of size zero and lines beyond 2^20 px that were not drawn, see include/mi_face.h)."""
+    p, mem, B, H, W, stride = _picture(frames, 3, "frames")
+    if mem == MI_MEM_DEVICE:
+        _device_ready(frames, device, None, "uint8")
+    out, po, ostride = _render_out(frames, mem, B, H, W, out, out_channels)
+    pc, coords = _render_operand(coords, mem, device, "float64", "coords")
+    per_frame = int(coords.shape[1]) if coords is not None and coords.ndim == 2 and int(coords.shape[0]) == B else -1
+    if coords is not None and per_frame < 0:
+        raise ValueError("coords must be [B, coords_per_frame]")
+    anns = (Annotation * max(len(annotations), 1))(*annotations)
+    skipped = _skipped_buffer(mem, B, frames)
+    _check(lib().mi_render_annotations(device, p, B, W, H, stride, anns, len(annotations), pc, max(per_frame, 0), po, out_channels, ostride,
+                                       _ptr(skipped)[0], mem, C.c_void_p(stream or 0)))
+    return out, skipped
+
+
+def render_faces(frames, faces=None, face_counts=None, landmarks=None, present=None, eyes=None, style=None, out=None, out_channels=4, device=0,
+                 stream=None):
+    """detections_to_render_data + face_landmarks_to_render_data + eye_landmarks_to_render_data + render_to_image (lib.rs:42-83) on what
+    Pipeline.run / FaceDetection.infer_images returned, in the memory they returned it in: faces float32 [B,17] or [B,F,17] with face_counts
+    int32 [B], landmarks float32 [B,468,3] and eyes float32 [B,2,76,3] with present int32 [B]; any group may be None.  style: RenderStyle.
+    With CUDA tensors nothing visits the host, and with a caller stream the call is asynchronous.  -> (out, skipped int32 [B])."""
+    p, mem, B, H, W, stride = _picture(frames, 3, "frames")
+    if mem == MI_MEM_DEVICE:
+        _device_ready(frames, device, None, "uint8")
+    out, po, ostride = _render_out(frames, mem, B, H, W, out, out_channels)
+    per_frame = 0
+    if faces is not None:
+        per_frame = 1 if faces.ndim == 2 else int(faces.shape[1])
+        if int(faces.shape[0]) != B or int(faces.shape[-1]) != 17 or face_counts is None:
+            raise ValueError("faces must be [B,17] or [B,F,17] and come with face_counts [B]")
+    for x, shape, what in ((landmarks, (B, NUM_FACE_LANDMARKS, 3), "landmarks"), (eyes, (B, 2, NUM_EYE_LANDMARKS + NUM_IRIS_LANDMARKS, 3), "eyes"),
+                           (face_counts, (B,), "face_counts"), (present, (B,), "present")):
+        if x is not None and tuple(int(v) for v in x.shape) != shape:
+            raise ValueError("%s must have shape %s" % (what, list(shape)))
+    pf, faces = _render_operand(faces, mem, device, "float32", "faces")
+    pn, face_counts = _render_operand(face_counts, mem, device, "int32", "face_counts")
+    pl, landmarks = _render_operand(landmarks, mem, device, "float32", "landmarks")
+    pp, present = _render_operand(present, mem, device, "int32", "present")
+    pe, eyes = _render_operand(eyes, mem, device, "float32", "eyes")
+    style = style if style is not None else RenderStyle()
+    skipped = _skipped_buffer(mem, B, frames)
+    _check(lib().mi_render_faces(device, p, B, W, H, stride, pf, pn, per_frame, pl, pp, pe, C.byref(style), po, out_channels, ostride,
+                                 _ptr(skipped)[0], mem, C.c_void_p(stream or 0)))
+    return out, skipped
 
 
 def _pipeline_submit_jpeg(self, slot, im_bytes):

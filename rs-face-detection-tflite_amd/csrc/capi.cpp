@@ -27,6 +27,7 @@
 #include "kernels.hpp"
 #include "jpeg.hpp"
 #include "preproc.hpp"
+#include "render.hpp"
 
 namespace {
 
@@ -2172,6 +2173,127 @@ int mi_image_to_tensor(int device, const uint8_t* rgb, int width, int height, in
                                    flip_horizontal != 0, d_out, padding_out, img.get(mi::image_to_tensor_scratch_bytes(width, height, stride, roi, out_w, out_h, keep_aspect_ratio != 0)), s);
         if (mem == MI_MEM_HOST) mi::hip_check(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, s), "D2H tensor");
         mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    });
+}
+
+extern "C++" {
+namespace {
+// bytes `batch` frames of `height` rows own: the last row owns row_bytes, not a whole stride
+size_t picture_bytes(int batch, int height, int stride, size_t row_bytes) {
+    return static_cast<size_t>(stride) * height * (batch - 1) + static_cast<size_t>(stride) * (height - 1) + row_bytes;
+}
+
+// everything mi_render_annotations and mi_render_faces check about their pictures, before any device is touched
+void render_check_canvas(const uint8_t* frames, int batch, int width, int height, int stride, const uint8_t* out, int out_channels, int out_stride,
+                         int mem) {
+    require(frames && out, "null argument");
+    require(mem == MI_MEM_HOST || mem == MI_MEM_DEVICE, "mem must be MI_MEM_HOST or MI_MEM_DEVICE");
+    require(batch > 0 && width > 0 && height > 0, "bad frame geometry");
+    require(stride >= 3 * static_cast<long>(width), "stride is smaller than 3 * width");
+    require(out_channels == 3 || out_channels == 4, "out_channels must be 3 (RGB) or 4 (RGBA)");
+    require(out_stride >= out_channels * static_cast<long>(width), "out_stride is smaller than out_channels * width");
+    if (out == frames) {
+        require(out_channels == 3 && out_stride == stride, "out may be frames (in place) only with out_channels 3 and out_stride == stride");
+        return;
+    }
+    const uint8_t* in_end = frames + picture_bytes(batch, height, stride, static_cast<size_t>(3) * width);
+    const uint8_t* out_end = out + picture_bytes(batch, height, out_stride, static_cast<size_t>(out_channels) * width);
+    require(out_end <= frames || in_end <= out, "out overlaps frames (only out == frames, in place, is an alias this call accepts)");
+}
+
+// The part the two render entries share: staging of the pictures for host callers (tight rows on the device), the canvas phase, the
+// draw phase (`draw(canvas, d_skipped, stream)` stages its own operands and launches), the way back.  Rows travel back without
+// their padding: the bytes of the caller's rows beyond out_channels * width are never written.
+template <class Draw>
+void render_run(int device, const uint8_t* frames, int batch, int width, int height, int stride, uint8_t* out, int out_channels, int out_stride,
+                int* skipped, int mem, void* stream, bool always_wait, Draw draw) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) throw ApiError(MI_EDEVICE, "no such HIP device (the renderer runs on the GPU; no CPU fallback exists)");
+    mi::hip_check(hipSetDevice(device), "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceBuf b_frames, b_out, b_skipped;
+    mi::RenderCanvas cv{frames, out, batch, width, height, stride, out_stride, out_channels};
+    int* d_skipped = skipped;
+    const size_t rows = static_cast<size_t>(batch) * height, in_row = static_cast<size_t>(3) * width, out_row = static_cast<size_t>(out_channels) * width;
+    if (mem == MI_MEM_HOST) {
+        auto* d_frames = static_cast<uint8_t*>(b_frames.get(rows * in_row));
+        mi::hip_check(hipMemcpy2DAsync(d_frames, in_row, frames, stride, in_row, rows, hipMemcpyHostToDevice, s), "H2D frames");
+        cv.frames = d_frames;
+        cv.stride = static_cast<int>(in_row);
+        cv.out = out == frames ? d_frames : static_cast<uint8_t*>(b_out.get(rows * out_row));
+        cv.out_stride = static_cast<int>(out_row);
+        if (skipped) d_skipped = static_cast<int*>(b_skipped.get(sizeof(int) * batch));
+    }
+    hipError_t e = mi::launch_render_canvas(cv, s);
+    if (e != hipSuccess) throw std::runtime_error(std::string("render canvas kernel launch failed: ") + hipGetErrorString(e));
+    draw(cv, d_skipped, s);
+    if (mem == MI_MEM_HOST) {
+        mi::hip_check(hipMemcpy2DAsync(out, out_stride, cv.out, out_row, out_row, rows, hipMemcpyDeviceToHost, s), "D2H picture");
+        if (skipped) mi::hip_check(hipMemcpyAsync(skipped, d_skipped, sizeof(int) * batch, hipMemcpyDeviceToHost, s), "D2H skipped");
+    }
+    if (mem == MI_MEM_HOST || !stream || always_wait) mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+}
+}  // namespace
+}  // extern "C++"
+
+int mi_render_annotations(int device, const uint8_t* frames, int batch, int width, int height, int stride, const mi_annotation* anns, int n_anns,
+                          const double* coords, long coords_per_frame, uint8_t* out, int out_channels, int out_stride, int* skipped, int mem,
+                          void* stream) {
+    return guarded([&] {
+        render_check_canvas(frames, batch, width, height, stride, out, out_channels, out_stride, mem);
+        require(n_anns >= 0 && coords_per_frame >= 0 && (n_anns == 0 || anns), "bad annotation list");
+        bool reads = false;
+        for (int a = 0; a < n_anns; a++) {
+            const mi_annotation& A = anns[a];
+            require(A.kind >= MI_ANN_POINTS && A.kind <= MI_ANN_FILLED_RECTS, "annotation kind must be one of MI_ANN_*");
+            require(A.first >= 0 && A.count >= 0, "annotation with a negative first / count");
+            const long per_item = A.kind == MI_ANN_POINTS ? 2 : 4;
+            require(A.first + A.count * per_item <= coords_per_frame, "annotation reads beyond coords_per_frame");
+            reads = reads || A.count > 0;
+        }
+        require(!reads || coords, "null argument");
+        DeviceBuf b_anns, b_coords;
+        render_run(device, frames, batch, width, height, stride, out, out_channels, out_stride, skipped, mem, stream, true,
+                   [&](const mi::RenderCanvas& cv, int* d_skipped, hipStream_t s) {
+                       const size_t ann_bytes = sizeof(mi_annotation) * n_anns, coord_bytes = sizeof(double) * coords_per_frame * batch;
+                       auto* d_anns = static_cast<mi_annotation*>(b_anns.get(ann_bytes + 16));
+                       if (n_anns) mi::hip_check(hipMemcpyAsync(d_anns, anns, ann_bytes, hipMemcpyHostToDevice, s), "H2D annotations");
+                       const double* d_coords = coords;
+                       if (mem == MI_MEM_HOST && reads) {
+                           d_coords = static_cast<const double*>(b_coords.get(coord_bytes));
+                           mi::hip_check(hipMemcpyAsync(const_cast<double*>(d_coords), coords, coord_bytes, hipMemcpyHostToDevice, s), "H2D coords");
+                       }
+                       hipError_t e = mi::launch_render_annotations(cv, d_anns, n_anns, d_coords, coords_per_frame, d_skipped, s);
+                       if (e != hipSuccess) throw std::runtime_error(std::string("render kernel launch failed: ") + hipGetErrorString(e));
+                   });
+    });
+}
+
+int mi_render_faces(int device, const uint8_t* frames, int batch, int width, int height, int stride, const mi_detection* faces, const int* face_counts,
+                    int faces_per_frame, const float* landmarks, const int* present, const float* eyes, const mi_render_style* style, uint8_t* out,
+                    int out_channels, int out_stride, int* skipped, int mem, void* stream) {
+    return guarded([&] {
+        render_check_canvas(frames, batch, width, height, stride, out, out_channels, out_stride, mem);
+        require(style, "null argument");
+        require(!faces || (face_counts && faces_per_frame > 0), "faces need face_counts and faces_per_frame > 0");
+        DeviceBuf b_faces, b_counts, b_landmarks, b_present, b_eyes;
+        render_run(device, frames, batch, width, height, stride, out, out_channels, out_stride, skipped, mem, stream, false,
+                   [&](const mi::RenderCanvas& cv, int* d_skipped, hipStream_t s) {
+                       auto staged = [&](DeviceBuf& buf, const void* p, size_t bytes) -> const void* {
+                           if (!p || mem == MI_MEM_DEVICE) return p;
+                           void* d = buf.get(bytes);
+                           mi::hip_check(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, s), "H2D results");
+                           return d;
+                       };
+                       const size_t B = static_cast<size_t>(batch);
+                       auto* d_faces = static_cast<const mi_detection*>(staged(b_faces, faces, sizeof(mi_detection) * B * (faces ? faces_per_frame : 0)));
+                       auto* d_counts = static_cast<const int*>(staged(b_counts, faces ? face_counts : nullptr, sizeof(int) * B));
+                       auto* d_landmarks = static_cast<const float*>(staged(b_landmarks, landmarks, sizeof(float) * B * MI_NUM_FACE_LANDMARKS * 3));
+                       auto* d_present = static_cast<const int*>(staged(b_present, present, sizeof(int) * B));
+                       auto* d_eyes = static_cast<const float*>(staged(b_eyes, eyes, sizeof(float) * B * 2 * (MI_NUM_EYE_LANDMARKS + MI_NUM_IRIS_LANDMARKS) * 3));
+                       hipError_t e = mi::launch_render_faces(cv, d_faces, d_counts, faces_per_frame, d_landmarks, d_present, d_eyes, *style, d_skipped, s);
+                       if (e != hipSuccess) throw std::runtime_error(std::string("render kernel launch failed: ") + hipGetErrorString(e));
+                   });
     });
 }
 
