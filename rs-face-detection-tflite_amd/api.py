@@ -553,6 +553,8 @@ class FaceDetection:
     def __init__(self, model_type=FaceDetectionModel.FrontCamera, model_path=None, device=0, model_bytes=None):
         self.L = lib()
         self.h = C.c_void_p()
+        self._slot_shape = {}   # slot -> (B, cap, frames) of the batch submit_images() queued
+        self._jpeg_cap = {}     # slot -> cap of the picture submit_jpeg() queued
         # model_path is a DIRECTORY (face_detection.rs:157-161); default "./models" resolved against the repo here
         d = model_path if model_path is not None else DEFAULT_MODEL_DIR
         if model_bytes is not None:      # the frozen .tflite already in memory (e.g. after an RCCL broadcast)
@@ -656,7 +658,6 @@ class FaceDetection:
             raise ValueError("frames must be a C-contiguous uint8 [B,H,W,3] array")
         B, H, W = frames.shape[:3]
         _check(self.L.mi_fd_submit_images(self.h, slot, C.c_void_p(frames.ctypes.data), B, W, H, frames.strides[1], cap))
-        self._slot_shape = getattr(self, "_slot_shape", {})
         self._slot_shape[slot] = (B, cap, frames)   # keeps the frames alive until collect()
 
     def collect(self, slot):
@@ -671,14 +672,14 @@ class FaceDetection:
         call, on this thread, while the device still works on the other slot's picture; everything else is queued.  `collect_jpeg(slot)`
         returns the detections."""
         _check(self.L.mi_fd_submit_jpeg(self.h, slot, im_bytes, len(im_bytes), cap))
-        self._jpeg_cap = getattr(self, "_jpeg_cap", {})
         self._jpeg_cap[slot] = cap
 
     def collect_jpeg(self, slot, with_size=False):
-        cap = self._jpeg_cap.pop(slot)
+        cap = self._jpeg_cap.get(slot, 64)   # (nothing submitted: the library refuses the call)
         buf = (CDetection * cap)()
         n, w, h = C.c_int(0), C.c_int(0), C.c_int(0)
         _check(self.L.mi_fd_collect_jpeg(self.h, slot, buf, cap, C.byref(n), C.byref(w), C.byref(h)))
+        self._jpeg_cap.pop(slot, None)
         dets = [Detection(np.frombuffer(buf[i].data, np.float32, 16).reshape(8, 2).copy(), float(buf[i].score)) for i in range(min(n.value, cap))]
         return (dets, (w.value, h.value)) if with_size else dets
 
@@ -704,6 +705,7 @@ class FaceLandmark:
     def __init__(self, model_path=None, device=0, model_bytes=None):
         self.L = lib()
         self.h = C.c_void_p()
+        self._slot_shape = {}   # slot -> (N, frames, rois) of the batch submit_images() queued
         p = model_path if model_path is not None else os.path.join(DEFAULT_MODEL_DIR, "face_landmark.tflite")
         if model_bytes is not None:
             _check(self.L.mi_fl_create_from_bytes(model_bytes, len(model_bytes), device, C.byref(self.h)))
@@ -793,7 +795,6 @@ class FaceLandmark:
                 raise ValueError("expected %d rois" % N)
         _check(self.L.mi_fl_submit_images(self.h, slot, C.c_void_p(frames.ctypes.data), B, W, H, frames.strides[1],
                                           C.cast(rarr, C.c_void_p) if rarr is not None else None, items_per_frame))
-        self._slot_shape = getattr(self, "_slot_shape", {})
         self._slot_shape[slot] = (N, frames, rarr)   # keeps frames and ROIs alive until collect()
 
     def collect(self, slot):

@@ -93,18 +93,23 @@ struct DeviceBuf {
 // operand and every result of a call in ONE pinned host block that is mapped into the device's address space: the kernels read the
 // padding / ROI / flags from it and write their results into it.  A call is then: one copy of the picture, the pre-processing launch,
 // the network's graph, the post-processing launch and ONE synchronisation, with no small copies either way.
+// The slots of the two-slot entries keep their results in such a block too; `mapped = false` gives plain pinned memory that only copies
+// read (the streamed JPEG form's coefficients): no device pointer.
 struct OneShot {
     void* host = nullptr;
     void* dev = nullptr;
     size_t cap = 0;
+    const bool mapped;
+    explicit OneShot(bool mapped_coherent = true) : mapped(mapped_coherent) {}
     void reserve(size_t bytes) {
         if (bytes <= cap) return;
         if (host) hipHostFree(host);
         host = dev = nullptr;
         cap = 0;
         // (coherent: the kernels' stores must be visible to the host once the stream has been synchronised, without a copy)
-        mi::hip_check(hipHostMalloc(&host, bytes, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
-        mi::hip_check(hipHostGetDevicePointer(&dev, host, 0), "hipHostGetDevicePointer");
+        mi::hip_check(hipHostMalloc(&host, bytes, mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault),
+                      mapped ? "hipHostMalloc" : "hipHostMalloc coefficients");
+        if (mapped) mi::hip_check(hipHostGetDevicePointer(&dev, host, 0), "hipHostGetDevicePointer");
         cap = bytes;
     }
     template <class T> T* h(size_t off) const { return reinterpret_cast<T*>(static_cast<char*>(host) + off); }
@@ -139,12 +144,68 @@ struct BandClaim {
     BandClaim(const BandClaim&) = delete;
     BandClaim& operator=(const BandClaim&) = delete;
 };
+// The claim of a streamed form (mi_fd_submit_jpeg / mi_pipeline_submit_jpeg): both slots run on one stream, so the handle holds ONE claim
+// while any of its streamed pictures is in flight.  acquire() at submit tells whether the picture may take the single-launch plan;
+// release() when a picture that acquired is collected.
+struct StreamClaim {
+    std::unique_ptr<BandClaim> claim;
+    int users = 0;
+    bool acquire(int device, int workgroups) {
+        if (users == 0) claim.reset(new BandClaim(device, workgroups));
+        users++;
+        return claim && claim->ok;
+    }
+    void release() {
+        if (--users == 0) claim.reset();
+    }
+};
 // offsets of the small operands inside the block; results start at kOneResults
 constexpr size_t kOnePad = 0, kOneRoi = 64, kOneSize = 128, kOneFlip = 136, kOneCount = 192, kOneResults = 256;
 
 void require(bool ok, const char* msg) {
     if (!ok) throw ApiError(MI_EINVAL, msg);
 }
+
+// a negative count is the post-processing kernel's report of a letterbox it cannot undo
+void check_letterbox(const int* counts, int n) {
+    for (int b = 0; b < n; b++)
+        if (counts[b] < 0) throw ApiError(MI_ERANGE, "letterbox scale is too small (reference asserts at transform.rs:121-122)");
+}
+
+// One picture per call on the single-launch plan: `network(one_shot)` enqueues the call's work and synchronises; `failed()` asks the
+// models' flags afterwards.  A launch that did not get its CUs (someone else's kernels hold them) leaves void results: the call is
+// repeated on the batched plan.  Without the claim the first run is the batched plan already.
+template <class Failed, class Network>
+void with_band_retry(bool claim_ok, Failed failed, Network network) {
+    network(claim_ok);
+    if (claim_ok && failed()) network(false);
+}
+
+// What the two-slot entries' slots share: the slot's own copy stream, `copied` (the upload has been queued in full) and `done` (so has
+// everything that writes the slot's results), and whether a submission waits to be collected.
+struct SlotSync {
+    hipStream_t copy = nullptr;
+    hipEvent_t copied = nullptr, done = nullptr;
+    bool pending = false;
+    SlotSync() = default;
+    SlotSync(const SlotSync&) = delete;
+    void open() {   // on first use
+        if (!copy) mi::hip_check(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking), "hipStreamCreate");
+        if (!copied) mi::hip_check(hipEventCreateWithFlags(&copied, hipEventDisableTiming), "hipEventCreate");
+        if (!done) mi::hip_check(hipEventCreateWithFlags(&done, hipEventDisableTiming), "hipEventCreate");
+    }
+    // submitted and never collected: its kernels still read and write the slot's and the handle's buffers.  A slot's own buffers die
+    // BEFORE this base does, and the handle's may go first too: both destructors call wait() before they free anything.
+    void wait() {
+        if (pending && done) hipEventSynchronize(done);
+    }
+    ~SlotSync() {
+        wait();
+        if (copy) hipStreamDestroy(copy);
+        if (copied) hipEventDestroy(copied);
+        if (done) hipEventDestroy(done);
+    }
+};
 
 }  // namespace
 
@@ -187,44 +248,61 @@ struct Use {
 // One of the two slots of the host-fed batch form (mi_fd_submit_images / mi_fd_collect): its own copy stream, device frames
 // and results, pinned host results.  The network itself runs on the handle's stream (one arena per handle), so the copies
 // of one slot overlap the kernels of the other.
-struct FdSlot {
-    hipStream_t copy = nullptr;
-    hipEvent_t copied = nullptr, done = nullptr;
+struct FdSlot : SlotSync {
     DeviceBuf d_frames, d_pad;
-    void* h_out = nullptr;      // pinned + mapped: [batch][cap] detections, then [batch] counts (written by the post-processing kernel)
-    size_t h_cap = 0;
+    OneShot out;                // [batch][cap] detections, then [batch] counts (written by the post-processing kernel)
     int batch = 0, cap = 0;
-    bool pending = false;
-    ~FdSlot() {
-        if (pending && done) hipEventSynchronize(done);  // a batch was submitted and never collected: its kernels still write into h_out
-        if (copy) hipStreamDestroy(copy);
-        if (copied) hipEventDestroy(copied);
-        if (done) hipEventDestroy(done);
-        if (h_out) hipHostFree(h_out);
-    }
+    ~FdSlot() { wait(); }
 };
 
 // One of the two slots of the streamed JPEG form (mi_fd_submit_jpeg / mi_fd_collect_jpeg; utils.rs:8-21 + face_detection.rs:205 for a stream of
 // encoded pictures): the entropy decoder writes the coefficients into the slot's pinned block, their copy runs on the slot's own stream, the
 // sample arithmetic / image_to_tensor / network / post-processing on the handle's stream, the results land in the slot's pinned mapped block.
-struct JpegSlot {
-    hipStream_t copy = nullptr;
-    hipEvent_t copied = nullptr, done = nullptr;
-    void* h_coef = nullptr;        // pinned: coefficients, then the quantisation tables
-    size_t h_coef_cap = 0;
-    DeviceBuf d_coef, d_qt, d_planes, d_rgb;
-    OneShot one;                   // padding in; detections + count out
-    mi::JpegFrame f;               // the picture in flight (its coefficients live in h_coef)
+// The pipeline's streamed form (mi_pipeline_submit_jpeg) uses the same slot for its decoder and adds its own result blocks (PipeJpegSlot).
+struct JpegSlot : SlotSync {
+    OneShot coef{false};           // plain pinned: coefficients, then the quantisation tables
+    DeviceBuf d_coef, d_planes, d_rgb;   // d_coef: the image of `coef`
+    OneShot one;                   // padding in; detections + count out (the detector's form)
+    mi::JpegFrame f;               // the picture in flight (its coefficients live in `coef`)
     int cap = 0;
-    bool pending = false, band = false, suspect = false, claimed = false;
-    ~JpegSlot() {
-        if (pending && done) hipEventSynchronize(done);
-        if (copy) hipStreamDestroy(copy);
-        if (copied) hipEventDestroy(copied);
-        if (done) hipEventDestroy(done);
-        if (h_coef) hipHostFree(h_coef);
-    }
+    // band: submitted on the single-launch plan; suspect: a raised flag may be this picture's (collect repeats it on the batched plan);
+    // claimed: holds a share of the handle's StreamClaim
+    bool band = false, suspect = false, claimed = false;
+    ~JpegSlot() { wait(); }
 };
+
+namespace {
+// A single-launch flag has been consumed by someone who cannot tell whose launch raised it (the flag is the handle's): every streamed
+// picture in flight on that plan may have void results.
+void mark_suspect(JpegSlot& a, JpegSlot& b) {
+    if (a.pending && a.band) a.suspect = true;
+    if (b.pending && b.band) b.suspect = true;
+}
+
+// The streamed collect entries (mi_fd_collect_jpeg / mi_pipeline_collect_jpeg), between the wait for the slot's `done` and the hand-out,
+// under the caller's Use.  A single launch that gave up leaves void results, and the flags are the handles': with the other slot's picture
+// in flight behind this one a raised flag may be that launch's.  So both are marked, and each is repeated on the batched plan when it is
+// collected (`rerun`: from the RGB picture, which is still in HBM; enqueues and synchronises).  Whatever happens, the slot is free
+// afterwards and its share of the claim is given back.
+template <class Failed, class Rerun>
+void jpeg_collect(StreamClaim& claim, JpegSlot& sl, JpegSlot& other, Failed failed, Rerun rerun) {
+    auto release = [&] {
+        if (sl.claimed) claim.release();
+        sl.claimed = false;
+        sl.pending = false;
+    };
+    try {
+        if (sl.band) {
+            if (failed()) mark_suspect(sl, other);
+            if (sl.suspect) rerun();
+        }
+    } catch (...) {
+        release();
+        throw;
+    }
+    release();
+}
+}  // namespace
 
 struct mi_fd {
     mi_model model;
@@ -236,15 +314,12 @@ struct mi_fd {
     OneShot one;
     FdSlot slot[2];
     JpegSlot jslot[2];
-    std::unique_ptr<BandClaim> jclaim;   // the CUs of the single-launch plan, held while a streamed picture is in flight (both slots run on one stream: one claim)
-    int jclaim_users = 0;
+    StreamClaim jclaim;   // the CUs of the single-launch plan, held while a streamed picture is in flight
     ~mi_fd() {
-        for (JpegSlot& sl : jslot)
-            if (sl.pending && sl.done) hipEventSynchronize(sl.done);
+        for (JpegSlot& sl : jslot) sl.wait();
         //  a batch that was submitted and never collected still reads the anchors and the table: wait for it before
         // anything is freed (hipFree happens to synchronise the device; this does not rely on it)
-        for (FdSlot& sl : slot)
-            if (sl.pending && sl.done) hipEventSynchronize(sl.done);
+        for (FdSlot& sl : slot) sl.wait();
         if (d_anchors) hipFree(d_anchors);
         if (d_lut) hipFree(d_lut);
     }
@@ -252,21 +327,11 @@ struct mi_fd {
 
 // One of the two slots of the mesh's host-fed batch form (mi_fl_submit_images / mi_fl_collect), like FdSlot: its own copy stream, device
 // frames and ROIs, and a pinned + mapped host block that the projection kernel writes the results into.
-struct FlSlot {
-    hipStream_t copy = nullptr;
-    hipEvent_t copied = nullptr, done = nullptr;
+struct FlSlot : SlotSync {
     DeviceBuf d_frames, d_rois;
-    void* h_out = nullptr;      // [N][468][3] landmarks, [N] present, [N] raw flags
-    size_t h_cap = 0;
+    OneShot out;                // [N][468][3] landmarks, [N] present, [N] raw flags
     int N = 0;
-    bool pending = false;
-    ~FlSlot() {
-        if (pending && done) hipEventSynchronize(done);
-        if (copy) hipStreamDestroy(copy);
-        if (copied) hipEventDestroy(copied);
-        if (done) hipEventDestroy(done);
-        if (h_out) hipHostFree(h_out);
-    }
+    ~FlSlot() { wait(); }
 };
 
 struct mi_fl {
@@ -277,8 +342,7 @@ struct mi_fl {
     OneShot one;
     FlSlot slot[2];
     ~mi_fl() {
-        for (FlSlot& sl : slot)
-            if (sl.pending && sl.done) hipEventSynchronize(sl.done);   // its kernels still read the handle's buffers
+        for (FlSlot& sl : slot) sl.wait();   // its kernels still read the handle's buffers
     }
 };
 
@@ -298,17 +362,14 @@ struct mi_pipeline {
     // the streamed form from encoded pictures (mi_pipeline_submit_jpeg / mi_pipeline_collect_jpeg): per slot the decoder's state and picture, the
     // results' device block and its pinned image
     struct PipeJpegSlot {
-        JpegSlot jpeg;
         DeviceBuf results;
         OneShot out;
-        bool pending = false, band = false, suspect = false, claimed = false;
+        JpegSlot jpeg;   // (last: destroyed first, and its destructor waits for the picture in flight)
     };
     PipeJpegSlot jslot[2];
-    std::unique_ptr<BandClaim> jclaim;
-    int jclaim_users = 0;
+    StreamClaim jclaim;
     ~mi_pipeline() {
-        for (PipeJpegSlot& sl : jslot)
-            if (sl.pending && sl.jpeg.done) hipEventSynchronize(sl.jpeg.done);
+        for (PipeJpegSlot& sl : jslot) sl.jpeg.wait();
     }
 };
 using PipeJpegSlot = mi_pipeline::PipeJpegSlot;
@@ -592,8 +653,7 @@ static void fd_post(mi_fd* h, const float* d_boxes, const float* d_scores, int b
     mi::hip_check(hipMemcpyAsync(out, a.out, sizeof(mi_detection) * static_cast<size_t>(cap) * batch, hipMemcpyDeviceToHost, s), "D2H detections");
     mi::hip_check(hipMemcpyAsync(counts, a.counts, sizeof(int) * batch, hipMemcpyDeviceToHost, s), "D2H counts");
     mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-    for (int b = 0; b < batch; b++)
-        if (counts[b] < 0) throw ApiError(MI_ERANGE, "letterbox scale is too small (reference asserts at transform.rs:121-122)");
+    check_letterbox(counts, batch);
 }
 
 int mi_fd_infer_tensor(mi_fd* h, const float* in, int batch, const double* padding, mi_detection* out, int cap_per_frame,
@@ -666,15 +726,15 @@ int mi_fd_infer_image(mi_fd* h, const uint8_t* rgb, int width, int height, int s
                     MI_MEM_DEVICE, s);
             mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
         };
-        network(claim.ok);
-        if (claim.ok && m.band_failed()) {  // the single launch did not get its CUs (someone else's kernels hold them): the batched plan
-            for (JpegSlot& js : h->jslot)       // (the flag is the handle's: a streamed picture in flight may have raised it)
-                if (js.pending && js.band) js.suspect = true;
-            network(false);
-        }
+        auto failed = [&] {
+            if (!m.band_failed()) return false;
+            mark_suspect(h->jslot[0], h->jslot[1]);   // (the flag is the handle's: a streamed picture in flight may have raised it)
+            return true;
+        };
+        with_band_retry(claim.ok, failed, network);
         *count = *o.h<int>(kOneCount);
         std::memcpy(out, o.h<char>(kOneResults), nout);
-        if (*count < 0) throw ApiError(MI_ERANGE, "letterbox scale is too small (reference asserts at transform.rs:121-122)");
+        check_letterbox(count, 1);
     });
 }
 
@@ -683,6 +743,48 @@ int mi_fd_infer_image(mi_fd* h, const uint8_t* rgb, int width, int height, int s
 // kernels — then, all asynchronous: coefficients to the device (slot's copy stream), dequantise + IDCT, up-sampling + colour conversion
 // (the RGB picture stays in HBM), image_to_tensor, the network (single-launch plan when its CUs are free), post-processing into the slot's
 // pinned mapped block.  collect: waits for the slot, repeats the network on the batched plan if its single launch gave up, hands the results out.
+
+// dequantise + IDCT, then up-sampling + colour conversion: coefficients -> RGB picture, all in device memory
+static void jpeg_launch(const mi::JpegFrame& f, const int16_t* d_coef, const uint16_t* d_qt, uint8_t* d_planes, uint8_t* d_rgb, hipStream_t s) {
+    int rc = mi::launch_jpeg_idct(f, d_coef, d_qt, d_planes, s);
+    if (rc == 0) rc = mi::launch_jpeg_color(f, d_planes, d_rgb, s);
+    if (rc) throw std::runtime_error(std::string("jpeg kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+}
+
+// submit, first half.  (1) the serial part, on this thread, while the device works on the other slot's picture: the coefficients go straight
+// into the slot's pinned block, the quantisation tables behind them; (2) their copy is queued on the slot's own stream, `copied` behind it.
+static void jpeg_stage(JpegSlot& sl, const uint8_t* bytes, size_t nbytes) {
+    sl.f.coef.ctx = &sl;
+    sl.f.coef.provide = [](size_t count, void* ctx) -> int16_t* {
+        JpegSlot& q = *static_cast<JpegSlot*>(ctx);
+        const size_t need = count * sizeof(int16_t) + sizeof q.f.qt;
+        if (need > q.coef.cap) q.coef.reserve(need + need / 4);
+        return q.coef.h<int16_t>(0);
+    };
+    try {
+        mi::jpeg_entropy_decode(bytes, nbytes, &sl.f);
+    } catch (const std::runtime_error& e) {
+        throw ApiError(MI_EINVAL, e.what());
+    }
+    const mi::JpegFrame& f = sl.f;
+    const size_t coef_bytes = f.coef.size() * sizeof(int16_t);
+    std::memcpy(sl.coef.h<char>(coef_bytes), f.qt, sizeof f.qt);
+    sl.open();
+    void* d_coef = sl.d_coef.get(coef_bytes + sizeof f.qt);
+    sl.d_planes.get(mi::jpeg_plane_bytes(f));
+    sl.d_rgb.get(static_cast<size_t>(3) * f.width * f.height);
+    mi::hip_check(hipMemcpyAsync(d_coef, sl.coef.host, coef_bytes + sizeof f.qt, hipMemcpyHostToDevice, sl.copy), "H2D coefficients");
+    mi::hip_check(hipEventRecord(sl.copied, sl.copy), "hipEventRecord");
+}
+
+// submit, second half, on the stream the networks run on: behind the copy, the sample arithmetic; the RGB picture (sl.d_rgb) stays in HBM
+static void jpeg_to_rgb(JpegSlot& sl, hipStream_t s) {
+    mi::hip_check(hipStreamWaitEvent(s, sl.copied, 0), "hipStreamWaitEvent");
+    char* d_coef = static_cast<char*>(sl.d_coef.p);
+    jpeg_launch(sl.f, reinterpret_cast<const int16_t*>(d_coef), reinterpret_cast<const uint16_t*>(d_coef + sl.f.coef.size() * sizeof(int16_t)),
+                static_cast<uint8_t*>(sl.d_planes.p), static_cast<uint8_t*>(sl.d_rgb.p), s);
+}
+
 static void fd_jpeg_network(mi_fd* h, JpegSlot& sl, bool one_shot, hipStream_t s) {
     mi::Model& m = *h->model.m;
     OneShot& o = sl.one;
@@ -703,55 +805,14 @@ int mi_fd_submit_jpeg(mi_fd* h, int slot, const uint8_t* bytes, size_t nbytes, i
         if (sl.pending) throw ApiError(MI_EINVAL, "slot holds a picture that has not been collected");
         mi::Model& m = *h->model.m;
         mi::hip_check(hipSetDevice(m.device()), "hipSetDevice");
-        // (1) the serial part, on this thread, while the device works on the other slot's picture: the coefficients go straight into pinned memory
-        sl.f.coef.ctx = &sl;
-        sl.f.coef.provide = [](size_t count, void* ctx) -> int16_t* {
-            JpegSlot& q = *static_cast<JpegSlot*>(ctx);
-            const size_t need = count * sizeof(int16_t) + sizeof q.f.qt;
-            if (need > q.h_coef_cap) {
-                if (q.h_coef) hipHostFree(q.h_coef);
-                q.h_coef = nullptr;
-                q.h_coef_cap = 0;
-                mi::hip_check(hipHostMalloc(&q.h_coef, need + need / 4, hipHostMallocDefault), "hipHostMalloc coefficients");
-                q.h_coef_cap = need + need / 4;
-            }
-            return static_cast<int16_t*>(q.h_coef);
-        };
-        try {
-            mi::jpeg_entropy_decode(bytes, nbytes, &sl.f);
-        } catch (const std::runtime_error& e) {
-            throw ApiError(MI_EINVAL, e.what());
-        }
-        const mi::JpegFrame& f = sl.f;
-        const size_t coef_bytes = f.coef.size() * sizeof(int16_t);
-        char* h_qt = static_cast<char*>(sl.h_coef) + coef_bytes;
-        std::memcpy(h_qt, f.qt, sizeof f.qt);
-        // (2) everything else is queued
-        if (!sl.copy) {
-            mi::hip_check(hipStreamCreateWithFlags(&sl.copy, hipStreamNonBlocking), "hipStreamCreate");
-            mi::hip_check(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming), "hipEventCreate");
-            mi::hip_check(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate");
-        }
-        auto* d_coef = static_cast<int16_t*>(sl.d_coef.get(coef_bytes + sizeof f.qt));
-        auto* d_qt = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(d_coef) + coef_bytes);
-        auto* d_planes = static_cast<uint8_t*>(sl.d_planes.get(mi::jpeg_plane_bytes(f)));
-        auto* d_rgb = static_cast<uint8_t*>(sl.d_rgb.get(static_cast<size_t>(3) * f.width * f.height));
-        const size_t nout = sizeof(mi_detection) * static_cast<size_t>(cap);
-        sl.one.reserve(kOneResults + nout);
+        jpeg_stage(sl, bytes, nbytes);
+        sl.one.reserve(kOneResults + sizeof(mi_detection) * static_cast<size_t>(cap));
         sl.cap = cap;
-        mi::hip_check(hipMemcpyAsync(d_coef, sl.h_coef, coef_bytes + sizeof f.qt, hipMemcpyHostToDevice, sl.copy), "H2D coefficients");
-        mi::hip_check(hipEventRecord(sl.copied, sl.copy), "hipEventRecord");
         hipStream_t s = m.stream();
         Use use(h->model, s);
-        mi::hip_check(hipStreamWaitEvent(s, sl.copied, 0), "hipStreamWaitEvent");
-        int rc = mi::launch_jpeg_idct(f, d_coef, d_qt, d_planes, s);
-        if (rc == 0) rc = mi::launch_jpeg_color(f, d_planes, d_rgb, s);
-        if (rc) throw std::runtime_error(std::string("jpeg kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-        // the single-launch plan's CUs: one claim for the handle while any of its streamed pictures is in flight
-        if (h->jclaim_users == 0) h->jclaim.reset(new BandClaim(m, 1));
-        h->jclaim_users++;
+        jpeg_to_rgb(sl, s);
+        sl.band = h->jclaim.acquire(m.device(), m.band_workgroups(1));
         sl.claimed = true;
-        sl.band = h->jclaim && h->jclaim->ok;
         sl.suspect = false;
         fd_jpeg_network(h, sl, sl.band, s);
         mi::hip_check(hipEventRecord(sl.done, s), "hipEventRecord");
@@ -772,30 +833,10 @@ int mi_fd_collect_jpeg(mi_fd* h, int slot, mi_detection* out, int cap, int* coun
         {
             hipStream_t s = m.stream();
             Use use(h->model, s);
-            auto release = [&] {
-                if (sl.claimed && --h->jclaim_users == 0) h->jclaim.reset();
-                sl.claimed = false;
-                sl.pending = false;
-            };
-            try {
-                if (sl.band) {
-                    // a single launch that gave up leaves void results; the flag is the handle's: with the other slot's picture in flight behind
-                    // this one it may be that launch's — both are repeated on the batched plan (from the RGB pictures, which are still in HBM)
-                    if (m.band_failed()) {
-                        sl.suspect = true;
-                        JpegSlot& other = h->jslot[1 - slot];
-                        if (other.pending && other.band) other.suspect = true;
-                    }
-                    if (sl.suspect) {
-                        fd_jpeg_network(h, sl, false, s);
-                        mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-                    }
-                }
-            } catch (...) {
-                release();
-                throw;
-            }
-            release();
+            jpeg_collect(h->jclaim, sl, h->jslot[1 - slot], [&] { return m.band_failed(); }, [&] {
+                fd_jpeg_network(h, sl, false, s);
+                mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+            });
         }
         const OneShot& o = sl.one;
         *count = *o.h<int>(kOneCount);
@@ -803,7 +844,7 @@ int mi_fd_collect_jpeg(mi_fd* h, int slot, mi_detection* out, int cap, int* coun
         if (cap > sl.cap) std::memset(out + sl.cap, 0, sizeof(mi_detection) * static_cast<size_t>(cap - sl.cap));
         if (width) *width = sl.f.width;
         if (height) *height = sl.f.height;
-        if (*count < 0) throw ApiError(MI_ERANGE, "letterbox scale is too small (reference asserts at transform.rs:121-122)");
+        check_letterbox(count, 1);
     });
 }
 
@@ -881,8 +922,7 @@ int mi_fd_infer_images(mi_fd* h, const uint8_t* frames, int batch, int width, in
         mi::hip_check(hipMemcpyAsync(out, d_out, nout, hipMemcpyDeviceToHost, s), "D2H detections");
         mi::hip_check(hipMemcpyAsync(counts, d_counts, sizeof(int) * batch, hipMemcpyDeviceToHost, s), "D2H counts");
         mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-        for (int b = 0; b < batch; b++)
-            if (counts[b] < 0) throw ApiError(MI_ERANGE, "letterbox scale is too small (reference asserts at transform.rs:121-122)");
+        check_letterbox(counts, batch);
     });
 }
 
@@ -897,17 +937,9 @@ int mi_fd_submit_images(mi_fd* h, int slot, const uint8_t* frames, int batch, in
         Use use(h->model, s);
         FdSlot& sl = h->slot[slot];
         if (sl.pending) throw ApiError(MI_EINVAL, "slot still holds an uncollected batch (call mi_fd_collect first)");
-        if (!sl.copy) mi::hip_check(hipStreamCreateWithFlags(&sl.copy, hipStreamNonBlocking), "hipStreamCreate");
-        if (!sl.copied) mi::hip_check(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming), "hipEventCreate");
-        if (!sl.done) mi::hip_check(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate");
+        sl.open();
         const size_t nout = sizeof(mi_detection) * static_cast<size_t>(cap_per_frame) * batch, ncnt = sizeof(int) * batch;
-        if (nout + ncnt > sl.h_cap) {
-            if (sl.h_out) hipHostFree(sl.h_out);
-            sl.h_out = nullptr; sl.h_cap = 0;
-            // (coherent: the kernel's stores must be visible to the host once `done` has fired, without a copy)
-            mi::hip_check(hipHostMalloc(&sl.h_out, nout + ncnt, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
-            sl.h_cap = nout + ncnt;
-        }
+        sl.out.reserve(nout + ncnt);
         // frames: host -> device on the slot's copy stream (asynchronous when `frames` is pinned memory: mi_host_alloc);
         // everything else on the handle's stream, behind the copy.  The post-processing kernel writes detections and counts
         // straight into the slot's pinned host block (mapped into the device's address space): a hipMemcpyAsync of the results
@@ -916,13 +948,10 @@ int mi_fd_submit_images(mi_fd* h, int slot, const uint8_t* frames, int batch, in
         mi::hip_check(hipMemcpyAsync(d_frames, frames, frames_bytes(batch, width, height, stride), hipMemcpyHostToDevice, sl.copy), "H2D frames");
         mi::hip_check(hipEventRecord(sl.copied, sl.copy), "hipEventRecord");
         mi::hip_check(hipStreamWaitEvent(s, sl.copied, 0), "hipStreamWaitEvent");
-        std::memset(sl.h_out, 0, nout + ncnt);  // slots beyond a frame's count read as zeros (the slot was collected: nothing in flight writes here)
-        void* mapped = nullptr;
-        mi::hip_check(hipHostGetDevicePointer(&mapped, sl.h_out, 0), "hipHostGetDevicePointer");
+        std::memset(sl.out.host, 0, nout + ncnt);  // slots beyond a frame's count read as zeros (the slot was collected: nothing in flight writes here)
         double* d_pad = static_cast<double*>(sl.d_pad.get(sizeof(double) * 4 * batch));
         try {
-            fd_images_device(h, d_frames, batch, width, height, stride, nullptr, d_pad, static_cast<mi_detection*>(mapped), cap_per_frame,
-                             reinterpret_cast<int*>(static_cast<char*>(mapped) + nout), s);
+            fd_images_device(h, d_frames, batch, width, height, stride, nullptr, d_pad, sl.out.d<mi_detection>(0), cap_per_frame, sl.out.d<int>(nout), s);
         } catch (...) {
             (void)hipStreamSynchronize(sl.copy);   //  the queued copy may still be reading the caller's frames: not after we return
             throw;
@@ -945,11 +974,10 @@ int mi_fd_collect(mi_fd* h, int slot, mi_detection* out, int* counts) {
         mi::hip_check(hipEventSynchronize(sl.done), "hipEventSynchronize");
         std::lock_guard<std::mutex> g(h->model.mu);
         const size_t nout = sizeof(mi_detection) * static_cast<size_t>(sl.cap) * sl.batch;
-        std::memcpy(out, sl.h_out, nout);
-        std::memcpy(counts, static_cast<char*>(sl.h_out) + nout, sizeof(int) * sl.batch);
+        std::memcpy(out, sl.out.host, nout);
+        std::memcpy(counts, sl.out.h<char>(nout), sizeof(int) * sl.batch);
         sl.pending = false;
-        for (int b = 0; b < sl.batch; b++)
-            if (counts[b] < 0) throw ApiError(MI_ERANGE, "letterbox scale is too small (reference asserts at transform.rs:121-122)");
+        check_letterbox(counts, sl.batch);
     });
 }
 
@@ -998,6 +1026,16 @@ int mi_fl_create(const char* model_path, int device, mi_fl** out) {
 void mi_fl_free(mi_fl* h) { delete h; }
 mi_model* mi_fl_model(mi_fl* h) { return h ? &h->model : nullptr; }
 
+// the mesh's two outputs into `a`, then project_landmarks + the face flag in one launch
+static void project_mesh(mi::Model& m, mi::ProjArgs& a, hipStream_t s) {
+    a.raw = m.output_device(0);
+    a.raw_fs = static_cast<long>(m.output_elems(0));
+    a.flag = m.output_device(1) + (m.output_elems(1) - 1);  // `flatten[flatten.len() - 1]` — face_landmark.rs:292-293
+    a.flag_fs = static_cast<long>(m.output_elems(1));
+    int rc = mi::launch_project(a, s);
+    if (rc) throw std::runtime_error(std::string("projection kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+}
+
 int mi_fl_infer_tensor(mi_fl* h, const float* in, int batch, const mi_rect* rois, const int* image_sizes, float* landmarks,
                        int* present, float* raw_flags, int mem, void* stream) {
     return guarded([&] {
@@ -1038,12 +1076,7 @@ int mi_fl_infer_tensor(mi_fl* h, const float* in, int batch, const mi_rect* rois
             a.raw_flag_out = raw_flags;
         }
         m.run_device(din, batch, s);
-        a.raw = m.output_device(0);
-        a.raw_fs = static_cast<long>(m.output_elems(0));
-        a.flag = m.output_device(1) + (m.output_elems(1) - 1);  // `flatten[flatten.len() - 1]` — face_landmark.rs:292-293
-        a.flag_fs = static_cast<long>(m.output_elems(1));
-        int rc = mi::launch_project(a, s);
-        if (rc) throw std::runtime_error(std::string("projection kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+        project_mesh(m, a, s);
         if (mem == MI_MEM_HOST) {
             mi::hip_check(hipMemcpyAsync(landmarks, a.out, lm_bytes, hipMemcpyDeviceToHost, s), "D2H landmarks");
             mi::hip_check(hipMemcpyAsync(present, a.present, sizeof(int) * batch, hipMemcpyDeviceToHost, s), "D2H present");
@@ -1116,12 +1149,7 @@ int mi_fl_infer_images(mi_fl* h, const uint8_t* frames, int batch, int width, in
             a.out = landmarks; a.present = present; a.raw_flag_out = raw_flags;
         }
         m.run_device(d_in, N, s);
-        a.raw = m.output_device(0);
-        a.raw_fs = static_cast<long>(m.output_elems(0));
-        a.flag = m.output_device(1) + (m.output_elems(1) - 1);
-        a.flag_fs = static_cast<long>(m.output_elems(1));
-        int rc = mi::launch_project(a, s);
-        if (rc) throw std::runtime_error(std::string("projection kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+        project_mesh(m, a, s);
         if (mem == MI_MEM_HOST) {
             mi::hip_check(hipMemcpyAsync(landmarks, a.out, lm_bytes, hipMemcpyDeviceToHost, s), "D2H landmarks");
             mi::hip_check(hipMemcpyAsync(present, a.present, sizeof(int) * N, hipMemcpyDeviceToHost, s), "D2H present");
@@ -1149,17 +1177,10 @@ int mi_fl_submit_images(mi_fl* h, int slot, const uint8_t* frames, int batch, in
         Use use(h->model, s);
         FlSlot& sl = h->slot[slot];
         if (sl.pending) throw ApiError(MI_EINVAL, "slot still holds an uncollected batch (call mi_fl_collect first)");
-        if (!sl.copy) mi::hip_check(hipStreamCreateWithFlags(&sl.copy, hipStreamNonBlocking), "hipStreamCreate");
-        if (!sl.copied) mi::hip_check(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming), "hipEventCreate");
-        if (!sl.done) mi::hip_check(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate");
+        sl.open();
         const int N = batch * items_per_frame;
-        const size_t lm_bytes = sizeof(float) * 3 * MI_NUM_FACE_LANDMARKS * N, total = lm_bytes + (sizeof(int) + sizeof(float)) * N;
-        if (total > sl.h_cap) {
-            if (sl.h_out) hipHostFree(sl.h_out);
-            sl.h_out = nullptr; sl.h_cap = 0;
-            mi::hip_check(hipHostMalloc(&sl.h_out, total, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
-            sl.h_cap = total;
-        }
+        const size_t lm_bytes = sizeof(float) * 3 * MI_NUM_FACE_LANDMARKS * N;
+        sl.out.reserve(lm_bytes + (sizeof(int) + sizeof(float)) * N);
         const size_t frame_bytes = static_cast<size_t>(stride) * height;
         auto* d_frames = static_cast<uint8_t*>(sl.d_frames.get(frame_bytes * batch));
         mi::hip_check(hipMemcpyAsync(d_frames, frames, frames_bytes(batch, width, height, stride), hipMemcpyHostToDevice, sl.copy), "H2D frames");
@@ -1169,8 +1190,6 @@ int mi_fl_submit_images(mi_fl* h, int slot, const uint8_t* frames, int batch, in
             mi::hip_check(hipMemcpyAsync(const_cast<mi::RectD*>(d_rois), rois, sizeof(mi_rect) * N, hipMemcpyHostToDevice, sl.copy), "H2D rois");
         }
         mi::hip_check(hipEventRecord(sl.copied, sl.copy), "hipEventRecord");
-        void* mapped = nullptr;
-        mi::hip_check(hipHostGetDevicePointer(&mapped, sl.h_out, 0), "hipHostGetDevicePointer");
         try {
             const int* d_sizes = d_rois ? batch_image_sizes(h->d_sizes_b, h->sizes_N, h->sizes_w, h->sizes_h, N, width, height, s) : nullptr;
             mi::hip_check(hipStreamWaitEvent(s, sl.copied, 0), "hipStreamWaitEvent");
@@ -1185,16 +1204,11 @@ int mi_fl_submit_images(mi_fl* h, int slot, const uint8_t* frames, int batch, in
             mi::ProjArgs a;
             a.B = N; a.n = MI_NUM_FACE_LANDMARKS; a.tensor_w = h->in_w; a.tensor_h = h->in_h;
             a.roi = d_rois; a.image_size = d_sizes;
-            a.out = static_cast<float*>(mapped);
-            a.present = reinterpret_cast<int*>(static_cast<char*>(mapped) + lm_bytes);
-            a.raw_flag_out = reinterpret_cast<float*>(static_cast<char*>(mapped) + lm_bytes + sizeof(int) * N);
+            a.out = sl.out.d<float>(0);
+            a.present = sl.out.d<int>(lm_bytes);
+            a.raw_flag_out = sl.out.d<float>(lm_bytes + sizeof(int) * N);
             m.run_device(d_in, N, s);
-            a.raw = m.output_device(0);
-            a.raw_fs = static_cast<long>(m.output_elems(0));
-            a.flag = m.output_device(1) + (m.output_elems(1) - 1);
-            a.flag_fs = static_cast<long>(m.output_elems(1));
-            int rc = mi::launch_project(a, s);
-            if (rc) throw std::runtime_error(std::string("projection kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+            project_mesh(m, a, s);
         } catch (...) {
             (void)hipStreamSynchronize(sl.copy);   // the queued copy may still be reading the caller's frames
             throw;
@@ -1217,9 +1231,9 @@ int mi_fl_collect(mi_fl* h, int slot, float* landmarks, int* present, float* raw
         mi::hip_check(hipEventSynchronize(sl.done), "hipEventSynchronize");
         std::lock_guard<std::mutex> g(h->model.mu);
         const size_t lm_bytes = sizeof(float) * 3 * MI_NUM_FACE_LANDMARKS * sl.N;
-        std::memcpy(landmarks, sl.h_out, lm_bytes);
-        std::memcpy(present, static_cast<char*>(sl.h_out) + lm_bytes, sizeof(int) * sl.N);
-        if (raw_flags) std::memcpy(raw_flags, static_cast<char*>(sl.h_out) + lm_bytes + sizeof(int) * sl.N, sizeof(float) * sl.N);
+        std::memcpy(landmarks, sl.out.host, lm_bytes);
+        std::memcpy(present, sl.out.h<char>(lm_bytes), sizeof(int) * sl.N);
+        if (raw_flags) std::memcpy(raw_flags, sl.out.h<char>(lm_bytes + sizeof(int) * sl.N), sizeof(float) * sl.N);
         sl.pending = false;
     });
 }
@@ -1256,16 +1270,10 @@ int mi_fl_infer_image(mi_fl* h, const uint8_t* rgb, int width, int height, int s
         BandClaim claim(m, 1);
         auto network = [&](bool one_shot) {
             m.run_device(d_t, 1, s, one_shot);
-            a.raw = m.output_device(0);
-            a.raw_fs = static_cast<long>(m.output_elems(0));
-            a.flag = m.output_device(1) + (m.output_elems(1) - 1);
-            a.flag_fs = static_cast<long>(m.output_elems(1));
-            int rc = mi::launch_project(a, s);
-            if (rc) throw std::runtime_error(std::string("projection kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+            project_mesh(m, a, s);
             mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
         };
-        network(claim.ok);
-        if (claim.ok && m.band_failed()) network(false);
+        with_band_retry(claim.ok, [&] { return m.band_failed(); }, network);
         const float* lm = o.h<float>(kOneResults);
         const int present = *o.h<int>(kOneCount);
         *count = 0;
@@ -1471,8 +1479,7 @@ int mi_iris_infer_image(mi_iris* h, const uint8_t* rgb, int width, int height, i
             iris_project(h, 1, d_roi, d_size, o.d<double>(kOnePad), o.d<int>(kOneFlip), o.d<float>(kContour), o.d<float>(kIris), s);
             mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
         };
-        network(claim.ok);
-        if (claim.ok && m.band_failed()) network(false);
+        with_band_retry(claim.ok, [&] { return m.band_failed(); }, network);
         const float *c = o.h<float>(kContour), *ir = o.h<float>(kIris);
         for (int i = 0; i < MI_NUM_EYE_LANDMARKS; i++) contour71[i] = mi_landmark{c[3 * i], c[3 * i + 1], c[3 * i + 2]};
         for (int i = 0; i < MI_NUM_IRIS_LANDMARKS; i++) iris5[i] = mi_landmark{ir[3 * i], ir[3 * i + 1], ir[3 * i + 2]};
@@ -1621,11 +1628,8 @@ static void pipeline_enqueue(mi_pipeline* p, const uint8_t* d_frames, int B, int
         mi::ProjArgs a;
         a.B = B; a.n = MI_NUM_FACE_LANDMARKS; a.tensor_w = p->fl->in_w; a.tensor_h = p->fl->in_h;
         a.roi = d_roi_face; a.image_size = d_sizes; a.gate = d_valid_face;
-        a.raw = flm.output_device(0); a.raw_fs = static_cast<long>(flm.output_elems(0));
-        a.flag = flm.output_device(1) + (flm.output_elems(1) - 1); a.flag_fs = static_cast<long>(flm.output_elems(1));
         a.out = o.lm; a.present = o.present;
-        int rc = mi::launch_project(a, s);
-        if (rc) throw std::runtime_error(std::string("projection kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+        project_mesh(flm, a, s);
     }
     // ---- 3. iris_roi_from_face_landmarks -> image_to_tensor(frame, eye roi, (64,64), true, (0,1), flip = right eye) -> iris net
     auto* d_roi_eye = static_cast<mi::RectD*>(p->roi_eye.get(sizeof(mi::RectD) * 2 * B));
@@ -1659,6 +1663,18 @@ static void pipeline_enqueue(mi_pipeline* p, const uint8_t* d_frames, int B, int
     tr("gather");
 }
 
+// Did a single-launch run of the pass give up?  band_failed() also CLEARS its model's flag, so all three are asked whatever the first
+// answers: `||` would leave a raised flag behind for the next call to trip over.
+static bool pipeline_band_failed(mi_pipeline* p) {
+    return (static_cast<int>(p->fd->model.m->band_failed()) | static_cast<int>(p->fl->model.m->band_failed()) |
+            static_cast<int>(p->iris->model.m->band_failed())) != 0;
+}
+
+// the CUs a single-launch pass over B pictures needs: its launches follow one another on one stream and share a claim of the largest
+static int pipeline_band_workgroups(mi_pipeline* p, int B) {
+    return std::max(std::max(p->fd->model.m->band_workgroups(B), p->fl->model.m->band_workgroups(B)), p->iris->model.m->band_workgroups(2 * B));
+}
+
 // the results of one pass, from the pinned image of its block into the caller's arrays
 static void pipeline_hand_out(const OneShot& out, const PipeLayout& L, int B, mi_detection* faces, int* face_counts, float* landmarks, int* present, float* eyes) {
     std::memcpy(faces, out.h<char>(L.faces), sizeof(mi_detection) * B);
@@ -1667,7 +1683,7 @@ static void pipeline_hand_out(const OneShot& out, const PipeLayout& L, int B, mi
     std::memcpy(present, out.h<char>(L.present), sizeof(int) * B);
     std::memcpy(eyes, out.h<char>(L.eyes), sizeof(float) * kEyeFs * 2 * B);
     for (int b = 0; b < B; b++) {
-        if (face_counts[b] < 0) throw ApiError(MI_ERANGE, "letterbox scale is too small (reference asserts at transform.rs:121-122)");
+        check_letterbox(face_counts + b, 1);
         if (face_counts[b] == 0) std::memset(&faces[b], 0, sizeof(mi_detection));
     }
 }
@@ -1679,8 +1695,6 @@ int mi_pipeline_run(mi_pipeline* p, const uint8_t* frames, int batch, int width,
         require(batch > 0 && width > 0 && height > 0 && stride >= 3 * width, "bad frame geometry");
         require(mem == MI_MEM_HOST || mem == MI_MEM_DEVICE, "mem must be MI_MEM_HOST or MI_MEM_DEVICE");
         mi::Model& fdm = *p->fd->model.m;
-        mi::Model& flm = *p->fl->model.m;
-        mi::Model& irm = *p->iris->model.m;
         mi::hip_check(hipSetDevice(fdm.device()), "hipSetDevice");
         hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fdm.stream();
         Use use_fd(p->fd->model, s), use_fl(p->fl->model, s), use_ir(p->iris->model, s);  // the pipeline's own three handles, fixed order
@@ -1695,96 +1709,54 @@ int mi_pipeline_run(mi_pipeline* p, const uint8_t* frames, int batch, int width,
         const uint8_t* d_frames = frames;
         if (mem == MI_MEM_HOST) {
             d_frames = static_cast<const uint8_t*>(p->frames.get(frame_bytes * B));
-            // the last frame's last row owns 3 * width bytes, not a whole stride
-            const size_t host_bytes = frame_bytes * (B - 1) + static_cast<size_t>(stride) * (height - 1) + static_cast<size_t>(3) * width;
-            mi::hip_check(hipMemcpyAsync(const_cast<uint8_t*>(d_frames), frames, host_bytes, hipMemcpyHostToDevice, s), "H2D frames");
+            mi::hip_check(hipMemcpyAsync(const_cast<uint8_t*>(d_frames), frames, frames_bytes(B, width, height, stride), hipMemcpyHostToDevice, s), "H2D frames");
         }
         // A picture or two from host memory (lib.rs:24-40 on one image): the detector and the face mesh may take their single-launch plans —
         // this call holds the CUs until its synchronisation below, and repeats itself on the batched plan should such a launch have given up.
         std::unique_ptr<BandClaim> claim;
-        if (mem == MI_MEM_HOST) claim = std::make_unique<BandClaim>(fdm.device(), std::max(std::max(fdm.band_workgroups(B), flm.band_workgroups(B)), irm.band_workgroups(2 * B)));
+        if (mem == MI_MEM_HOST) claim = std::make_unique<BandClaim>(fdm.device(), pipeline_band_workgroups(p, B));
         const PipeOut o = mem == MI_MEM_DEVICE ? PipeOut{faces, face_counts, landmarks, present, eyes} : L.in(d_results);
-        for (int attempt = 0; attempt < 2; attempt++) {
-            const bool one_shot = claim && claim->ok && attempt == 0;
+        auto network = [&](bool one_shot) {
             pipeline_enqueue(p, d_frames, B, width, height, stride, o, one_shot, s);
-            if (mem == MI_MEM_HOST) {
-                mi::hip_check(hipMemcpyAsync(p->out.host, d_results, L.bytes, hipMemcpyDeviceToHost, s), "D2H results");
-                mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-                if (one_shot && (static_cast<int>(fdm.band_failed()) | static_cast<int>(flm.band_failed()) | static_cast<int>(irm.band_failed()))) continue;
-                pipeline_hand_out(p->out, L, B, faces, face_counts, landmarks, present, eyes);
-            } else if (!stream) {
-                mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-            }
-            break;
-        }
+            if (mem == MI_MEM_HOST) mi::hip_check(hipMemcpyAsync(p->out.host, d_results, L.bytes, hipMemcpyDeviceToHost, s), "D2H results");
+            if (mem == MI_MEM_HOST || !stream) mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        };
+        with_band_retry(claim && claim->ok, [&] { return pipeline_band_failed(p); }, network);
+        if (mem == MI_MEM_HOST) pipeline_hand_out(p->out, L, B, faces, face_counts, landmarks, present, eyes);
     });
 }
 
 // ---- the flow of lib.rs:18-40 for a STREAM of encoded pictures: convert_image_to_mat + FaceDetection::infer + FaceLandmark::infer + 2 x
 // IrisLandmark::infer per picture, two slots (see mi_fd_submit_jpeg): the entropy decoder of picture n + 1 runs on the calling thread while the
 // device works through picture n's four networks.
+static void pipeline_jpeg_network(mi_pipeline* p, PipeJpegSlot& sl, bool one_shot, hipStream_t s) {
+    const PipeLayout L(1);
+    char* d_results = static_cast<char*>(sl.results.get(L.bytes));
+    const JpegSlot& js = sl.jpeg;
+    pipeline_enqueue(p, static_cast<const uint8_t*>(js.d_rgb.p), 1, js.f.width, js.f.height, 3 * js.f.width, L.in(d_results), one_shot, s);
+    mi::hip_check(hipMemcpyAsync(sl.out.host, d_results, L.bytes, hipMemcpyDeviceToHost, s), "D2H results");
+}
+
 int mi_pipeline_submit_jpeg(mi_pipeline* p, int slot, const uint8_t* bytes, size_t nbytes) {
     return guarded([&] {
         require(p && bytes, "null argument");
         require(slot == 0 || slot == 1, "slot must be 0 or 1");
         PipeJpegSlot& sl = p->jslot[slot];
-        if (sl.pending) throw ApiError(MI_EINVAL, "slot holds a picture that has not been collected");
-        mi::Model& fdm = *p->fd->model.m;
-        mi::Model& flm = *p->fl->model.m;
-        mi::Model& irm = *p->iris->model.m;
-        mi::hip_check(hipSetDevice(fdm.device()), "hipSetDevice");
         JpegSlot& js = sl.jpeg;
-        js.f.coef.ctx = &js;
-        js.f.coef.provide = [](size_t count, void* ctx) -> int16_t* {
-            JpegSlot& q = *static_cast<JpegSlot*>(ctx);
-            const size_t need = count * sizeof(int16_t) + sizeof q.f.qt;
-            if (need > q.h_coef_cap) {
-                if (q.h_coef) hipHostFree(q.h_coef);
-                q.h_coef = nullptr;
-                q.h_coef_cap = 0;
-                mi::hip_check(hipHostMalloc(&q.h_coef, need + need / 4, hipHostMallocDefault), "hipHostMalloc coefficients");
-                q.h_coef_cap = need + need / 4;
-            }
-            return static_cast<int16_t*>(q.h_coef);
-        };
-        try {
-            mi::jpeg_entropy_decode(bytes, nbytes, &js.f);
-        } catch (const std::runtime_error& e) {
-            throw ApiError(MI_EINVAL, e.what());
-        }
-        const mi::JpegFrame& f = js.f;
-        const size_t coef_bytes = f.coef.size() * sizeof(int16_t);
-        std::memcpy(static_cast<char*>(js.h_coef) + coef_bytes, f.qt, sizeof f.qt);
-        if (!js.copy) {
-            mi::hip_check(hipStreamCreateWithFlags(&js.copy, hipStreamNonBlocking), "hipStreamCreate");
-            mi::hip_check(hipEventCreateWithFlags(&js.copied, hipEventDisableTiming), "hipEventCreate");
-            mi::hip_check(hipEventCreateWithFlags(&js.done, hipEventDisableTiming), "hipEventCreate");
-        }
-        auto* d_coef = static_cast<int16_t*>(js.d_coef.get(coef_bytes + sizeof f.qt));
-        auto* d_qt = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(d_coef) + coef_bytes);
-        auto* d_planes = static_cast<uint8_t*>(js.d_planes.get(mi::jpeg_plane_bytes(f)));
-        auto* d_rgb = static_cast<uint8_t*>(js.d_rgb.get(static_cast<size_t>(3) * f.width * f.height));
-        const PipeLayout L(1);
-        char* d_results = static_cast<char*>(sl.results.get(L.bytes));
-        sl.out.reserve(L.bytes);
-        mi::hip_check(hipMemcpyAsync(d_coef, js.h_coef, coef_bytes + sizeof f.qt, hipMemcpyHostToDevice, js.copy), "H2D coefficients");
-        mi::hip_check(hipEventRecord(js.copied, js.copy), "hipEventRecord");
+        if (js.pending) throw ApiError(MI_EINVAL, "slot holds a picture that has not been collected");
+        mi::Model& fdm = *p->fd->model.m;
+        mi::hip_check(hipSetDevice(fdm.device()), "hipSetDevice");
+        jpeg_stage(js, bytes, nbytes);
+        sl.out.reserve(PipeLayout(1).bytes);
         hipStream_t s = fdm.stream();
         Use use_fd(p->fd->model, s), use_fl(p->fl->model, s), use_ir(p->iris->model, s);
-        mi::hip_check(hipStreamWaitEvent(s, js.copied, 0), "hipStreamWaitEvent");
-        int rc = mi::launch_jpeg_idct(f, d_coef, d_qt, d_planes, s);
-        if (rc == 0) rc = mi::launch_jpeg_color(f, d_planes, d_rgb, s);
-        if (rc) throw std::runtime_error(std::string("jpeg kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-        if (p->jclaim_users == 0)
-            p->jclaim.reset(new BandClaim(fdm.device(), std::max(std::max(fdm.band_workgroups(1), flm.band_workgroups(1)), irm.band_workgroups(2))));
-        p->jclaim_users++;
-        sl.claimed = true;
-        sl.band = p->jclaim && p->jclaim->ok;
-        sl.suspect = false;
-        pipeline_enqueue(p, d_rgb, 1, f.width, f.height, 3 * f.width, L.in(d_results), sl.band, s);
-        mi::hip_check(hipMemcpyAsync(sl.out.host, d_results, L.bytes, hipMemcpyDeviceToHost, s), "D2H results");
+        jpeg_to_rgb(js, s);
+        js.band = p->jclaim.acquire(fdm.device(), pipeline_band_workgroups(p, 1));
+        js.claimed = true;
+        js.suspect = false;
+        pipeline_jpeg_network(p, sl, js.band, s);
         mi::hip_check(hipEventRecord(js.done, s), "hipEventRecord");
-        sl.pending = true;
+        js.pending = true;
     });
 }
 
@@ -1793,44 +1765,20 @@ int mi_pipeline_collect_jpeg(mi_pipeline* p, int slot, mi_detection* face, int* 
         require(p && face && face_count && landmarks && present && eyes, "null argument");
         require(slot == 0 || slot == 1, "slot must be 0 or 1");
         PipeJpegSlot& sl = p->jslot[slot];
-        if (!sl.pending) throw ApiError(MI_EINVAL, "nothing was submitted to this slot");
-        mi::Model& fdm = *p->fd->model.m;
-        mi::Model& flm = *p->fl->model.m;
-        mi::Model& irm = *p->iris->model.m;
-        mi::hip_check(hipSetDevice(fdm.device()), "hipSetDevice");
         JpegSlot& js = sl.jpeg;
+        if (!js.pending) throw ApiError(MI_EINVAL, "nothing was submitted to this slot");
+        mi::Model& fdm = *p->fd->model.m;
+        mi::hip_check(hipSetDevice(fdm.device()), "hipSetDevice");
         mi::hip_check(hipEventSynchronize(js.done), "hipEventSynchronize");
-        const PipeLayout L(1);
         {
             hipStream_t s = fdm.stream();
             Use use_fd(p->fd->model, s), use_fl(p->fl->model, s), use_ir(p->iris->model, s);
-            auto release = [&] {
-                if (sl.claimed && --p->jclaim_users == 0) p->jclaim.reset();
-                sl.claimed = false;
-                sl.pending = false;
-            };
-            try {
-                if (sl.band) {
-                    // (the flags are the handles': with the other slot's picture in flight behind this one a raised flag may be that picture's — both are repeated)
-                    if (static_cast<int>(fdm.band_failed()) | static_cast<int>(flm.band_failed()) | static_cast<int>(irm.band_failed())) {
-                        sl.suspect = true;
-                        PipeJpegSlot& other = p->jslot[1 - slot];
-                        if (other.pending && other.band) other.suspect = true;
-                    }
-                    if (sl.suspect) {
-                        char* d_results = static_cast<char*>(sl.results.p);
-                        pipeline_enqueue(p, static_cast<const uint8_t*>(js.d_rgb.p), 1, js.f.width, js.f.height, 3 * js.f.width, L.in(d_results), false, s);
-                        mi::hip_check(hipMemcpyAsync(sl.out.host, d_results, L.bytes, hipMemcpyDeviceToHost, s), "D2H results");
-                        mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-                    }
-                }
-            } catch (...) {
-                release();
-                throw;
-            }
-            release();
+            jpeg_collect(p->jclaim, js, p->jslot[1 - slot].jpeg, [&] { return pipeline_band_failed(p); }, [&] {
+                pipeline_jpeg_network(p, sl, false, s);
+                mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+            });
         }
-        pipeline_hand_out(sl.out, L, 1, face, face_count, landmarks, present, eyes);
+        pipeline_hand_out(sl.out, PipeLayout(1), 1, face, face_count, landmarks, present, eyes);
         if (width) *width = js.f.width;
         if (height) *height = js.f.height;
     });
@@ -2116,9 +2064,7 @@ int mi_jpeg_decode_rgb(int device, const uint8_t* bytes, size_t nbytes, uint8_t*
         uint8_t* d_rgb = mem == MI_MEM_DEVICE ? rgb : static_cast<uint8_t*>(out.get(out_bytes));
         mi::hip_check(hipMemcpyAsync(d_coef, f.coef.data(), coef_bytes, hipMemcpyHostToDevice, s), "H2D coefficients");
         mi::hip_check(hipMemcpyAsync(d_qt, f.qt, sizeof f.qt, hipMemcpyHostToDevice, s), "H2D quantisation tables");
-        int rc = mi::launch_jpeg_idct(f, d_coef, d_qt, d_planes, s);
-        if (rc == 0) rc = mi::launch_jpeg_color(f, d_planes, d_rgb, s);
-        if (rc) throw std::runtime_error(std::string("jpeg kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+        jpeg_launch(f, d_coef, d_qt, d_planes, d_rgb, s);
         if (mem == MI_MEM_HOST) mi::hip_check(hipMemcpyAsync(rgb, d_rgb, out_bytes, hipMemcpyDeviceToHost, s), "D2H rgb");
         mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");  // the scratch buffers and the host coefficients die with this call
         *width = f.width;
