@@ -2,13 +2,10 @@
 #include "engine.hpp"
 #include "launch.hpp"
 
-#include <mutex>
-
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <stdexcept>
 
 namespace mi {
@@ -20,11 +17,17 @@ void hip_check(hipError_t e, const char* what) {
 namespace {
 constexpr int kHeadStreams = 4;  // most side streams for output heads that run beside the trunk (option "heads")
 
-void same_pad(int in, int k, int stride, int out, int* before) {
-    int total = std::max(0, (out - 1) * stride + k - in);
-    *before = total / 2;
-}
+void same_pad(int in, int k, int stride, int out, int* before) { *before = std::max(0, (out - 1) * stride + k - in) / 2; }
 long align_up(long v, long a) { return (v + a - 1) / a * a; }
+template <class T>  // dev becomes a device copy of host (none when host is empty); the host copy is not needed again and is freed
+void upload(T*& dev, std::vector<T>& host, const char* what_alloc, const char* what_copy) {
+    if (dev) hip_check(hipFree(dev), "hipFree");
+    dev = nullptr;
+    if (host.empty()) return;
+    hip_check(hipMalloc(reinterpret_cast<void**>(&dev), host.size() * sizeof(T)), what_alloc);
+    hip_check(hipMemcpy(dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice), what_copy);
+    std::vector<T>().swap(host);
+}
 }  // namespace
 
 Model::Model(const uint8_t* bytes, size_t n, int device) : device_(device), blob_(bytes, bytes + n) {
@@ -67,74 +70,82 @@ void Model::invalidate_graphs() {
     graphs_.clear();
 }
 
+// The options: one row per key.  A set clamps the value into [lo, hi] (a [0, 1] range is a switch: every value but 0 is stored as 1), then invalidates
+// the captured graphs and has the arena laid out again on the next run; `flags` says what else it does, or what the key does differently.
+struct Model::Option {
+    enum { kReplan = 1,      // the plan depends on it: lowered and packed again before the next run (dirty_)
+           kFreeSmall = 2,   // the small-batch scratch is sized by it
+           kKeepGraphs = 4,  // touches neither graphs nor arena
+           kOneOf = 8,       // lo is a set instead: bit v says that v is accepted, every other value is stored as 0
+           kKiB = 16 /* set and read in KiB, stored in bytes */, kWriteOnly = 32, kReadOnly = 64,
+           kBandGen = 128 }; // stored in band_gen_, and the next band launch takes the wrap path (band_gen_force_)
+    const char* key;
+    int Model::*field;
+    int lo, hi, flags;
+};
+
+const Model::Option* Model::find_option(const std::string& key) {
+    using O = Option;
+    constexpr int kMax = 0x7fffffff;
+    static const Option table[] = {
+        {"chunk", &Model::chunk_, 0, kMax, 0},  // frames per chunk of a run (0: chosen per run)
+        {"graph", &Model::use_graph_, 0, 1, 0},  // 0: eager launches instead of hipGraph replay
+        {"fuse", &Model::fuse_level_, 0, 5, O::kReplan},  // fusion level of the lowering (plan.hpp)
+        {"res_budget", &Model::res_budget_, 16, 156, O::kReplan | O::kKiB},  // LDS (KiB) a stage program may use
+        {"pipe", &Model::pipe_max_, 0, 4, O::kReplan},  // blocks per row-pipelined chain (level 4)
+        {"small_chain", &Model::small_chain_, 0, 64, O::kFreeSmall},  // frames up to which a row-pipelined chain runs one launch per block (0: never)
+        // row pipeline: 1 = one row per step (strip_pipe_kernel), 2 = two rows, packed-FMA pointwise convs (strip_pipe2_kernel), 4 = one row, MFMA pointwise convs (strip_pipe1m_kernel)
+        {"pipe_rows", &Model::pipe_rows_, 1 << 1 | 1 << 2 | 1 << 4, 0, O::kOneOf},
+        {"pipe_band", &Model::pipe_band_, 0, 4096, 0},  // rows per band of the row pipelines (0: automatic)
+        {"strip", &Model::strip_, 0, 1, 0},  // 0: none of the strip / operand-layout kernels runs (blocks stay on the block kernel and its fused forms)
+        {"stem_fuse", &Model::stem_fuse_, 0, 1, 0},  // 0: the first convolution keeps its own launch in front of the face mesh's block pair (mdblock_kernel<stem+pair>)
+        {"stem_mfma", &Model::stem_mfma_, 0, 1, 0},  // 0: the detectors' 5x5 first convolution stays on stem_conv_kernel (packed VALU FMAs) at every batch size (bit-identical)
+        {"pair_fuse", &Model::pair_fuse_, 0, 1, 0},  // 0: two plain blocks in a row keep a launch each (the face mesh's 48x48x32 blocks: mwalk_kernel), no mdblock_kernel<pair>
+        {"mdb_band", &Model::mdb_band_, 0, 4096, 0},  // rows per band of the mdblock_kernel launches (0: chosen per launch)
+        {"mchain", &Model::mchain_, 0, 1, 0},  // 0: the 32x32x48 blocks run one launch each (mstrip_kernel) instead of one launch per run
+        {"tail", &Model::tail_, 0, 1, O::kReplan},  // 0: no stage program runs on tail_kernels.hip
+        {"tail_pre", &Model::tail_pre_, 0, 2, 0},  // tail programs: 0 = chosen per launch, 1 = constants a stage ahead (one workgroup per CU), 2 = 128 registers (two per CU)
+        {"tail_g", &Model::tail_g_, 0, 64, 0},  // frames per workgroup of the tail stage programs (0: chosen per launch)
+        {"band", &Model::band_, 0, 2, O::kReplan},  // single-launch plan: 0 never, 1 one_shot runs (the single-image entries), 2 every run of few enough frames
+        {"band_test_fail", &Model::band_test_fail_, 0, 1, O::kWriteOnly},  // test hook: the next single-launch run reports that it gave up
+        {"band_test_absent", &Model::band_test_absent_, 0, 256, O::kWriteOnly},  // test hook: every k-th workgroup of a single-launch run leaves at once without publishing (0: off)
+        {"band_test_gen", nullptr, 0, kMax, O::kBandGen | O::kWriteOnly},  // test hook: the host's count of band launches (the packet tags wrap at 2^26: see run_device)
+        {"band_wide", &Model::band_wide_ok_, 0, 1, O::kReplan},  // single-launch plan: stages of more than 128 channels (0: the program ends in front of the first one)
+        {"band_fork", &Model::band_fork_, 0, 1, O::kReplan},  // single-launch plan: the second branch behind a fork on the idle workgroups
+        {"band_nw", &Model::band_nw_, 8, 256, O::kReplan},  // single-launch plan: most workgroups per frame
+        {"band_fail_streak", &Model::band_fail_streak_, 0, 0, O::kReadOnly},  // single launches in a row that gave up
+        {"band_wraps", &Model::band_wraps_, 0, 0, O::kReadOnly},  // times the band workspace was cleared because the packet tags wrapped
+        {"fork", &Model::fork_, 0, 1, 0},  // 0: output heads and tail branches stay on the trunk's stream
+        {"heads", &Model::head_streams_opt_, 1, kHeadStreams, O::kReplan},  // side streams the output heads are spread over
+        {"reuse", &Model::reuse_, 0, 1, O::kReplan},  // 0: debugging layout, every tensor keeps its own arena slot
+        {"lanes", &Model::lanes_, 1, 4, 0},  // chunks of a run in flight on streams of their own
+        {"test_poison", &Model::test_poison_, 1 << 1 | 1 << 2, 0, O::kOneOf | O::kKeepGraphs},  // test hook: fill the scratch and output buffers before every run (poison_scratch)
+    };
+    for (const Option& o : table)
+        if (key == o.key) return &o;
+    return nullptr;
+}
+
 void Model::set_option(const std::string& key, int value) {
-    if (key == "test_poison") {   // test hook: fill the scratch and output buffers before every run (poison_scratch); no re-layout, no new graphs
-        test_poison_ = (value == 1 || value == 2) ? value : 0;
-        return;
-    }
-    if (key == "chunk") chunk_ = std::max(0, value);
-    else if (key == "graph") use_graph_ = value != 0;
-    else if (key == "fuse") { fuse_level_ = std::min(5, std::max(0, value)); dirty_ = true; }
-    else if (key == "res_budget") { res_budget_ = std::min(156, std::max(16, value)) * 1024; dirty_ = true; }  // LDS (KiB) a stage program may use
-    else if (key == "pipe") { pipe_max_ = std::min(4, std::max(0, value)); dirty_ = true; }   // blocks per row-pipelined chain (level 4)
-    else if (key == "small_chain") { small_chain_ = std::max(0, std::min(value, 64)); if (d_small_) { hipFree(d_small_); d_small_ = nullptr; small_floats_ = 0; } invalidate_graphs(); }  // frames up to which a row-pipelined chain runs one launch per block (0: never)
-    else if (key == "pipe_rows") { pipe_rows_ = (value == 1 || value == 2 || value == 4) ? value : 0; }     // 1: one row per pipeline step (strip_pipe_kernel), 2: two rows, packed-FMA pointwise convs (strip_pipe2_kernel), 4: one row, MFMA pointwise convs (strip_pipe1m_kernel)
-    else if (key == "pipe_band") { pipe_band_ = std::max(0, std::min(value, 4096)); }   // rows per band of the row pipelines (0: automatic)
-    else if (key == "strip") { strip_ = value != 0; }
-    else if (key == "stem_fuse") { stem_fuse_ = value != 0; }   // 0: the first convolution keeps its own launch in front of the face mesh's block pair (mdblock_kernel<stem+pair>, round 6)
-    else if (key == "stem_mfma") { stem_mfma_ = value != 0; }   // 0: the detectors' 5x5 first convolution stays on stem_conv_kernel (packed VALU FMAs) at every batch size; the results are bit-identical
-    else if (key == "pair_fuse") { pair_fuse_ = value != 0; }   // 0: two plain blocks in a row keep a launch each (the face mesh's 48x48x32 blocks: mwalk_kernel) instead of one mdblock_kernel<pair>
-    else if (key == "mdb_band") { mdb_band_ = std::max(0, std::min(value, 4096)); }   // rows per band of the mdblock_kernel launches (0: chosen per launch)
-    else if (key == "mchain") { mchain_ = value != 0; }   // 0: the 32x32x48 blocks run one launch each (mstrip_kernel) instead of one launch per run
-    else if (key == "tail") { tail_ = value != 0; dirty_ = true; }   // 0: no stage program runs on tail_kernels.hip (the round-4 plan)
-    else if (key == "tail_pre") { tail_pre_ = std::max(0, std::min(value, 2)); }   // tail programs: 0 = chosen per launch, 1 = constants a stage ahead (one workgroup per CU), 2 = 128 registers (two per CU)
-    else if (key == "tail_g") { tail_g_ = std::max(0, std::min(value, 64)); }   // frames per workgroup of the tail stage programs (0: chosen per launch)
-    else if (key == "band") { band_ = std::max(0, std::min(value, 2)); dirty_ = true; }   // single-launch plan: 0 never, 1 one_shot runs (the single-image entries), 2 every run of few enough frames
-    else if (key == "band_test_fail") { band_test_fail_ = value != 0; }   // test hook: the next single-launch run reports that it gave up
-    else if (key == "band_test_absent") { band_test_absent_ = std::max(0, std::min(value, 256)); }   // test hook: every k-th workgroup of a single-launch run leaves at once without publishing (a workgroup that is not resident; 0: off)
-    else if (key == "band_test_gen") { band_gen_ = static_cast<unsigned>(std::max(0, value)); band_gen_force_ = true; }   // test hook: the host's count of band launches (the packet tags wrap at 2^26: see run_device)
-    else if (key == "band_wide") { band_wide_ok_ = value != 0; dirty_ = true; }   // single-launch plan: stages of more than 128 channels (0: the program ends in front of the first one)
-    else if (key == "band_fork") { band_fork_ = value != 0; dirty_ = true; }   // single-launch plan: the second branch behind a fork on the idle workgroups
-    else if (key == "band_nw") { band_nw_ = std::max(8, std::min(value, 256)); dirty_ = true; }   // its workgroups per frame
-    else if (key == "fork") { fork_ = value != 0; }
-    else if (key == "heads") { head_streams_opt_ = std::min(kHeadStreams, std::max(1, value)); dirty_ = true; }  // side streams the output heads are spread over                                             // 0: output heads stay on the trunk's stream                                          // 0: LDS-ring block kernel for every block
-    else if (key == "reuse") { reuse_ = value != 0; dirty_ = true; }
-    else if (key == "lanes") lanes_ = std::min(4, std::max(1, value));
-    else throw std::runtime_error("unknown option '" + key + "'");
+    const Option* o = find_option(key);
+    if (!o || (o->flags & Option::kReadOnly)) throw std::runtime_error("unknown option '" + key + "'");
+    int v = (o->lo == 0 && o->hi == 1) ? value != 0 : std::min(o->hi, std::max(o->lo, value));
+    if (o->flags & Option::kOneOf) v = (value >= 0 && value < 31 && (o->lo >> value & 1)) ? value : 0;
+    if (o->flags & Option::kKiB) v *= 1024;
+    if (o->flags & Option::kBandGen) { band_gen_ = static_cast<unsigned>(v); band_gen_force_ = true; }
+    else this->*o->field = v;
+    if (o->flags & Option::kKeepGraphs) return;
+    if (o->flags & Option::kReplan) dirty_ = true;
+    if ((o->flags & Option::kFreeSmall) && d_small_) { hipFree(d_small_); d_small_ = nullptr; small_floats_ = 0; }
     invalidate_graphs();
     chunk_cap_ = 0;  // arena is re-laid out on the next run
 }
 
 int Model::get_option(const std::string& key) const {
-    if (key == "chunk") return chunk_;
-    if (key == "graph") return use_graph_;
-    if (key == "fuse") return fuse_level_;
-    if (key == "res_budget") return res_budget_ / 1024;
-    if (key == "pipe") return pipe_max_;
-    if (key == "small_chain") return small_chain_;
-    if (key == "pipe_rows") return pipe_rows_;
-    if (key == "pipe_band") return pipe_band_;
-    if (key == "strip") return strip_;
-    if (key == "stem_fuse") return stem_fuse_;
-    if (key == "stem_mfma") return stem_mfma_;
-    if (key == "pair_fuse") return pair_fuse_;
-    if (key == "mdb_band") return mdb_band_;
-    if (key == "mchain") return mchain_;
-    if (key == "tail") return tail_;
-    if (key == "tail_pre") return tail_pre_;
-    if (key == "tail_g") return tail_g_;
-    if (key == "band") return band_;
-    if (key == "band_fork") return band_fork_;
-    if (key == "band_wide") return band_wide_ok_;
-    if (key == "band_nw") return band_nw_;
-    if (key == "band_fail_streak") return band_fail_streak_;
-    if (key == "band_wraps") return band_wraps_;
-    if (key == "fork") return fork_;
-    if (key == "heads") return head_streams_opt_;
-    if (key == "reuse") return reuse_;
-    if (key == "lanes") return lanes_;
-    if (key == "test_poison") return test_poison_;
-    throw std::runtime_error("unknown option '" + key + "'");
+    const Option* o = find_option(key);
+    if (!o || (o->flags & Option::kWriteOnly)) throw std::runtime_error("unknown option '" + key + "'");
+    const int v = this->*o->field;
+    return (o->flags & Option::kKiB) ? v / 1024 : v;
 }
 
 void Model::rebuild() {
@@ -142,559 +153,85 @@ void Model::rebuild() {
     hip_check(hipSetDevice(device_), "hipSetDevice");
     invalidate_graphs();
     plan_ = build_plan(parse_tflite(blob_.data(), blob_.size()), fuse_level_, pipe_max_, res_budget_, tail_ != 0);
-    const Graph& g = plan_.graph;
     if (!reuse_) {  // debugging layout: every tensor keeps its own slot
         long off = 0;
-        for (size_t t = 0; t < g.tensors.size(); t++)
+        for (size_t t = 0; t < plan_.graph.tensors.size(); t++)
             if (plan_.root_offset[t] >= 0) { plan_.root_offset[t] = off; off += plan_.root_elems[t]; }
         plan_.arena_floats_per_frame = off;
     }
-    // ---- pack every constant the launches need into one device blob
-    std::vector<float> host;
-    auto put = [&](const std::vector<float>& v) {
-        long off = align_up(static_cast<long>(host.size()), 64);
-        host.resize(static_cast<size_t>(off) + v.size(), 0.f);
-        std::copy(v.begin(), v.end(), host.begin() + off);
-        return off;
-    };
-    const size_t NN = plan_.nodes.size();
-    node_w_.assign(NN, -1); node_b_.assign(NN, -1); node_w2_.assign(NN, -1); node_b2_.assign(NN, -1); node_alpha_.assign(NN, -1);
-    chain_off_.assign(NN, {});
-    chain_head_off_.assign(NN, {});
-    node_strip_.assign(NN, -1);
-    node_mwalk_.assign(NN, -1);
-    node_stem_.assign(NN, -1);
-    node_pair_.assign(NN, -1);
-    res_cblob_.assign(NN, {});
-    res_wblk_.assign(NN, {});
-    tail_wa_.assign(NN, {});
-    tail_wc_.assign(NN, {});
-    // pointwise weights [O][1][1][I] -> MFMA A-fragment order [tile][k-chunk][lane][4]:
-    // lane l = (row m = l & 31, k-half h = l >> 5) holds W[tile*32 + m][h*Cp/2 + 4*chunk + e], zero padded
-    auto pack_pw = [&](int wt, int kblk = 0) {
-        const auto& ws = g.tensors[wt].shape;
-        const auto& src = g.tensors[wt].f32;
-        // [O][KH][KW][I] read as [O][KH*KW*I]: the k x k stride-k convolutions of the stage programs contract over the
-        // "virtual channels" (tap, channel) in exactly this order
-        int O = ws[0], I = ws[1] * ws[2] * ws[3], Cp, Cop;
-        block_weight_dims(I, O, &Cp, &Cop);
-        const int Ch = Cp / 2, MT = Cop / 32;
-        std::vector<float> r(static_cast<size_t>(Cop) * Cp, 0.f);
-        for (int mt = 0; mt < MT; mt++)
-            for (int j = 0; j < Ch / 4; j++)
-                for (int l = 0; l < 64; l++)
-                    for (int e2 = 0; e2 < 4; e2++) {
-                        int o = mt * 32 + (l & 31), c = (l >> 5) * Ch + 4 * j + e2;
-                        if (kblk == 16) c = 16 * (j / 2) + 8 * (l >> 5) + 4 * (j % 2) + e2;  // K-blocked order of the LDS-staged pointwise stages
-                        if (o < O && c < I) r[((static_cast<size_t>(mt) * (Ch / 4) + j) * 64 + l) * 4 + e2] = src[static_cast<size_t>(o) * I + c];
-                    }
-        return put(r);
-    };
-    for (size_t i = 0; i < NN; i++) {
-        const Node& n = plan_.nodes[i];
-        if (n.kind == Node::Chain) {
-            for (const Node& m : n.members) {
-                MemberOff mo;
-                mo.w = put(g.tensors[m.w].f32);
-                if (m.b >= 0) mo.b = put(g.tensors[m.b].f32);
-                mo.w2 = pack_pw(m.w2);
-                if (m.b2 >= 0) mo.b2 = put(g.tensors[m.b2].f32);
-                if (m.alpha >= 0) mo.alpha = put(g.tensors[m.alpha].f32);
-                const auto& ws = g.tensors[m.w2].shape;  // [O][1][1][I]
-                if (n.chain_pre || n.chain_post) {
-                    // frame-resident chain with stride-2 edge stages: block-kernel packing only
-                } else if (m.sh == 2) {  // stride-2 tail of a row pipeline
-                    std::vector<float> sc(static_cast<size_t>(strip_consts_s2_floats(ws[3], ws[0])));
-                    strip_pack_consts_s2(ws[3], ws[0], g.tensors[m.w].f32.data(), m.b >= 0 ? g.tensors[m.b].f32.data() : nullptr, g.tensors[m.w2].f32.data(),
-                                         m.b2 >= 0 ? g.tensors[m.b2].f32.data() : nullptr, m.alpha >= 0 ? g.tensors[m.alpha].f32.data() : nullptr, m.act, sc.data());
-                    mo.strip = put(sc);
-                } else if (strip_shape_ok(ws[3], ws[0])) {
-                    std::vector<float> sc(static_cast<size_t>(strip_consts_floats(ws[3])));
-                    strip_pack_consts(ws[3], g.tensors[m.w].f32.data(), m.b >= 0 ? g.tensors[m.b].f32.data() : nullptr, g.tensors[m.w2].f32.data(),
-                                      m.b2 >= 0 ? g.tensors[m.b2].f32.data() : nullptr, m.alpha >= 0 ? g.tensors[m.alpha].f32.data() : nullptr, m.act, sc.data());
-                    mo.strip = put(sc);
-                }
-                chain_off_[i].push_back(mo);
-            }
-            // a row-pipelined pair of plain BlazeBlocks on a wide layer also gets the constants of the operand-layout kernel
-            // (mdblock_kernels.hip, pair form; which of the two runs is decided per launch)
-            if (n.members.size() == 2 && !n.chain_pre && !n.chain_post && n.head_pairs.empty()) {
-                const Node &pa = n.members[0], &pb = n.members[1];
-                const auto& sx = g.tensors[pa.in[0]].shape;
-                auto plain = [&](const Node& m) { return m.w >= 0 && m.sh == 1 && m.sw == 1 && m.res == m.in[0] && m.res_mode == RES_DIRECT && !m.res_after && m.padding == Padding::Same; };
-                const int C = sx[3], Cm = g.tensors[pa.out].shape[3], Co = g.tensors[pb.out].shape[3];
-                if (sx.size() == 4 && plain(pa) && plain(pb) && pb.in[0] == pa.out && mdblock_shape_ok(sx[2], C, Cm, Co, true)) {
-                    std::vector<float> mc(static_cast<size_t>(mdblock_consts_floats(sx[2], C, Cm, Co, true)));
-                    auto ptr = [&](int t) { return t >= 0 ? g.tensors[t].f32.data() : nullptr; };
-                    mdblock_pack_consts(sx[2], C, Cm, Co, ptr(pa.w), ptr(pa.b), ptr(pa.w2), ptr(pa.b2), pa.act == ACT_PRELU ? ptr(pa.alpha) : nullptr, pa.act,
-                                        ptr(pb.w), ptr(pb.b), ptr(pb.w2), ptr(pb.b2), pb.act == ACT_PRELU ? ptr(pb.alpha) : nullptr, pb.act, mc.data(), true);
-                    node_mwalk_[i] = put(mc);   // (the slot of the Block nodes' mwalk constants: a Chain node has none of its own)
-                }
-            }
-            // output heads of the launch: the weights of a pair stacked [Co_a + Co_b][C] in A-fragment order, the biases stacked
-            for (const Node::HeadPair& hp : n.head_pairs) {
-                const Node* hn[2] = {&n.head_nodes[static_cast<size_t>(hp.a)], hp.b >= 0 ? &n.head_nodes[static_cast<size_t>(hp.b)] : nullptr};
-                auto wt = [&](const Node& m) { return m.kind == Node::Conv ? m.w : m.w2; };
-                auto bt = [&](const Node& m) { return m.kind == Node::Conv ? m.b : m.b2; };
-                const int I = g.tensors[wt(*hn[0])].shape[3];
-                std::vector<float> rows, bias;
-                for (const Node* m : hn) {
-                    if (!m) continue;
-                    const auto& w = g.tensors[wt(*m)];
-                    if (w.shape[3] != I || w.shape[1] != 1 || w.shape[2] != 1) throw std::runtime_error("engine: output heads of a pair differ in their input width");
-                    rows.insert(rows.end(), w.f32.begin(), w.f32.end());
-                    if (bt(*m) >= 0) bias.insert(bias.end(), g.tensors[bt(*m)].f32.begin(), g.tensors[bt(*m)].f32.end());
-                    else bias.insert(bias.end(), static_cast<size_t>(w.shape[0]), 0.f);
-                }
-                const int O = static_cast<int>(rows.size()) / I, MT = (O + 31) / 32, Ch = I / 2;
-                std::vector<float> r(static_cast<size_t>(MT) * 32 * I, 0.f);
-                for (int mt = 0; mt < MT; mt++)
-                    for (int j = 0; j < Ch / 4; j++)
-                        for (int l = 0; l < 64; l++)
-                            for (int e2 = 0; e2 < 4; e2++) {
-                                const int o = mt * 32 + (l & 31), c = (l >> 5) * Ch + 4 * j + e2;
-                                if (o < O) r[((static_cast<size_t>(mt) * (Ch / 4) + j) * 64 + l) * 4 + e2] = rows[static_cast<size_t>(o) * I + c];
-                            }
-                bias.resize(static_cast<size_t>(MT) * 32, 0.f);
-                MemberOff mo;
-                mo.w2 = put(r);
-                mo.b2 = put(bias);
-                chain_head_off_[i].push_back(mo);
-            }
-            continue;
-        }
-        if (n.kind == Node::Resident && n.xc) {
-            // expand / contract runs (xc_kernels.hip): per member the depthwise taps and biases as stored, the pointwise matrix in the block kernel's packing
-            for (const Node& m : n.members) {
-                MemberOff mo;
-                mo.w2 = pack_pw(m.w2);
-                // the stage's small constants as the kernel copies them to LDS: taps [9][Cp], depthwise bias [Cp], pointwise bias [Cop]
-                const int C = g.tensors[m.in[0]].shape[3], Co = g.tensors[m.out].shape[3], Cp = (C + 7) & ~7;
-                std::vector<float> cb(static_cast<size_t>(xc_const_floats(C, Co)), 0.f);
-                if (m.w >= 0)
-                    for (int t = 0; t < 9; t++)
-                        for (int c = 0; c < C; c++) cb[static_cast<size_t>(t) * Cp + c] = g.tensors[m.w].f32[static_cast<size_t>(t) * C + c];
-                if (m.b >= 0)
-                    for (int c = 0; c < C; c++) cb[static_cast<size_t>(9) * Cp + c] = g.tensors[m.b].f32[static_cast<size_t>(c)];
-                if (m.b2 >= 0)
-                    for (int c = 0; c < Co; c++) cb[static_cast<size_t>(10) * Cp + c] = g.tensors[m.b2].f32[static_cast<size_t>(c)];
-                mo.strip = put(cb);
-                chain_off_[i].push_back(mo);
-            }
-            res_wblk_[i].clear();
-            res_cblob_[i].clear();
-            continue;
-        }
-        if (n.kind == Node::Resident && n.dblock) {
-            // double block (dblock_kernels.hip): both pointwise matrices in the block kernel's packing, one blob of small constants
-            const Node &pa = n.members[0], &pb = n.members[1];
-            const int C = g.tensors[pa.in[0]].shape[3], Cm = g.tensors[pa.out].shape[3], Co = g.tensors[pb.out].shape[3], Cmp = (Cm + 7) & ~7, MT = (Co + 31) / 32, MTA = (Cm + 31) / 32;
-            MemberOff ma, mb;
-            ma.w2 = pack_pw(pa.w2);
-            mb.w2 = pack_pw(pb.w2);
-            std::vector<float> cb(static_cast<size_t>(dblock_const_floats(C, Cm, Co)), 0.f);
-            auto slope = [&](const Node& m, int c) { return m.act == ACT_PRELU ? g.tensors[m.alpha].f32[static_cast<size_t>(c)] : (m.act == ACT_NONE ? 1.f : 0.f); };
-            size_t o = 0;
-            for (int tap = 0; tap < 9; tap++)
-                for (int c = 0; c < C; c++) cb[o + static_cast<size_t>(tap) * C + c] = g.tensors[pa.w].f32[static_cast<size_t>(tap) * C + c];
-            o += static_cast<size_t>(9) * C;
-            for (int c = 0; c < C; c++) cb[o + c] = pa.b >= 0 ? g.tensors[pa.b].f32[static_cast<size_t>(c)] : 0.f;
-            o += static_cast<size_t>(C);
-            for (int c = 0; c < Cm; c++) { cb[o + c] = pa.b2 >= 0 ? g.tensors[pa.b2].f32[static_cast<size_t>(c)] : 0.f; cb[o + static_cast<size_t>(32) * MTA + c] = slope(pa, c); }
-            o += static_cast<size_t>(64) * MTA;
-            for (int tap = 0; tap < 9; tap++)
-                for (int c = 0; c < Cm; c++) cb[o + static_cast<size_t>(tap) * Cmp + c] = g.tensors[pb.w].f32[static_cast<size_t>(tap) * Cm + c];
-            o += static_cast<size_t>(9) * Cmp;
-            for (int c = 0; c < Cm; c++) cb[o + c] = pb.b >= 0 ? g.tensors[pb.b].f32[static_cast<size_t>(c)] : 0.f;
-            o += static_cast<size_t>(Cmp);
-            for (int c = 0; c < Co; c++) { cb[o + c] = pb.b2 >= 0 ? g.tensors[pb.b2].f32[static_cast<size_t>(c)] : 0.f; cb[o + static_cast<size_t>(32) * MT + c] = slope(pb, c); }
-            ma.strip = put(cb);
-            // the wide layers also get the constants of the operand-layout kernel (mdblock_kernels.hip); which of the two runs is decided per launch
-            const int Wd = g.tensors[pa.in[0]].shape[2];
-            if (mdblock_shape_ok(Wd, C, Cm, Co) && pa.res < 0 && pb.res == pa.in[0]) {
-                std::vector<float> mc(static_cast<size_t>(mdblock_consts_floats(Wd, C, Cm, Co)));
-                auto ptr = [&](int t) { return t >= 0 ? g.tensors[t].f32.data() : nullptr; };
-                mdblock_pack_consts(Wd, C, Cm, Co, ptr(pa.w), ptr(pa.b), ptr(pa.w2), ptr(pa.b2), pa.act == ACT_PRELU ? ptr(pa.alpha) : nullptr, pa.act,
-                                    ptr(pb.w), ptr(pb.b), ptr(pb.w2), ptr(pb.b2), pb.act == ACT_PRELU ? ptr(pb.alpha) : nullptr, pb.act, mc.data());
-                mb.strip = put(mc);
-            }
-            chain_off_[i].push_back(ma);
-            chain_off_[i].push_back(mb);
-            res_wblk_[i].clear();
-            res_cblob_[i].clear();
-            continue;
-        }
-        if (n.kind == Node::Resident && n.bneck) {
-            // bottleneck pairs (bneck_kernels.hip): per pair the first pointwise matrix with its contraction index in the MFMA result
-            // order, the second in the block kernel's order, and one blob of small constants
-            for (size_t k = 0; k + 1 < n.members.size(); k += 2) {
-                const Node &pa = n.members[k], &pb = n.members[k + 1];
-                const auto& w1s = g.tensors[pa.w2].shape;  // [Cm][1][1][C]
-                const int Cm = w1s[0], C = w1s[3];
-                const auto& w1 = g.tensors[pa.w2].f32;
-                std::vector<float> r(static_cast<size_t>(Cm) * C, 0.f);
-                const int NCH1 = C / 8;
-                for (int t = 0; t < Cm / 32; t++)
-                    for (int j = 0; j < NCH1; j++)
-                        for (int l = 0; l < 64; l++)
-                            for (int e = 0; e < 4; e++)
-                                r[((static_cast<size_t>(t) * NCH1 + j) * 64 + l) * 4 + e] = w1[static_cast<size_t>(32 * t + (l & 31)) * C + 32 * (j / 4) + 8 * (j % 4) + 4 * (l >> 5) + e];
-                MemberOff ma, mb;
-                ma.w2 = put(r);
-                mb.w2 = pack_pw(pb.w2);
-                std::vector<float> cb(static_cast<size_t>(bneck_const_floats(C, Cm)), 0.f);
-                auto slope = [&](const Node& m, int c) { return m.act == ACT_PRELU ? g.tensors[m.alpha].f32[static_cast<size_t>(c)] : (m.act == ACT_NONE ? 1.f : 0.f); };
-                for (int c = 0; c < Cm; c++) {
-                    cb[static_cast<size_t>(c)] = pa.b2 >= 0 ? g.tensors[pa.b2].f32[static_cast<size_t>(c)] : 0.f;
-                    cb[static_cast<size_t>(Cm + c)] = slope(pa, c);
-                    for (int tap = 0; tap < 9; tap++) cb[static_cast<size_t>(2 * Cm + tap * Cm + c)] = g.tensors[pb.w].f32[static_cast<size_t>(tap) * Cm + c];
-                    cb[static_cast<size_t>(11 * Cm + c)] = pb.b >= 0 ? g.tensors[pb.b].f32[static_cast<size_t>(c)] : 0.f;
-                }
-                for (int c = 0; c < C; c++) {
-                    cb[static_cast<size_t>(12 * Cm + c)] = pb.b2 >= 0 ? g.tensors[pb.b2].f32[static_cast<size_t>(c)] : 0.f;
-                    cb[static_cast<size_t>(12 * Cm + C + c)] = slope(pb, c);
-                }
-                ma.strip = put(cb);
-                // 32-pixel-wide pairs also get the constants of the operand-layout kernel (mdblock_kernels.hip, mbneck_kernel)
-                const int Wd = g.tensors[pa.in[0]].shape[2];
-                if (mbneck_shape_ok(Wd, C, Cm)) {
-                    std::vector<float> mc(static_cast<size_t>(mbneck_consts_floats(Wd, C, Cm)));
-                    auto ptr = [&](int t) { return t >= 0 ? g.tensors[t].f32.data() : nullptr; };
-                    mbneck_pack_consts(Wd, C, Cm, ptr(pa.w2), ptr(pa.b2), pa.act == ACT_PRELU ? ptr(pa.alpha) : nullptr, pa.act, ptr(pb.w), ptr(pb.b), ptr(pb.w2), ptr(pb.b2),
-                                       pb.act == ACT_PRELU ? ptr(pb.alpha) : nullptr, pb.act, mc.data());
-                    mb.strip = put(mc);
-                }
-                chain_off_[i].push_back(ma);
-                chain_off_[i].push_back(mb);
-            }
-            res_wblk_[i].clear();
-            res_cblob_[i].clear();
-            continue;
-        }
-        if (n.kind == Node::Resident && n.tail) {
-            // tail_kernels.hip: per stage the A operands of v_mfma_f32_16x16x4_f32 — lane (k-quarter kq = l / 16, row m = l % 16) holds, for
-            // float4 step i, W[16 tile + m][kq * Kv / 4 + 4 i .. + 3] ([O][KH][KW][I] read as [O][Kv]) — and the small constants:
-            // [bias][slope] padded to whole tiles, then for depthwise stages the taps [9][Kv] and the depthwise bias [Kv]
-            tail_wa_[i].assign(n.stages.size(), -1);
-            tail_wc_[i].assign(n.stages.size(), -1);
-            for (size_t k = 0; k < n.stages.size(); k++) {
-                const Node::Stage& sg = n.stages[k];
-                const TailStage& st = sg.tst;
-                if (st.kind == TAIL_LOAD) continue;
-                const Node& m = n.members[static_cast<size_t>(sg.member)];
-                const auto& wsrc = g.tensors[m.kind == Node::Conv ? m.w : m.w2].f32;
-                const int O = st.Co, Kv = st.Kv, nct = (O + 15) / 16, n4 = Kv / 16, K4 = Kv / 4;
-                if (wsrc.size() != static_cast<size_t>(O) * Kv) throw std::runtime_error("engine: tail stage weights do not match its shape");
-                std::vector<float> r(static_cast<size_t>(nct) * n4 * 256, 0.f);
-                for (int ct = 0; ct < nct; ct++)
-                    for (int q = 0; q < n4; q++)
-                        for (int l = 0; l < 64; l++)
-                            for (int e = 0; e < 4; e++) {
-                                const int o = 16 * ct + (l & 15), c = (l >> 4) * K4 + 4 * q + e;
-                                if (o < O) r[((static_cast<size_t>(ct) * n4 + q) * 64 + l) * 4 + e] = wsrc[static_cast<size_t>(o) * Kv + c];
-                            }
-                tail_wa_[i][k] = put(r);
-                const int bias_t = m.kind == Node::Conv ? m.b : m.b2;
-                std::vector<float> cb(static_cast<size_t>(32 * nct) + (st.kind == TAIL_DW ? static_cast<size_t>(10) * Kv : 0), 0.f);
-                for (int c = 0; c < O; c++) {
-                    cb[static_cast<size_t>(c)] = bias_t >= 0 ? g.tensors[bias_t].f32[static_cast<size_t>(c)] : 0.f;
-                    cb[static_cast<size_t>(16 * nct + c)] = m.act == ACT_PRELU ? g.tensors[m.alpha].f32[static_cast<size_t>(c)] : (m.act == ACT_NONE ? 1.f : 0.f);
-                }
-                if (st.kind == TAIL_DW) {
-                    const auto& wd = g.tensors[m.w].f32;  // [3][3][C]
-                    for (int t = 0; t < 9 * Kv; t++) cb[static_cast<size_t>(32 * nct + t)] = wd[static_cast<size_t>(t)];
-                    if (m.b >= 0)
-                        for (int c = 0; c < Kv; c++) cb[static_cast<size_t>(32 * nct + 9 * Kv + c)] = g.tensors[m.b].f32[static_cast<size_t>(c)];
-                }
-                tail_wc_[i][k] = put(cb);
-            }
-            continue;
-        }
-        if (n.kind == Node::Resident) {
-            for (const Node& m : n.members) {
-                MemberOff mo;
-                // pointwise / k x k stride-k weights in A-fragment order (the k x k ones over the virtual channels)
-                mo.w2 = pack_pw(m.kind == Node::Conv ? m.w : m.w2);
-                chain_off_[i].push_back(mo);
-            }
-            // per stage: the small constants, padded the way the kernel copies them to LDS
-            res_wblk_[i].assign(n.stages.size(), -1);
-            for (size_t k = 0; k < n.stages.size(); k++)
-                if (n.stages[k].st.kblk) {
-                    const Node& m = n.members[static_cast<size_t>(n.stages[k].member)];
-                    res_wblk_[i][k] = pack_pw(m.kind == Node::Conv ? m.w : m.w2, n.stages[k].st.kblk);
-                }
-            res_cblob_[i].assign(n.stages.size(), -1);
-            for (size_t k = 0; k < n.stages.size(); k++) {
-                const Node::Stage& sg = n.stages[k];
-                if (sg.st.kind == RES_STAGE_LOAD) continue;
-                const Node& m = n.members[static_cast<size_t>(sg.member)];
-                const ResStage& st = sg.st;
-                const int Cp = (st.Kv + 7) & ~7, Cop = (st.Co + 31) / 32 * 32;
-                std::vector<float> cb(static_cast<size_t>(resident_const_floats(st)), 0.f);
-                size_t o = 0;
-                const int bias_t = m.kind == Node::Conv ? m.b : m.b2;
-                if (st.kind == RES_STAGE_DW) {
-                    const auto& wd = g.tensors[m.w].f32;  // [3][3][C]
-                    for (int tap = 0; tap < 9; tap++)
-                        for (int c = 0; c < st.Kv; c++) cb[static_cast<size_t>(tap) * Cp + c] = wd[static_cast<size_t>(tap) * st.Kv + c];
-                    if (m.b >= 0)
-                        for (int c = 0; c < st.Kv; c++) cb[static_cast<size_t>(9) * Cp + c] = g.tensors[m.b].f32[c];
-                    o = static_cast<size_t>(10) * Cp;
-                }
-                for (int c = 0; c < st.Co; c++) {
-                    cb[o + c] = bias_t >= 0 ? g.tensors[bias_t].f32[c] : 0.f;
-                    cb[o + Cop + c] = m.act == ACT_PRELU ? g.tensors[m.alpha].f32[c] : (m.act == ACT_NONE ? 1.f : 0.f);
-                }
-                res_cblob_[i][k] = put(cb);
-            }
-            continue;
-        }
-        if (n.b >= 0) node_b_[i] = put(g.tensors[n.b].f32);
-        if (n.b2 >= 0) node_b2_[i] = put(g.tensors[n.b2].f32);
-        if (n.alpha >= 0) node_alpha_[i] = put(g.tensors[n.alpha].f32);
-        if (n.kind == Node::Conv && n.gemm_head) {
-            node_w_[i] = put(g.tensors[n.w].f32);  // [O][KH*KW*I] as stored: the GEMM's W[N][K]
-        } else if (n.kind == Node::Conv) {
-            const auto& ws = g.tensors[n.w].shape;  // [O][KH][KW][I]
-            const auto& src = g.tensors[n.w].f32;
-            int O = ws[0], KH = ws[1], KW = ws[2], I = ws[3], Cop = (O + 3) & ~3;
-            std::vector<float> r(static_cast<size_t>(KH) * KW * I * Cop, 0.f);
-            for (int o = 0; o < O; o++)
-                for (int ky = 0; ky < KH; ky++)
-                    for (int kx = 0; kx < KW; kx++)
-                        for (int c = 0; c < I; c++)
-                            r[((static_cast<size_t>(ky) * KW + kx) * I + c) * Cop + o] = src[((static_cast<size_t>(o) * KH + ky) * KW + kx) * I + c];
-            node_w_[i] = put(r);
-            // the face mesh's first convolution can run inside the launch of the block pair behind it (mdblock_kernels.hip, MD::STEM)
-            const auto& sxi = g.tensors[n.in[0]].shape;
-            const auto& sxo = g.tensors[n.out].shape;
-            if (sxi.size() == 4 && sxo.size() == 4 && n.padding == Padding::Same && n.ept < 0 && n.res < 0 && n.in[0] == g.inputs[0] &&
-                (n.act == ACT_NONE || n.act == ACT_RELU || n.act == ACT_RELU6 || n.act == ACT_PRELU) &&
-                mdblock_stem_shape_ok(sxi[1], sxi[2], sxi[3], n.KH, n.KW, n.sh, n.sw, sxo[1], sxo[2], sxo[3]) && !(n.act == ACT_PRELU && n.alpha < 0) &&
-                [&] {   // its output is read by the next node alone (the pair: as input and as the first block's skip) and is no graph output
-                    int readers = 0;
-                    for (const Node& m : plan_.nodes) {
-                        for (int t : m.in) readers += t == n.out ? 1 : 0;
-                        if (m.res == n.out) readers++;
-                    }
-                    bool is_out = false;
-                    for (int t : g.outputs) is_out = is_out || plan_.storage[t].root == plan_.storage[n.out].root;
-                    return readers == 1 && !is_out && i + 1 < NN && plan_.nodes[i + 1].kind == Node::Chain && plan_.nodes[i + 1].members.size() == 2 &&
-                           plan_.nodes[i + 1].in.size() >= 1 && plan_.nodes[i + 1].in[0] == n.out;
-                }()) {
-                std::vector<float> sc(static_cast<size_t>(mdblock_stem_consts_floats()));
-                mdblock_pack_stem(src.data(), n.b >= 0 ? g.tensors[n.b].f32.data() : nullptr, n.act == ACT_PRELU && n.alpha >= 0 ? g.tensors[n.alpha].f32.data() : nullptr, n.act, sc.data());
-                node_stem_[i] = put(sc);
-            }
-        } else if (n.kind == Node::Dw) {
-            node_w_[i] = put(g.tensors[n.w].f32);
-        } else if (n.kind == Node::Block) {
-            if (n.w >= 0) node_w_[i] = put(g.tensors[n.w].f32);
-            node_w2_[i] = pack_pw(n.w2);
-            const auto& ws = g.tensors[n.w2].shape;  // [O][1][1][I]
-            if (n.w >= 0 && n.sh == 1 && n.sw == 1 && n.padding == Padding::Same && strip_shape_ok(ws[3], ws[0])) {
-                std::vector<float> sc(static_cast<size_t>(strip_consts_floats(ws[3])));
-                strip_pack_consts(ws[3], g.tensors[n.w].f32.data(), n.b >= 0 ? g.tensors[n.b].f32.data() : nullptr, g.tensors[n.w2].f32.data(),
-                                  n.b2 >= 0 ? g.tensors[n.b2].f32.data() : nullptr, n.alpha >= 0 ? g.tensors[n.alpha].f32.data() : nullptr, n.act, sc.data());
-                node_strip_[i] = put(sc);
-            } else if (n.w >= 0 && n.sh == 1 && n.sw == 1 && n.padding == Padding::Same && mstrip_shape_ok(ws[3], ws[0]) && g.tensors[n.out].shape[2] == 32) {
-                std::vector<float> sc(static_cast<size_t>(mstrip_consts_floats(ws[3])));
-                mstrip_pack_consts(ws[3], g.tensors[n.w].f32.data(), n.b >= 0 ? g.tensors[n.b].f32.data() : nullptr, g.tensors[n.w2].f32.data(),
-                                   n.b2 >= 0 ? g.tensors[n.b2].f32.data() : nullptr, n.alpha >= 0 ? g.tensors[n.alpha].f32.data() : nullptr, n.act, sc.data());
-                node_strip_[i] = put(sc);
-            }
-            const int Wn = g.tensors[n.out].shape.size() == 4 ? g.tensors[n.out].shape[2] : 0;
-            if (n.w >= 0 && n.sh == 1 && n.sw == 1 && n.padding == Padding::Same && mwalk_shape_ok(Wn, ws[3], ws[0])) {
-                std::vector<float> sc(static_cast<size_t>(mwalk_consts_floats(Wn, ws[3], ws[0])));
-                mwalk_pack_consts(Wn, ws[3], ws[0], g.tensors[n.w].f32.data(), n.b >= 0 ? g.tensors[n.b].f32.data() : nullptr, g.tensors[n.w2].f32.data(),
-                                  n.b2 >= 0 ? g.tensors[n.b2].f32.data() : nullptr, n.alpha >= 0 ? g.tensors[n.alpha].f32.data() : nullptr, n.act, sc.data());
-                node_mwalk_[i] = put(sc);
-            }
-            // stride-2 blocks with an operand-layout form (ms2_kernels.hip; the same slot: a node is one or the other)
-            const auto& sin = g.tensors[n.in[0]].shape;
-            const bool pool_skip = n.res >= 0 && n.res == n.in[0] && n.res_mode == RES_MAXPOOL && !n.res_after;
-            if (n.w >= 0 && n.sh == 2 && n.sw == 2 && n.padding == Padding::Same && n.ept < 0 && sin.size() == 4 && (n.res < 0 || pool_skip) &&
-                ms2_shape_ok(sin[2], ws[3], ws[0], pool_skip)) {
-                std::vector<float> sc(static_cast<size_t>(ms2_consts_floats(sin[2], ws[3], ws[0], pool_skip)));
-                ms2_pack_consts(sin[2], ws[3], ws[0], pool_skip, g.tensors[n.w].f32.data(), n.b >= 0 ? g.tensors[n.b].f32.data() : nullptr, g.tensors[n.w2].f32.data(),
-                                n.b2 >= 0 ? g.tensors[n.b2].f32.data() : nullptr, n.alpha >= 0 ? g.tensors[n.alpha].f32.data() : nullptr, n.act, sc.data());
-                node_mwalk_[i] = put(sc);
-            }
-        }
-    }
-    // two plain BlazeBlocks in a row on a layer mdblock_kernels.hip has a pair form for (the face mesh's 48x48x32 blocks, round 6): the constants of the pair
-    // launch, kept at the first node; which form runs is decided per launch
-    for (size_t i = 0; i + 1 < NN; i++) {
-        const Node &pa = plan_.nodes[i], &pb = plan_.nodes[i + 1];
-        auto plain = [&](const Node& m) {
-            return m.kind == Node::Block && m.w >= 0 && m.in.size() == 1 && m.sh == 1 && m.sw == 1 && m.res == m.in[0] && m.res_mode == RES_DIRECT && !m.res_after &&
-                   m.padding == Padding::Same && m.ept < 0 && (m.act != ACT_PRELU || m.alpha >= 0);
-        };
-        if (!plain(pa) || !plain(pb) || pb.in[0] != pa.out) continue;
-        const auto& sx = g.tensors[pa.in[0]].shape;
-        if (sx.size() != 4 || g.tensors[pa.out].shape != sx || g.tensors[pb.out].shape != sx || !mdblock_shape_ok(sx[2], sx[3], sx[3], sx[3], true)) continue;
-        // the tensor between the two is never written by that launch: nobody else may read it
-        bool only_reader = true;
-        for (size_t j = 0; j < NN && only_reader; j++) {
-            if (j == i + 1) continue;
-            for (int t : plan_.nodes[j].in) only_reader = only_reader && t != pa.out;
-            only_reader = only_reader && plan_.nodes[j].res != pa.out;
-        }
-        for (int t : g.outputs) only_reader = only_reader && plan_.storage[t].root != plan_.storage[pa.out].root;
-        if (!only_reader) continue;
-        std::vector<float> mc(static_cast<size_t>(mdblock_consts_floats(sx[2], sx[3], sx[3], sx[3], true)));
-        auto ptr = [&](int t) { return t >= 0 ? g.tensors[t].f32.data() : nullptr; };
-        mdblock_pack_consts(sx[2], sx[3], sx[3], sx[3], ptr(pa.w), ptr(pa.b), ptr(pa.w2), ptr(pa.b2), pa.act == ACT_PRELU ? ptr(pa.alpha) : nullptr, pa.act,
-                            ptr(pb.w), ptr(pb.b), ptr(pb.w2), ptr(pb.b2), pb.act == ACT_PRELU ? ptr(pb.alpha) : nullptr, pb.act, mc.data(), true);
-        node_pair_[i] = put(mc);
-    }
-    host.resize(host.size() + 4096, 0.f);  // slack: the stage programs' A-fragment prefetch walks up to 8 KiB past a tile's last chunk
-    if (d_weights_) hip_check(hipFree(d_weights_), "hipFree");
-    d_weights_ = nullptr;
-    hip_check(hipMalloc(reinterpret_cast<void**>(&d_weights_), std::max<size_t>(host.size(), 64) * sizeof(float)), "hipMalloc weights");
-    hip_check(hipMemcpy(d_weights_, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice), "upload weights");
-    // ---- stage programs of the resident launches: pointer-free descriptors, resolved against ResBases at launch
-    {
-        std::vector<ResStage> progs;
-        node_prog_.assign(NN, -1);
-        auto ref = [&](int t) {
-            ResRef r;
-            const Storage& st = plan_.storage[t];
-            r.inner = st.offset;
-            r.fs = st.frame_stride;
-            if (st.root == plan_.storage[g.inputs[0]].root) { r.base = 1; return r; }
-            for (size_t k = 0; k < g.outputs.size(); k++)
-                if (plan_.storage[g.outputs[k]].root == st.root) {
-                    if (2 + k >= static_cast<size_t>(kResBases)) throw std::runtime_error("stage program: too many graph outputs");
-                    r.base = 2 + static_cast<int>(k);
-                    return r;
-                }
-            if (plan_.root_offset[st.root] < 0) throw std::runtime_error("stage program: tensor has no storage");
-            r.base = 0;
-            r.root_off = plan_.root_offset[st.root];
-            return r;
-        };
-        std::vector<TailStage> tprogs;
-        for (size_t i = 0; i < NN; i++) {
-            const Node& n = plan_.nodes[i];
-            if (n.kind != Node::Resident || !n.tail) continue;
-            node_prog_[i] = static_cast<long>(tprogs.size());
-            for (size_t k = 0; k < n.stages.size(); k++) {
-                const Node::Stage& sg = n.stages[k];
-                TailStage st = sg.tst;
-                if (sg.src_t >= 0) st.src_g = ref(sg.src_t);
-                if (st.kind != TAIL_LOAD) {
-                    if (sg.dst_t >= 0) st.dst_g = ref(sg.dst_t);
-                    if (sg.res_t >= 0) st.res_g = ref(sg.res_t);
-                    st.w_a = tail_wa_[i][k];
-                    st.w_c = tail_wc_[i][k];
-                }
-                tprogs.push_back(st);
-            }
-        }
-        if (d_tail_programs_) hip_check(hipFree(d_tail_programs_), "hipFree");
-        d_tail_programs_ = nullptr;
-        if (!tprogs.empty()) {
-            hip_check(hipMalloc(reinterpret_cast<void**>(&d_tail_programs_), tprogs.size() * sizeof(TailStage)), "hipMalloc programs");
-            hip_check(hipMemcpy(d_tail_programs_, tprogs.data(), tprogs.size() * sizeof(TailStage), hipMemcpyHostToDevice), "upload programs");
-        }
-        for (size_t i = 0; i < NN; i++) {
-            const Node& n = plan_.nodes[i];
-            if (n.kind != Node::Resident || n.tail) continue;
-            node_prog_[i] = static_cast<long>(progs.size());
-            for (const Node::Stage& sg : n.stages) {
-                ResStage st = sg.st;
-                if (sg.src_t >= 0) st.src_g = ref(sg.src_t);
-                if (st.kind != RES_STAGE_LOAD) {
-                    if (sg.dst_t >= 0) st.dst_g = ref(sg.dst_t);
-                    if (sg.res_t >= 0) st.res_g = ref(sg.res_t);
-                    const size_t k = static_cast<size_t>(&sg - n.stages.data());
-                    st.w_pw = st.kblk ? res_wblk_[i][k] : chain_off_[i][static_cast<size_t>(sg.member)].w2;
-                    st.cblob = res_cblob_[i][k];
-                }
-                progs.push_back(st);
-            }
-        }
-        if (d_programs_) hip_check(hipFree(d_programs_), "hipFree");
-        d_programs_ = nullptr;
-        if (!progs.empty()) {
-            hip_check(hipMalloc(reinterpret_cast<void**>(&d_programs_), progs.size() * sizeof(ResStage)), "hipMalloc programs");
-            hip_check(hipMemcpy(d_programs_, progs.data(), progs.size() * sizeof(ResStage), hipMemcpyHostToDevice), "upload programs");
-        }
-    }
-    // ---- output heads that may run beside the trunk: compute nodes whose output lives in a graph-output buffer and is
-    // read by no other launch, and that come after the last trunk node in plan order (so no later trunk launch can
-    // re-use arena memory they still read: the arena's liveness analysis follows plan order)
-    {
-        const size_t N = plan_.nodes.size();
-        head_slot_.assign(N, -1); head_wait_.assign(N, -1); event_after_.assign(N, 0);
-        auto is_view = [&](const Node& n) { return n.kind == Node::Reshape || n.kind == Node::Concat; };
-        auto root = [&](int t) { return plan_.storage[t].root; };
-        std::vector<int> out_roots;
-        for (int o : g.outputs) out_roots.push_back(root(o));
-        std::vector<char> head(N, 0);
-        int last_trunk = -1;
-        for (size_t i = 0; i < N; i++) {
-            const Node& n = plan_.nodes[i];
-            if (is_view(n)) continue;
-            bool feeds_output = std::find(out_roots.begin(), out_roots.end(), root(n.out)) != out_roots.end();
-            for (size_t j = 0; j < N && feeds_output; j++) {
-                const Node& m = plan_.nodes[j];
-                if (is_view(m)) continue;
-                for (int x : m.in) if (x == n.out) feeds_output = false;
-                if (m.res == n.out) feeds_output = false;
-            }
-            if (n.kind == Node::Resident && (n.in.size() != 1 || !n.extra_out.empty())) feeds_output = false;  // several inputs / outputs: stays on the trunk
-            head[i] = feeds_output;
-            if (!feeds_output) last_trunk = static_cast<int>(i);
-        }
-        std::vector<int> slot_of_producer(N + 1, -1);
-        int slots = 0;
-        for (size_t i = 0; i < N; i++) {
-            const Node& n = plan_.nodes[i];
-            if (!head[i] || static_cast<int>(i) < last_trunk || is_view(n)) continue;
-            int prod = -1;  // the launch that produces (the buffer of) its input
-            for (size_t j = 0; j < i; j++) {
-                if (is_view(plan_.nodes[j])) continue;
-                bool makes = root(plan_.nodes[j].out) == root(n.in[0]);
-                for (int t : plan_.nodes[j].extra_out) makes |= root(t) == root(n.in[0]);
-                if (makes) prod = static_cast<int>(j);
-            }
-            if (n.res >= 0 && n.res != n.in[0]) continue;  // two producers: keep it on the trunk
-            // heads are spread round robin over `heads` side streams (option, default 1).  They are independent of each other, but
-            // on BackCamera (four small heads behind the last trunk launch) every extra parallel branch of the replay graph cost
-            // more than it hid: 1.675 ms per step with 1 stream, 1.69 / 1.68 / 1.72 with 2 / 3 / 4
-            (void)slot_of_producer;
-            head_slot_[i] = slots++ % std::max(1, std::min(head_streams_opt_, kHeadStreams));
-            head_wait_[i] = prod;
-            if (prod >= 0) event_after_[prod] = 1;
-        }
-        // tail branches (Plan::branch): chain 0 stays on the trunk stream, every other chain runs on a side stream behind the launch
-        // that produced its newest input (the trunk runs in plan order, so the older inputs are done by then; launches of the same
-        // chain share a stream).  The arena keeps everything the branches touch allocated to the end of the plan.
-        static const bool no_branches = getenv("MI_NO_BRANCHES") != nullptr;  // development aid
-        for (size_t i = 0; i < N && !no_branches && plan_.branch.size() == N; i++) {
-            const Node& n = plan_.nodes[i];
-            if (plan_.branch[i] < 1 || is_view(n)) continue;
-            int prod = -1;
-            std::vector<int> srcs = n.in;
-            if (n.res >= 0) srcs.push_back(n.res);
-            for (int t : srcs)
-                for (size_t j = 0; j < i; j++) {
-                    if (is_view(plan_.nodes[j])) continue;
-                    bool makes = root(plan_.nodes[j].out) == root(t);
-                    for (int x : plan_.nodes[j].extra_out) makes |= root(x) == root(t);
-                    if (makes) prod = std::max(prod, static_cast<int>(j));
-                }
-            head_slot_[i] = (plan_.branch[i] - 1) % std::max(1, std::min(head_streams_opt_, kHeadStreams));
-            head_wait_[i] = prod;
-            if (prod >= 0) event_after_[static_cast<size_t>(prod)] = 1;
-        }
-    }
+    consts_ = pack_plan_consts(plan_);  // every constant the launches need and the stage programs (consts.cpp)
+    upload(d_weights_, consts_.blob, "hipMalloc weights", "upload weights");  // (never empty: the blob ends in its slack)
+    upload(d_tail_programs_, consts_.tail_progs, "hipMalloc programs", "upload programs");
+    upload(d_programs_, consts_.progs, "hipMalloc programs", "upload programs");
+    schedule_side_streams();
     build_bandnet();
     dirty_ = false;
     chunk_cap_ = 0;
+}
+
+// Output heads that may run beside the trunk: compute nodes whose output lives in a graph-output buffer and is
+// read by no other launch, and that come after the last trunk node in plan order (so no later trunk launch can
+// re-use arena memory they still read: the arena's liveness analysis follows plan order)
+void Model::schedule_side_streams() {
+    const Graph& g = plan_.graph;
+    const size_t N = plan_.nodes.size();
+    head_slot_.assign(N, -1); head_wait_.assign(N, -1); event_after_.assign(N, 0);
+    auto is_view = [&](const Node& n) { return n.kind == Node::Reshape || n.kind == Node::Concat; };
+    auto root = [&](int t) { return plan_.storage[t].root; };
+    auto producer = [&](int t, size_t before) {  // the last launch in front of node `before` that writes (the buffer of) tensor t, -1: none
+        int prod = -1;
+        for (size_t j = 0; j < before; j++) {
+            if (is_view(plan_.nodes[j])) continue;
+            bool makes = root(plan_.nodes[j].out) == root(t);
+            for (int x : plan_.nodes[j].extra_out) makes |= root(x) == root(t);
+            if (makes) prod = static_cast<int>(j);
+        }
+        return prod;
+    };
+    auto beside = [&](size_t i, int slot, int prod) {  // node i runs on side stream `slot`, behind launch prod
+        head_slot_[i] = slot % std::max(1, std::min(head_streams_opt_, kHeadStreams));
+        head_wait_[i] = prod;
+        if (prod >= 0) event_after_[static_cast<size_t>(prod)] = 1;
+    };
+    std::vector<int> out_roots;
+    for (int o : g.outputs) out_roots.push_back(root(o));
+    std::vector<char> head(N, 0);
+    int last_trunk = -1;
+    for (size_t i = 0; i < N; i++) {
+        const Node& n = plan_.nodes[i];
+        if (is_view(n)) continue;
+        bool feeds_output = std::find(out_roots.begin(), out_roots.end(), root(n.out)) != out_roots.end();
+        for (size_t j = 0; j < N && feeds_output; j++) {
+            const Node& m = plan_.nodes[j];
+            if (is_view(m)) continue;
+            for (int x : m.in) if (x == n.out) feeds_output = false;
+            if (m.res == n.out) feeds_output = false;
+        }
+        if (n.kind == Node::Resident && (n.in.size() != 1 || !n.extra_out.empty())) feeds_output = false;  // several inputs / outputs: stays on the trunk
+        head[i] = feeds_output;
+        if (!feeds_output) last_trunk = static_cast<int>(i);
+    }
+    int slots = 0;
+    for (size_t i = 0; i < N; i++) {
+        const Node& n = plan_.nodes[i];
+        if (!head[i] || static_cast<int>(i) < last_trunk || is_view(n)) continue;
+        if (n.res >= 0 && n.res != n.in[0]) continue;  // two producers: keep it on the trunk
+        // heads are spread round robin over `heads` side streams (option, default 1).  They are independent of each other, but
+        // on BackCamera (four small heads behind the last trunk launch) every extra parallel branch of the replay graph cost
+        // more than it hid: 1.675 ms per step with 1 stream, 1.69 / 1.68 / 1.72 with 2 / 3 / 4
+        beside(i, slots++, producer(n.in[0], i));
+    }
+    // tail branches (Plan::branch): chain 0 stays on the trunk stream, every other chain runs on a side stream behind the launch
+    // that produced its newest input (the trunk runs in plan order, so the older inputs are done by then; launches of the same
+    // chain share a stream).  The arena keeps everything the branches touch allocated to the end of the plan.
+    static const bool no_branches = getenv("MI_NO_BRANCHES") != nullptr;  // development aid
+    for (size_t i = 0; i < N && !no_branches && plan_.branch.size() == N; i++) {
+        const Node& n = plan_.nodes[i];
+        if (plan_.branch[i] < 1 || is_view(n)) continue;
+        int prod = n.res >= 0 ? producer(n.res, i) : -1;
+        for (int t : n.in) prod = std::max(prod, producer(t, i));
+        beside(i, plan_.branch[i] - 1, prod);
+    }
 }
 
 void Model::free_bandnet() {
@@ -937,7 +474,7 @@ void Model::build_bandnet_try(bool conv2_ok) {
         std::vector<float> cb(static_cast<size_t>(32 * nct + (dw_block ? 10 * C : 0)), 0.f);
         for (int c = 0; c < Co; c++) {
             cb[static_cast<size_t>(c)] = bt >= 0 ? g.tensors[bt].f32[static_cast<size_t>(c)] : 0.f;
-            cb[static_cast<size_t>(16 * nct + c)] = n.act == ACT_PRELU ? g.tensors[n.alpha].f32[static_cast<size_t>(c)] : (n.act == ACT_NONE ? 1.f : 0.f);
+            cb[static_cast<size_t>(16 * nct + c)] = act_slope(g, n, c);
         }
         if (dw_block) {
             const auto& wd = g.tensors[n.w].f32;  // [1][3][3][C]
@@ -1711,8 +1248,8 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
         const auto& so = g.tensors[n.out].shape;
         auto dim = [](const std::vector<int>& v, size_t d) { return d < v.size() ? v[d] : 1; };
         Epilogue ep;
-        ep.bias = (n.kind == Node::Block ? node_b2_[i] : node_b_[i]) >= 0 ? d_weights_ + (n.kind == Node::Block ? node_b2_[i] : node_b_[i]) : nullptr;
-        ep.alpha = node_alpha_[i] >= 0 ? d_weights_ + node_alpha_[i] : nullptr;
+        ep.bias = (n.kind == Node::Block ? consts_.node_b2[i] : consts_.node_b[i]) >= 0 ? d_weights_ + (n.kind == Node::Block ? consts_.node_b2[i] : consts_.node_b[i]) : nullptr;
+        ep.alpha = consts_.node_alpha[i] >= 0 ? d_weights_ + consts_.node_alpha[i] : nullptr;
         ep.act = n.act;
         if (n.res >= 0) {
             const auto& sr = g.tensors[n.res].shape;
@@ -1736,7 +1273,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                 if (n.gemm_head) {
                     HeadGemmArgs h;
                     h.in = ip; h.out = op; h.in_fs = in_fs; h.out_fs = out_fs;
-                    h.w = d_weights_ + node_w_[i];
+                    h.w = d_weights_ + consts_.node_w[i];
                     h.bias = ep.bias; h.alpha = ep.alpha; h.act = ep.act;
                     h.B = F; h.K = si[1] * si[2] * si[3]; h.N = so[3];
                     rc = launch_head_gemm(h, s);
@@ -1744,9 +1281,9 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                     break;
                 }
                 // the first convolution inside the launch of the pair of BlazeBlocks behind it (f32 pictures, from 32 frames on: mdblock_kernels.hip, MD::STEM)
-                if (strip_ && stem_fuse_ && node_stem_[i] >= 0 && !u8_.frames) {   // (node_stem_: the graph's side of the conditions, checked when the constants were packed)
+                if (strip_ && stem_fuse_ && consts_.node_stem[i] >= 0 && !u8_.frames) {   // (consts_.node_stem: the graph's side of the conditions, checked when the constants were packed)
                     const size_t j = i + 1;
-                    if (node_mwalk_[j] >= 0 && !event_after_[i] && head_slot_[j] < 0) {
+                    if (consts_.node_chain_pair[j] >= 0 && !event_after_[i] && head_slot_[j] < 0) {
                         const Node& c = plan_.nodes[j];
                         const auto& co = g.tensors[c.out].shape;
                         DblockArgs d;
@@ -1757,8 +1294,8 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                         d.hi2 = c.members[1].act == ACT_RELU6 ? 6.f : INFINITY;
                         d.skip1 = 1; d.skip2_from_a = 1;
                         d.act1 = c.members[0].act; d.act2 = c.members[1].act;
-                        d.mconsts = d_weights_ + node_mwalk_[j];
-                        d.stem_in = ip; d.stem_in_fs = in_fs; d.stem_consts = d_weights_ + node_stem_[i];
+                        d.mconsts = d_weights_ + consts_.node_chain_pair[j];
+                        d.stem_in = ip; d.stem_in_fs = in_fs; d.stem_consts = d_weights_ + consts_.node_stem[i];
                         d.stem_hi = n.act == ACT_RELU6 ? 6.f : INFINITY;
                         d.band_rows = mdb_band_;
                         if (mdblock_kernel_supports(d)) {
@@ -1771,7 +1308,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                 }
                 ConvArgs a;
                 a.in = ip; a.out = op; a.in_fs = in_fs; a.out_fs = out_fs;
-                a.w = d_weights_ + node_w_[i];
+                a.w = d_weights_ + consts_.node_w[i];
                 a.B = F; a.H = si[1]; a.W = si[2]; a.C = si[3]; a.Ho = so[1]; a.Wo = so[2]; a.Co = so[3]; a.Cop = (a.Co + 3) & ~3;
                 a.KH = n.KH; a.KW = n.KW; a.sh = n.sh; a.sw = n.sw;
                 if (n.padding == Padding::Same) { same_pad(a.H, a.KH, a.sh, a.Ho, &a.pt); same_pad(a.W, a.KW, a.sw, a.Wo, &a.pl); }
@@ -1790,7 +1327,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
             case Node::Dw: {
                 DwArgs a;
                 a.in = ip; a.out = op; a.in_fs = in_fs; a.out_fs = out_fs;
-                a.w = d_weights_ + node_w_[i];
+                a.w = d_weights_ + consts_.node_w[i];
                 a.B = F; a.H = si[1]; a.W = si[2]; a.C = si[3]; a.Ho = so[1]; a.Wo = so[2];
                 a.KH = n.KH; a.KW = n.KW; a.sh = n.sh; a.sw = n.sw;
                 if (n.padding == Padding::Same) { same_pad(a.H, a.KH, a.sh, a.Ho, &a.pt); same_pad(a.W, a.KW, a.sw, a.Wo, &a.pl); }
@@ -1806,9 +1343,9 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                     a.B = F; a.H = si[1]; a.W = si[2]; a.nstages = static_cast<int>(n.members.size());
                     for (size_t k = 0; k < n.members.size(); k++) {
                         const Node& m = n.members[k];
-                        const MemberOff& mo = chain_off_[i][k];
+                        const MemberOff& mo = consts_.chain_off[i][k];
                         XcStage& st = a.st[k];
-                        st.cblob = d_weights_ + mo.strip;
+                        st.cblob = d_weights_ + mo.cblob;
                         st.has_dw = m.w >= 0;
                         st.w_pw = d_weights_ + mo.w2;
                         st.C = g.tensors[m.in[0]].shape[3]; st.Co = g.tensors[m.out].shape[3]; st.act = m.act;
@@ -1825,15 +1362,15 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                     DblockArgs a;
                     a.in = ip; a.in_fs = in_fs; a.out = op; a.out_fs = out_fs;
                     a.B = F; a.H = si[1]; a.W = si[2]; a.C = si[3]; a.Cm = g.tensors[n.members[0].out].shape[3]; a.Co = so[3];
-                    a.w1 = d_weights_ + chain_off_[i][0].w2;
-                    a.w2 = d_weights_ + chain_off_[i][1].w2;
-                    a.consts = d_weights_ + chain_off_[i][0].strip;
+                    a.w1 = d_weights_ + consts_.chain_off[i][0].w2;
+                    a.w2 = d_weights_ + consts_.chain_off[i][1].w2;
+                    a.consts = d_weights_ + consts_.chain_off[i][0].cblob;
                     a.hi1 = n.members[0].act == ACT_RELU6 ? 6.f : INFINITY;
                     a.hi2 = n.members[1].act == ACT_RELU6 ? 6.f : INFINITY;
                     a.skip1 = n.members[0].res >= 0;                       // two plain BlazeBlocks: each adds its own input
                     a.skip2_from_a = n.members[1].res == n.members[0].out;
                     a.act1 = n.members[0].act; a.act2 = n.members[1].act;
-                    if (chain_off_[i][1].strip >= 0) a.mconsts = d_weights_ + chain_off_[i][1].strip;
+                    if (consts_.chain_off[i][1].mconsts >= 0) a.mconsts = d_weights_ + consts_.chain_off[i][1].mconsts;
                     if (strip_ && mdblock_kernel_supports(a)) {
                         if (labels) labels->back() = "mdblock_kernel";
                         rc = launch_mdblock(a, s);
@@ -1849,15 +1386,15 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                     a.nblocks = static_cast<int>(n.members.size() / 2);
                     a.bands = n.res_bands;
                     for (int k = 0; k < a.nblocks; k++) {
-                        const MemberOff &ma = chain_off_[i][static_cast<size_t>(2 * k)], &mb = chain_off_[i][static_cast<size_t>(2 * k + 1)];
+                        const MemberOff &ma = consts_.chain_off[i][static_cast<size_t>(2 * k)], &mb = consts_.chain_off[i][static_cast<size_t>(2 * k + 1)];
                         a.blocks[k].w1 = d_weights_ + ma.w2;
                         a.blocks[k].w2 = d_weights_ + mb.w2;
-                        a.blocks[k].consts = d_weights_ + ma.strip;
+                        a.blocks[k].consts = d_weights_ + ma.cblob;
                         a.blocks[k].hi1 = n.members[static_cast<size_t>(2 * k)].act == ACT_RELU6 ? 6.f : INFINITY;
                         a.blocks[k].hi2 = n.members[static_cast<size_t>(2 * k + 1)].act == ACT_RELU6 ? 6.f : INFINITY;
                         a.blocks[k].act1 = n.members[static_cast<size_t>(2 * k)].act;
                         a.blocks[k].act2 = n.members[static_cast<size_t>(2 * k + 1)].act;
-                        if (mb.strip >= 0) a.blocks[k].mconsts = d_weights_ + mb.strip;
+                        if (mb.mconsts >= 0) a.blocks[k].mconsts = d_weights_ + mb.mconsts;
                     }
                     if (strip_ && mbneck_kernel_supports(a)) {
                         if (labels) labels->back() = "mbneck_kernel";
@@ -1869,7 +1406,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                 }
                 if (n.tail) {
                     TailLaunch a;
-                    a.prog = d_tail_programs_ + node_prog_[i];
+                    a.prog = d_tail_programs_ + consts_.node_prog[i];
                     a.nstages = static_cast<int>(n.stages.size());
                     a.B = F;
                     a.frame_floats = n.tail_frame_floats;
@@ -1889,7 +1426,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                     break;
                 }
                 ResLaunch a;
-                a.prog = d_programs_ + node_prog_[i];
+                a.prog = d_programs_ + consts_.node_prog[i];
                 a.nstages = static_cast<int>(n.stages.size());
                 a.B = F;
                 a.bands = n.res_bands;
@@ -1909,7 +1446,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
             case Node::Chain: {
                 ChainArgs a;
                 auto fill = [&](ChainBlock& cb, size_t k) {
-                    const MemberOff& mo = chain_off_[i][k];
+                    const MemberOff& mo = consts_.chain_off[i][k];
                     cb.w_dw = d_weights_ + mo.w;
                     cb.b_dw = mo.b >= 0 ? d_weights_ + mo.b : nullptr;
                     cb.w_pw = d_weights_ + mo.w2;
@@ -1943,8 +1480,8 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                         const Node::HeadPair& hp = n.head_pairs[k];
                         ChainHead& H = a.heads[hp.src];
                         H.on = 1; H.src = hp.src;
-                        H.w_pw = d_weights_ + chain_head_off_[i][k].w2;
-                        H.bias = d_weights_ + chain_head_off_[i][k].b2;
+                        H.w_pw = d_weights_ + consts_.chain_head_off[i][k].w2;
+                        H.bias = d_weights_ + consts_.chain_head_off[i][k].b2;
                         const int ta = n.head_nodes[static_cast<size_t>(hp.a)].out;
                         H.Co_a = g.tensors[ta].shape.back();
                         H.out_a = tensor_ptr_mut(ta, chunk_start, &H.out_a_fs);
@@ -1965,7 +1502,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                     rc = launch_chain(a, s);
                     break;
                 }
-                if (strip_ && node_mwalk_[i] >= 0) {   // a pair of plain BlazeBlocks with an operand-layout form
+                if (strip_ && consts_.node_chain_pair[i] >= 0) {   // a pair of plain BlazeBlocks with an operand-layout form
                     DblockArgs d;
                     d.in = ip; d.in_fs = in_fs; d.out = op; d.out_fs = out_fs;
                     d.B = F; d.H = si[1]; d.W = si[2]; d.C = si[3]; d.Cm = g.tensors[n.members[0].out].shape[3]; d.Co = so[3];
@@ -1973,7 +1510,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                     d.hi2 = n.members[1].act == ACT_RELU6 ? 6.f : INFINITY;
                     d.skip1 = 1; d.skip2_from_a = 1;
                     d.act1 = n.members[0].act; d.act2 = n.members[1].act;
-                    d.mconsts = d_weights_ + node_mwalk_[i];
+                    d.mconsts = d_weights_ + consts_.node_chain_pair[i];
                     d.band_rows = mdb_band_;
                     if (mdblock_kernel_supports(d)) {
                         if (labels) labels->back() = "mdblock_kernel<pair>";
@@ -1984,7 +1521,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                 // row-pipelined group of strip blocks: only the first input and the last output exist in memory
                 std::vector<BlockArgs> blk(n.members.size());
                 for (size_t k = 0; k < n.members.size(); k++) {
-                    const MemberOff& mo = chain_off_[i][k];
+                    const MemberOff& mo = consts_.chain_off[i][k];
                     const Node& m = n.members[k];
                     BlockArgs& b = blk[k];
                     b.in = ip; b.out = op; b.in_fs = in_fs; b.out_fs = out_fs;
@@ -2046,18 +1583,18 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                 BlockArgs a;
                 a.in = ip; a.out = op; a.in_fs = in_fs; a.out_fs = out_fs;
                 a.has_dw = n.w >= 0;
-                a.w_dw = a.has_dw ? d_weights_ + node_w_[i] : nullptr;
-                a.b_dw = node_b_[i] >= 0 ? d_weights_ + node_b_[i] : nullptr;
-                a.w_pw = d_weights_ + node_w2_[i];
+                a.w_dw = a.has_dw ? d_weights_ + consts_.node_w[i] : nullptr;
+                a.b_dw = consts_.node_b[i] >= 0 ? d_weights_ + consts_.node_b[i] : nullptr;
+                a.w_pw = d_weights_ + consts_.node_w2[i];
                 a.B = F; a.H = si[1]; a.W = si[2]; a.C = si[3]; a.Ho = so[1]; a.Wo = so[2]; a.Co = so[3];
                 a.sh = n.sh; a.sw = n.sw;
                 if (a.has_dw && n.padding == Padding::Same) { same_pad(a.H, 3, a.sh, a.Ho, &a.pt); same_pad(a.W, 3, a.sw, a.Wo, &a.pl); }
                 if (a.has_dw && n.ept >= 0) { a.pt = n.ept; a.pl = n.epl; }
                 a.ep = ep;
-                a.w_strip = node_strip_[i] >= 0 ? d_weights_ + node_strip_[i] : nullptr;
-                a.w_mwalk = node_mwalk_[i] >= 0 ? d_weights_ + node_mwalk_[i] : nullptr;
+                a.w_strip = consts_.node_strip[i] >= 0 ? d_weights_ + consts_.node_strip[i] : nullptr;
+                a.w_mwalk = consts_.node_mwalk[i] >= 0 ? d_weights_ + consts_.node_mwalk[i] : nullptr;
                 // this block and the next one as ONE launch (mdblock_kernel, pair form): the tensor between them is neither written nor read
-                if (strip_ && pair_fuse_ && node_pair_[i] >= 0 && i + 1 < plan_.nodes.size() && !event_after_[i] && head_slot_[i + 1] < 0 && head_slot_[i] < 0) {
+                if (strip_ && pair_fuse_ && consts_.node_pair[i] >= 0 && i + 1 < plan_.nodes.size() && !event_after_[i] && head_slot_[i + 1] < 0 && head_slot_[i] < 0) {
                     const Node& nb = plan_.nodes[i + 1];
                     {
                         DblockArgs d;
@@ -2069,7 +1606,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                         d.hi2 = nb.act == ACT_RELU6 ? 6.f : INFINITY;
                         d.skip1 = 1; d.skip2_from_a = 1;
                         d.act1 = n.act; d.act2 = nb.act;
-                        d.mconsts = d_weights_ + node_pair_[i];
+                        d.mconsts = d_weights_ + consts_.node_pair[i];
                         d.band_rows = mdb_band_;
                         // (the launch reads its input while it writes its output: the arena keeps the two apart — plan.cpp, liveness — and this checks it)
                         const bool apart = d.out + d.out_fs * F <= d.in || d.in + d.in_fs * F <= d.out;
@@ -2099,7 +1636,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                     std::vector<BlockArgs> run{a};
                     for (size_t j = i + 1; j < plan_.nodes.size() && run.size() < 8; j++) {
                         const Node& m = plan_.nodes[j];
-                        if (m.kind != Node::Block || m.w < 0 || m.in.size() != 1 || m.in[0] != plan_.nodes[j - 1].out || node_strip_[j] < 0 || head_slot_[j] >= 0) break;
+                        if (m.kind != Node::Block || m.w < 0 || m.in.size() != 1 || m.in[0] != plan_.nodes[j - 1].out || consts_.node_strip[j] < 0 || head_slot_[j] >= 0) break;
                         const auto& mi_ = g.tensors[m.in[0]].shape;
                         const auto& mo_ = g.tensors[m.out].shape;
                         if (mi_.size() != 4 || mo_ != mi_) break;
@@ -2107,16 +1644,16 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
                         bb.in = tensor_ptr(m.in[0], in, chunk_start, &bb.in_fs);
                         bb.out = tensor_ptr_mut(m.out, chunk_start, &bb.out_fs);
                         bb.has_dw = 1;
-                        bb.w_dw = d_weights_ + node_w_[j];
-                        bb.b_dw = node_b_[j] >= 0 ? d_weights_ + node_b_[j] : nullptr;
-                        bb.w_pw = d_weights_ + node_w2_[j];
-                        bb.w_strip = d_weights_ + node_strip_[j];
+                        bb.w_dw = d_weights_ + consts_.node_w[j];
+                        bb.b_dw = consts_.node_b[j] >= 0 ? d_weights_ + consts_.node_b[j] : nullptr;
+                        bb.w_pw = d_weights_ + consts_.node_w2[j];
+                        bb.w_strip = d_weights_ + consts_.node_strip[j];
                         bb.B = F; bb.H = mi_[1]; bb.W = mi_[2]; bb.C = mi_[3]; bb.Ho = mo_[1]; bb.Wo = mo_[2]; bb.Co = mo_[3];
                         bb.sh = m.sh; bb.sw = m.sw;
                         if (m.padding == Padding::Same) { same_pad(bb.H, 3, bb.sh, bb.Ho, &bb.pt); same_pad(bb.W, 3, bb.sw, bb.Wo, &bb.pl); }
                         if (m.ept >= 0) break;
-                        bb.ep.bias = node_b2_[j] >= 0 ? d_weights_ + node_b2_[j] : nullptr;
-                        bb.ep.alpha = node_alpha_[j] >= 0 ? d_weights_ + node_alpha_[j] : nullptr;
+                        bb.ep.bias = consts_.node_b2[j] >= 0 ? d_weights_ + consts_.node_b2[j] : nullptr;
+                        bb.ep.alpha = consts_.node_alpha[j] >= 0 ? d_weights_ + consts_.node_alpha[j] : nullptr;
                         bb.ep.act = m.act;
                         if (m.res >= 0) {
                             if (m.res != m.in[0] || m.res_mode != RES_DIRECT || m.res_after) break;
@@ -2235,7 +1772,7 @@ bool Model::takes_u8_input() {
             static const float some_bias = 0.f;
             a.ep.bias = &some_bias;
             a.ep.res_mode = n.res >= 0 ? n.res_mode : RES_NONE;
-            stem = conv_takes_u8(a) && node_b_[&n - plan_.nodes.data()] >= 0;
+            stem = conv_takes_u8(a) && consts_.node_b[&n - plan_.nodes.data()] >= 0;
         }
     }
     return readers == 1 && stem;
@@ -2332,7 +1869,7 @@ int Model::band_workgroups(int batch) {
 }
 
 bool Model::band_failed() {
-    if (band_test_fail_ && band_ran_) { band_test_fail_ = false; band_ran_ = false; return true; }
+    if (band_test_fail_ && band_ran_) { band_test_fail_ = 0; band_ran_ = false; return true; }
     const bool ran = band_ran_;
     band_ran_ = false;
     if (!h_band_fail_ || !*h_band_fail_) {

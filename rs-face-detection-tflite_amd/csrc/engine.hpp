@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "consts.hpp"
 #include "plan.hpp"
 
 namespace mi {
@@ -67,7 +68,10 @@ class Model {
     std::string describe() const { return plan_.describe(); }
 
    private:
-    void rebuild();                       // (re)lower + upload weights for the current options
+    void rebuild();                       // (re)lower, pack (consts.cpp) + upload weights for the current options
+    void schedule_side_streams();         // which nodes of plan_ run beside the trunk (head_slot_, head_wait_, event_after_)
+    struct Option;                        // one row of the option table (engine.cpp)
+    static const Option* find_option(const std::string& key);
     void build_bandnet();                 // the single-launch plan of the same graph, when its operators have band stages
     void build_bandnet_try(bool conv2_ok);
     void free_bandnet();
@@ -86,7 +90,14 @@ class Model {
     int device_ = 0;
     std::vector<uint8_t> blob_;
     Plan plan_;
-    int fuse_level_ = 5, res_budget_ = 156 * 1024, chunk_ = 0, use_graph_ = 1, reuse_ = 1, lanes_ = 1, pipe_max_ = 4, strip_ = 1, pipe_rows_ = 0, pipe_band_ = 0, fork_ = 1, head_streams_opt_ = 1, stem_fuse_ = 1, pair_fuse_ = 1, mdb_band_ = 0, stem_mfma_ = 1;
+    // options (what each means: the table in engine.cpp, find_option)
+    int fuse_level_ = 5, pipe_max_ = 4, tail_ = 1, reuse_ = 1;    // "fuse", "pipe", "tail", "reuse"
+    int res_budget_ = 156 * 1024;                                  // "res_budget", in bytes
+    int chunk_ = 0, lanes_ = 1, use_graph_ = 1;                    // "chunk", "lanes", "graph"
+    int fork_ = 1, head_streams_opt_ = 1;                          // "fork", "heads"
+    int strip_ = 1, stem_fuse_ = 1, stem_mfma_ = 1, pair_fuse_ = 1, mchain_ = 1;   // "strip", "stem_fuse", "stem_mfma", "pair_fuse", "mchain"
+    int pipe_rows_ = 0, pipe_band_ = 0, mdb_band_ = 0;             // "pipe_rows", "pipe_band", "mdb_band"
+    int tail_pre_ = 0, tail_g_ = 0;                                // "tail_pre", "tail_g"
     int arena_lane_ = 0;                    // arena region the chunk being enqueued writes to
     std::vector<hipStream_t> side_streams_;  // lanes 1.. run on their own streams (forked/joined with events)
     std::vector<hipEvent_t> lane_events_;
@@ -99,26 +110,11 @@ class Model {
     bool dirty_ = true;
 
     float* d_weights_ = nullptr;
-    std::vector<long> node_w_, node_b_, node_w2_, node_b2_, node_alpha_;  // float offsets into d_weights_ (-1 none)
-    std::vector<long> node_pair_;   // constants of the pair launch this Block node and the next one share (mdblock_pack_consts, pair form), -1: no such form
-    std::vector<long> node_stem_;   // the first convolution's constants for the launch it shares with the block pair behind it (mdblock_pack_stem), -1: no such form
-    std::vector<long> node_mwalk_;  // mwalk-kernel constants of a Block node (mwalk_pack_consts), -1 when the shape does not qualify
-    std::vector<long> node_strip_;  // strip-kernel constants of a Block node (strip_pack_consts), -1 when the shape does not qualify
-    struct MemberOff { long w = -1, b = -1, w2 = -1, b2 = -1, alpha = -1, strip = -1; };
+    PlanConsts consts_;      // float offsets into d_weights_ of every launch's constants (the host blob and programs are freed after the upload)
     int profile_inner_ = 1;  // executions of a launch between its two profiling marks (profile() only)
-    std::vector<std::vector<MemberOff>> chain_off_;  // per node: offsets of each chain member's constants
-    std::vector<std::vector<MemberOff>> chain_head_off_;  // per node, per head pair: stacked weights (w2) and bias (b2)
 
     ResStage* d_programs_ = nullptr;        // stage programs of the Resident nodes (device memory)
-    TailStage* d_tail_programs_ = nullptr;  // ... of those that run on tail_kernels.hip (Node::tail; node_prog_ indexes this array then)
-    std::vector<std::vector<long>> tail_wa_, tail_wc_;  // per tail node, per stage: A operands / small constants (-1: LOAD)
-    int mchain_ = 1;                        // option "mchain"
-    int tail_ = 1;                          // option "tail"
-    int tail_pre_ = 0;                      // option "tail_pre"
-    int tail_g_ = 0;                        // option "tail_g": frames per workgroup of the tail programs (0 = chosen per launch)
-    std::vector<std::vector<long>> res_wblk_;   // per Resident node, per stage: K-blocked weight packing (-1: classic order)
-    std::vector<std::vector<long>> res_cblob_;  // per Resident node, per stage: offset of its packed constants (-1: LOAD)
-    std::vector<long> node_prog_;           // per node: first stage in d_programs_ (-1 none)
+    TailStage* d_tail_programs_ = nullptr;  // ... of those that run on tail_kernels.hip (Node::tail; consts_.node_prog indexes this array then)
     float* d_arena_ = nullptr;
     size_t arena_floats_ = 0;
     int chunk_cap_ = 0;      // frames per chunk the arena is laid out for
@@ -135,7 +131,7 @@ class Model {
     bool band_ready_ = false;       // the graph has a single-launch form
     bool band_use_ = false;         // the run being enqueued takes it
     bool band_ran_ = false;         // the last run_device took it
-    bool band_test_fail_ = false;   // option "band_test_fail"
+    int band_test_fail_ = 0;        // option "band_test_fail"
     int band_test_absent_ = 0;      // option "band_test_absent"
     int test_poison_ = 0;           // option "test_poison": 0 off, 1 = 0xFF bytes (NaN), 2 = 0x7F bytes (3.39e38) in scratch and outputs before every run
     int band_fail_streak_ = 0;      // single launches in a row that gave up; at 3 the handle stops using the plan (band_ = 0)
@@ -152,7 +148,8 @@ class Model {
     struct BandExt { int out_k = -1, tensor = -1; };   // BandLaunch::base[2 + j]: graph output out_k, or the arena storage of `tensor` (read by a launch behind the band program)
     std::vector<BandExt> band_ext_;
     std::vector<char> band_node_runs_;   // per plan_ node from band_first_ on: 1 = it runs as its own launch behind the band launch (the program stops in front of it)
-    bool band_fork_ = true, band_cv2_ = false, band_xb_ = false, band_saw_conv2_ = false, band_wide_ = false, band_wide_ok_ = true;
+    int band_fork_ = 1, band_wide_ok_ = 1;   // options "band_fork", "band_wide"
+    bool band_cv2_ = false, band_xb_ = false, band_saw_conv2_ = false, band_wide_ = false;
     BandPacked* d_band_prog_ = nullptr;
     float* d_band_consts_ = nullptr;
     float* d_band_ws_ = nullptr;
