@@ -12,6 +12,13 @@ float act_slope(const Graph& g, const Node& m, int c) {
     return g.tensors.at(static_cast<size_t>(m.alpha)).f32.at(static_cast<size_t>(c));
 }
 
+const std::vector<float>& const_data(const Graph& g, int t, long need) {
+    if (t < 0 || static_cast<size_t>(t) >= g.tensors.size()) throw std::runtime_error("consts: a layer names a constant tensor that does not exist");
+    const std::vector<float>& v = g.tensors[static_cast<size_t>(t)].f32;
+    if (need < 0 || v.size() < static_cast<size_t>(need)) throw std::runtime_error("consts: a constant tensor is shorter than the layer that reads it");
+    return v;
+}
+
 namespace {
 // rows [O][I] -> MFMA A-fragment order [tile][k-chunk][lane][4] of a zero padded [Cop][Cp] matrix: lane l = (row m = l & 31,
 // k-half h = l >> 5) holds W[tile*32 + m][h*Cp/2 + 4*chunk + e].  kblk == 16: the K-blocked order of the LDS-staged pointwise stages
@@ -54,12 +61,7 @@ struct Packer {
     }
     const std::vector<int>& shape(int t) const { return g.tensors.at(static_cast<size_t>(t)).shape; }
     int dim(int t, size_t d) const { return shape(t).at(d); }
-    // constant tensor t, of which the caller reads the first `need` floats
-    const std::vector<float>& data(int t, long need = 0) const {
-        const std::vector<float>& v = g.tensors.at(static_cast<size_t>(t)).f32;
-        if (need < 0 || v.size() < static_cast<size_t>(need)) throw std::runtime_error("consts: a constant tensor is shorter than the layer that reads it");
-        return v;
-    }
+    const std::vector<float>& data(int t, long need = 0) const { return const_data(g, t, need); }
     const float* ptr(int t, long need) const { return t >= 0 ? data(t, need).data() : nullptr; }
     long put_tensor(int t) { return put(data(t)); }
     // `rows` rows of n floats of tensor t (when it exists) to dst + off, `stride` apart

@@ -40,6 +40,10 @@ struct PlanConsts {
 // plan.root_offset is final when this is called (the stage programs carry arena offsets)
 PlanConsts pack_plan_consts(const Plan& plan);
 
+// constant tensor t, of which the caller reads the first `need` floats: the only way the packers (consts.cpp, bandplan.cpp) read a constant.
+// A tensor that does not exist or is shorter than that (the model is untrusted) throws std::runtime_error
+const std::vector<float>& const_data(const Graph& g, int t, long need = 0);
+
 // negative-side slope of channel c behind m's activation: PReLU alpha, 1 without an activation, 0 for ReLU / ReLU6
 float act_slope(const Graph& g, const Node& m, int c);
 

@@ -241,728 +241,29 @@ void Model::free_bandnet() {
     if (d_band_sync_) hipFree(d_band_sync_);
     if (h_band_fail_) hipHostFree(h_band_fail_);
     d_band_prog_ = nullptr; d_band_consts_ = nullptr; d_band_ws_ = nullptr; d_band_sync_ = nullptr; h_band_fail_ = nullptr; d_band_fail_ = nullptr;
-    band_ready_ = false;
+    band_plan_ = BandPlan();
 }
 
-// The single-launch plan (bandnet_kernels.hip).  It is made from the level-2 lowering of the same graph — one node per BlazeBlock /
-// convolution — when that is: a first convolution (which keeps its launch of the batched plan), then nothing but 3x3 BlazeBlocks whose
-// skip is their own input (or, without a stride, another tensor of the program: the iris network's bottlenecks), pointwise blocks,
-// 1x1 convolutions and 2x2 stride-2 convolutions, each reading the tensor of an earlier one.  The program stops in front of the first node
-// that is none of these (the face mesh's and the iris network's two whole-frame convolutions): the plan nodes from there on keep their
-// launches of the batched plan, behind the band launch, and the tensors they read are written to their arena storage by the band
-// program — provided no launch of the batched plan straddles the cut.  Graphs whose FIRST block is already something else (full_range's
-// double blocks) leave band_ready_ false and the handle on the batched plan.
-// MI_BAND_DEBUG=1 names the line at which a graph was found to have no single-launch form
-#define BAND_GIVE_UP do { if (std::getenv("MI_BAND_DEBUG")) std::fprintf(stderr, "bandnet: no single-launch plan (engine.cpp:%d)\n", __LINE__); return; } while (0)
-// (round 5) 2x2 stride-2 convolutions and the blocks behind them, whose skip is the 2x2 max of the convolution's input,
-// are stages too: the whole iris network but its two whole-frame heads is one program (iris_landmark.rs:203).  Should a graph with such
-// nodes have no program with them, it is lowered once more with the program ending in front of the first of them (the earlier form).
+// The single-launch plan (bandnet_kernels.hip) of the same graph: planned on the host from the level-2 lowering (build_band_plan, bandplan.cpp);
+// here it is uploaded and given its workspace, its sync words and its fail word.  A graph without such a plan leaves the handle on the batched plan
 void Model::build_bandnet() {
-    band_saw_conv2_ = false;
-    build_bandnet_try(true);
-    if (!band_ready_ && band_saw_conv2_) build_bandnet_try(false);
-}
-
-void Model::build_bandnet_try(bool conv2_ok) {
     free_bandnet();
-    if (!band_ || fuse_level_ < 2) BAND_GIVE_UP;
-    const Plan p2 = build_plan(parse_tflite(blob_.data(), blob_.size()), 2);
-    const Graph& g = p2.graph;
-    auto is_view = [](const Node& n) { return n.kind == Node::Reshape || n.kind == Node::Concat; };
-    // the first launch of both plans must be the same convolution
-    size_t i5 = 0, i2 = 0;
-    while (i5 < plan_.nodes.size() && is_view(plan_.nodes[i5])) i5++;
-    while (i2 < p2.nodes.size() && is_view(p2.nodes[i2])) i2++;
-    if (i5 >= plan_.nodes.size() || i2 >= p2.nodes.size()) BAND_GIVE_UP;
-    const Node &stem5 = plan_.nodes[i5], &stem2 = p2.nodes[i2];
-    if (stem5.kind != Node::Conv || stem2.kind != Node::Conv || stem5.out != stem2.out || stem5.gemm_head) BAND_GIVE_UP;
-    band_stem_out_ = stem2.out;
-    if (plan_.storage[band_stem_out_].root != band_stem_out_ || plan_.storage[band_stem_out_].offset != 0) BAND_GIVE_UP;
-    band_first_ = static_cast<int>(i5) + 1;
-    while (band_first_ < static_cast<int>(plan_.nodes.size()) && is_view(plan_.nodes[static_cast<size_t>(band_first_)])) band_first_++;
-    if (band_first_ >= static_cast<int>(plan_.nodes.size())) BAND_GIVE_UP;
-    // workgroups per frame: one per row of the first tensor, at most band_nw_ (the bands of the later, smaller tensors are one row of every
-    // 2nd, 4th ... workgroup)
-    const auto& stem_shape = g.tensors[band_stem_out_].shape;
-    if (stem_shape.size() != 4) BAND_GIVE_UP;
-    int NW = band_nw_;
-    while (NW > 1 && (stem_shape[1] % NW) && (NW % stem_shape[1])) NW--;
-    if (stem_shape[1] < NW) NW = stem_shape[1];
-    band_nw_used_ = NW;
-    band_max_frames_ = std::max(0, device_cu_count() / NW);
-    if (band_max_frames_ < 1) BAND_GIVE_UP;
-
-    std::vector<BandStage> prog;
-    std::vector<const Node*> nodes;
-    std::vector<float> consts;
-    std::vector<int> producer(g.tensors.size(), -1);
-    std::vector<int> out_root;
-    for (int o : g.outputs) out_root.push_back(p2.storage[o].root);
-    band_ext_.clear();
-    auto ext_slot = [&](int out_k, int tensor) {   // BandLaunch::base index of a graph output / an arena tensor (-1: no slot left)
-        for (size_t j = 0; j < band_ext_.size(); j++)
-            if (band_ext_[j].out_k == out_k && band_ext_[j].tensor == tensor) return 2 + static_cast<int>(j);
-        if (2 + band_ext_.size() >= static_cast<size_t>(kBandBases)) return -1;
-        BandExt e; e.out_k = out_k; e.tensor = tensor;
-        band_ext_.push_back(e);
-        return 1 + static_cast<int>(band_ext_.size());
-    };
-    std::vector<char> band_op(g.ops.size(), 0);   // .tflite operators the band program computes
-    size_t cut = p2.nodes.size();                 // first p2 node the program does not take
-    auto put = [&](const std::vector<float>& v) {
-        const long off = align_up(static_cast<long>(consts.size()), 64);
-        consts.resize(static_cast<size_t>(off) + v.size(), 0.f);
-        std::copy(v.begin(), v.end(), consts.begin() + off);
-        return off;
-    };
-    // ---- pass 1: one stage per node, its shape, bands, source and constants
-    for (size_t i = i2 + 1; i < p2.nodes.size(); i++) {
-        const Node& n = p2.nodes[i];
-        if (is_view(n)) continue;
-        const bool pw_block = n.kind == Node::Block && n.w < 0;
-        const bool dw_block = n.kind == Node::Block && n.w >= 0;
-        const bool conv1 = n.kind == Node::Conv && n.KH == 1 && n.KW == 1 && n.sh == 1 && n.sw == 1 && !n.gemm_head;
-        const bool conv2 = conv2_ok && n.kind == Node::Conv && n.KH == 2 && n.KW == 2 && n.sh == 2 && n.sw == 2 && !n.gemm_head && n.in.size() == 1 &&
-                           g.tensors[n.in[0]].shape.size() == 4 && g.tensors[n.in[0]].shape[1] % 2 == 0 && g.tensors[n.in[0]].shape[2] % 2 == 0 &&
-                           g.tensors[n.in[0]].shape[3] % 32 == 0 && n.in[0] != band_stem_out_;
-        if (std::getenv("MI_BAND_DEBUG"))
-            std::fprintf(stderr, "bandnet: node %zu kind %d K %dx%d s %d in %zu res %d mode %d after %d ept %d act %d gemm %d\n", i, static_cast<int>(n.kind), n.KH, n.KW, n.sh, n.in.size(), n.res, n.res_mode,
-                         n.res_after ? 1 : 0, n.ept, n.act, n.gemm_head ? 1 : 0);
-        if (!pw_block && !dw_block && !conv1 && !conv2) { cut = i; break; }
-        if (conv2) band_saw_conv2_ = true;
-        // full_range's lateral convolutions — a 1x1 convolution with a fused activation, then ADD with the bilinearly up-sampled coarser map: the skip
-        // joins BEHIND the activation — are stages of the WIDE instantiation when the coarse tensor is the program's (round 6); any other such node ends the program
-        const bool up2x = (conv1 || pw_block) && n.res_after && n.res >= 0 && n.res_mode == RES_UP2X && band_wide_ok_ && n.in.size() == 1 && n.ept < 0 &&
-                          producer[static_cast<size_t>(n.res)] >= 0 && g.tensors[n.res].shape.size() == 4;
-        // (full_range_sparse pads its stride-2 blocks explicitly, one pixel in front: the same stage with its window one row / column earlier — round 6)
-        const bool pre = dw_block && n.ept == 1 && n.epl == 1 && n.sh == 2 && n.sw == 2 && n.padding == Padding::Valid && n.res < 0 && band_wide_ok_;
-        if (n.in.size() != 1 || (n.ept >= 0 && !pre) || (n.res_after && !up2x)) {
-            if (prog.empty()) BAND_GIVE_UP;
-            cut = i;
-            break;
-        }
-        const auto& si = g.tensors[n.in[0]].shape;
-        const auto& so = g.tensors[n.out].shape;
-        if (si.size() != 4 || so.size() != 4) BAND_GIVE_UP;
-        BandStage st;
-        st.kind = dw_block ? BAND_BLOCK : BAND_PW;
-        st.H = si[1]; st.W = si[2]; st.C = si[3]; st.Ho = so[1]; st.Wo = so[2]; st.Co = so[3];
-        const bool wide_ok = band_wide_ok_ && !conv2 && st.C <= 384 && st.Co <= 384 && (st.C <= 128 || st.C % 16 == 0) && (st.Co <= 128 || st.Co % 16 == 0);   // (the WIDE instantiation: round 6)
-        if (st.C % 4 || st.C < 8 || st.Co < 1 || ((st.C > 128 || st.Co > 128) && !wide_ok)) {
-            // channel counts the kernel does not take (a wave keeps ONE 16-channel output tile and at most eight 16-value chunks of A operands): the
-            // program ends in front of this node when it has stages already (full_range: the trunk down to 12x12x36; round 6), else there is none
-            if (prog.empty()) BAND_GIVE_UP;
-            cut = i;
-            break;
-        }
-        st.S = 1;
-        if (dw_block) {
-            if (n.KH != 3 || n.KW != 3 || n.sh != n.sw || (n.sh != 1 && n.sh != 2) || (n.padding != Padding::Same && !pre)) BAND_GIVE_UP;
-            st.S = n.sh;
-            st.pre = pre ? 1 : 0;
-            if (st.S == 2 && ((st.H & 1) || (st.W & 1))) BAND_GIVE_UP;
-            if (st.Ho != st.H / st.S || st.Wo != st.W / st.S) BAND_GIVE_UP;
-        } else if (conv2) {
-            st.S = 2;   // (even sizes: SAME and VALID are the same window)
-            if (st.Ho != st.H / 2 || st.Wo != st.W / 2 || n.res >= 0) BAND_GIVE_UP;
-        } else if (st.Ho != st.H || st.Wo != st.W) {
-            BAND_GIVE_UP;
-        }
-        st.act = n.act;
-        if (n.act != ACT_NONE && n.act != ACT_RELU && n.act != ACT_RELU6 && n.act != ACT_PRELU) BAND_GIVE_UP;
-        st.res_mode = RES_NONE;
-        if (up2x) {
-            const auto& sr = g.tensors[n.res].shape;
-            const BandStage& cd = prog[static_cast<size_t>(producer[static_cast<size_t>(n.res)])];
-            if (sr[1] * 2 != st.Ho || sr[2] * 2 != st.Wo || sr[3] != st.Co || (st.Co & 3) || cd.R != 1 || (st.Wo / 2) * (st.Co / 4) > 512) { if (prog.empty()) BAND_GIVE_UP; cut = i; break; }
-            st.res_mode = RES_UP2X;
-            st.res_dep = producer[static_cast<size_t>(n.res)];   // (its rows come through the packets, not from a tile: pass 2)
-            st.res_c = st.Co;
-        } else if (n.res >= 0) {
-            if (!dw_block) BAND_GIVE_UP;
-            if (n.res != n.in[0] && n.res_mode == RES_MAXPOOL) {
-                // the skip is the 2x2 max of the tensor the 2x2 convolution in front of this block read: the rows 2r, 2r + 1 of it that the
-                // owner of output row r needs are in the LDS tile that convolution read them from
-                const auto& sr = g.tensors[n.res].shape;
-                const int d = producer[static_cast<size_t>(n.in[0])];
-                // (round 6: ... or the stride-2 BLOCK in front — full_range's down-sampling pairs: DW s2 + PW reduce, then DW + PW expand + 2x2 max of the
-                // pair's input, zero-padded from its res_c channels to Co)
-                if (st.S != 1 || sr.size() != 4 || sr[1] != 2 * st.Ho || sr[2] != 2 * st.Wo || sr[3] > st.Co || (sr[3] & 3) || d < 0) BAND_GIVE_UP;
-                const BandStage& cv = prog[static_cast<size_t>(d)];
-                if (cv.S != 2 || cv.pre || cv.dep < 0 || cv.dep != producer[static_cast<size_t>(n.res)]) BAND_GIVE_UP;
-                st.res_dep = cv.dep;
-                st.res_mode = RES_MAXPOOL;
-                st.res_c = sr[3];
-            }
-            else if (n.res != n.in[0]) {
-                // the skip is another tensor of the program, with the output's shape (its rows then have the output's owners)
-                const auto& sr = g.tensors[n.res].shape;
-                if (n.res_mode != RES_DIRECT || st.S != 1 || sr.size() != 4 || sr[1] != st.Ho || sr[2] != st.Wo || sr[3] > st.Co || (sr[3] & 3)) BAND_GIVE_UP;   // (fewer channels than Co: zero-padded)
-                st.res_c = sr[3];
-                if (n.res == band_stem_out_) st.res_dep = -1;
-                else if (producer[static_cast<size_t>(n.res)] >= 0) st.res_dep = producer[static_cast<size_t>(n.res)];
-                else BAND_GIVE_UP;
-                st.res_mode = RES_DIRECT;
-            }
-            else if (n.res_mode == RES_DIRECT && st.S == 1 && st.Co >= st.C) st.res_mode = RES_DIRECT;   // (Co > C: the skip is zero-padded to Co channels)
-            else if (n.res_mode == RES_MAXPOOL && st.S == 2 && st.Co >= st.C) st.res_mode = RES_MAXPOOL;
-            else BAND_GIVE_UP;
-        }
-        // bands: whole rows per workgroup while there are at least NW rows, one row for every (NW / rows)-th workgroup below that
-        auto log2_exact = [](int v) { int k = 0; while ((1 << k) < v) k++; return (1 << k) == v ? k : -1; };
-        if (st.Ho >= NW) {
-            if (st.Ho % NW) BAND_GIVE_UP;
-            st.R = st.Ho / NW; st.wshift = 0; st.nbands = NW;
-        } else {
-            if (NW % st.Ho || log2_exact(NW / st.Ho) < 0) BAND_GIVE_UP;
-            st.R = 1; st.wshift = log2_exact(NW / st.Ho); st.nbands = st.Ho;
-        }
-        if (n.in[0] == band_stem_out_) {
-            st.src_base = 1; st.src_off = 0; st.dep = -1; st.Rin = 0;
-            st.src_fs = plan_.storage[band_stem_out_].frame_stride;
-            if (st.src_fs & 3) BAND_GIVE_UP;
-        } else {
-            const int d = producer[static_cast<size_t>(n.in[0])];
-            if (d < 0) BAND_GIVE_UP;
-            const BandStage& pd = prog[static_cast<size_t>(d)];
-            st.dep = d;
-            st.Rin = pd.R;
-            // the owner of output row r must own input row S r, and the rows it lacks must be at most one above and two below its own
-            for (int b = 0; b < st.nbands; b++) {
-                const int r0 = b * st.R, nro = std::min(st.Ho, r0 + st.R) - r0, p0 = st.S * r0;
-                if (((p0 / pd.R) << pd.wshift) != (b << st.wshift) || p0 % pd.R) BAND_GIVE_UP;
-                const int rin = std::min(pd.R, st.H - p0);
-                const int yb = dw_block ? (st.S == 1 ? p0 + nro + 1 : p0 + 2 * nro + 1 - st.pre) : (conv2 ? p0 + 2 * nro : p0 + nro);
-                const int below = yb - (p0 + rin);
-                if (below < 0 || below > 2) BAND_GIVE_UP;
-                if (((dw_block && (st.S == 1 || st.pre) ? 1 : 0) + below) * st.W * (st.C / 4) > 4 * 512) BAND_GIVE_UP;   // the halo rows: four 16-byte elements per lane
-            }
-        }
-        // a plain copy of the output where it is a graph output (through the reshape / concatenation views behind it)
-        const Storage& so_st = p2.storage[n.out];
-        for (size_t k = 0; k < out_root.size(); k++)
-            if (out_root[k] == so_st.root) {
-                st.dst_base = ext_slot(static_cast<int>(k), -1); st.dst_off = so_st.offset; st.dst_fs = so_st.frame_stride;
-                if (st.dst_base < 0) BAND_GIVE_UP;
-            }
-        if (st.dst_base < 0 && so_st.root != n.out) BAND_GIVE_UP;
-        if (st.dst_base < 0 && st.Co % 4) BAND_GIVE_UP;
-        if ((st.dst_off & 3) || (st.dst_fs & 3)) {
-            if (st.Co % 4 == 0) BAND_GIVE_UP;   // 16-byte stores need the alignment; the ragged heads store floats
-        }
-        // constants
-        const int wt = n.kind == Node::Conv ? n.w : n.w2, bt = n.kind == Node::Conv ? n.b : n.b2;
-        const auto& wsrc = g.tensors[wt].f32;
-        const int C = conv2 ? 4 * st.C : st.C;   // (the contraction length: [Co][2][2][C] read as [Co][4 C])
-        const int Co = st.Co, nct = (Co + 15) / 16, n16 = C / 16, has8 = (C / 8) & 1, has4 = (C / 4) & 1, per_ct = n16 * 256 + has8 * 128 + has4 * 64;
-        if (wsrc.size() != static_cast<size_t>(Co) * C) BAND_GIVE_UP;
-        std::vector<float> A(static_cast<size_t>(nct) * per_ct, 0.f);
-        for (int ct = 0; ct < nct; ct++)
-            for (int l = 0; l < 64; l++) {
-                const int o = 16 * ct + (l & 15), kq = l >> 4;
-                if (o >= Co) continue;
-                for (int j = 0; j < n16; j++)
-                    for (int e = 0; e < 4; e++) A[static_cast<size_t>(ct) * per_ct + (j * 64 + l) * 4 + e] = wsrc[static_cast<size_t>(o) * C + 16 * j + 4 * kq + e];
-                if (has8)
-                    for (int e = 0; e < 2; e++) A[static_cast<size_t>(ct) * per_ct + n16 * 256 + l * 2 + e] = wsrc[static_cast<size_t>(o) * C + 16 * n16 + 2 * kq + e];
-                if (has4) A[static_cast<size_t>(ct) * per_ct + n16 * 256 + has8 * 128 + l] = wsrc[static_cast<size_t>(o) * C + 16 * n16 + 8 * has8 + kq];
-            }
-        st.c_floats = bandnet_const_floats(st);   // (what the kernel stages in LDS: without the depthwise taps where they do not fit — a wide stage reads them from L2)
-        st.per_ct = per_ct;
-        if (nct > 24 || (nct > 8 && !wide_ok)) BAND_GIVE_UP;
-        st.wpc_shift = nct == 1 ? 3 : (nct == 2 ? 2 : (nct <= 4 ? 1 : 0));
-        std::vector<float> cb(static_cast<size_t>(32 * nct + (dw_block ? 10 * C : 0)), 0.f);
-        for (int c = 0; c < Co; c++) {
-            cb[static_cast<size_t>(c)] = bt >= 0 ? g.tensors[bt].f32[static_cast<size_t>(c)] : 0.f;
-            cb[static_cast<size_t>(16 * nct + c)] = act_slope(g, n, c);
-        }
-        if (dw_block) {
-            const auto& wd = g.tensors[n.w].f32;  // [1][3][3][C]
-            if (wd.size() != static_cast<size_t>(9) * C) BAND_GIVE_UP;
-            for (int t = 0; t < 9 * C; t++) cb[static_cast<size_t>(32 * nct + t)] = wd[static_cast<size_t>(t)];
-            if (n.b >= 0)
-                for (int c = 0; c < C; c++) cb[static_cast<size_t>(32 * nct + 9 * C + c)] = g.tensors[n.b].f32[static_cast<size_t>(c)];
-        }
-        st.w_a = put(A);
-        st.w_c = put(cb);
-        auto magic = [](int d) { return d <= 1 ? 0u : static_cast<unsigned>((0x100000000ull + static_cast<unsigned long long>(d) - 1) / static_cast<unsigned long long>(d)); };
-        st.mC4 = magic(st.C / 4); st.mWo = magic(st.Wo); st.mrowq = magic(st.W * (st.C / 4));
-        if (static_cast<long>(st.R + 3) * st.W * (st.C / 4) >= 65536 || st.R * st.Wo * std::max(st.C, st.Co) / 4 >= 65536) BAND_GIVE_UP;   // the magic divisions' range
-        producer[static_cast<size_t>(n.out)] = static_cast<int>(prog.size());
-        prog.push_back(st);
-        nodes.push_back(&n);
-        for (int o : n.src_ops) band_op[static_cast<size_t>(o)] = 1;
-    }
-    if (prog.empty() || prog.size() > 63) BAND_GIVE_UP;
-    // ---- the cut: a plan node behind the first convolution either lies wholly inside the band program (the band launch stands for it) or wholly
-    // behind it (it keeps its launch); a tensor such a launch reads from the program is written to its arena storage by the producing stage
-    band_node_runs_.assign(plan_.nodes.size(), 0);
-    if (g.ops.size() != plan_.graph.ops.size() || g.tensors.size() > plan_.storage.size()) BAND_GIVE_UP;
-    {
-        std::vector<int> op_producer(g.tensors.size(), -1);
-        for (size_t o = 0; o < g.ops.size(); o++)
-            for (int t : g.ops[o].outputs)
-                if (t >= 0) op_producer[static_cast<size_t>(t)] = static_cast<int>(o);
-        std::function<void(const Node&, std::vector<int>&)> reads = [&](const Node& n, std::vector<int>& v) {
-            for (int t : n.in) v.push_back(t);
-            if (n.res >= 0) v.push_back(n.res);
-            for (const Node& m : n.members) reads(m, v);
-            for (const Node& m : n.head_nodes) reads(m, v);
-            for (const Node::Stage& sg : n.stages) { if (sg.src_t >= 0) v.push_back(sg.src_t); if (sg.res_t >= 0) v.push_back(sg.res_t); }
-        };
-        bool any_band = false;
-        for (size_t i = static_cast<size_t>(band_first_); i < plan_.nodes.size(); i++) {
-            const Node& n = plan_.nodes[i];
-            if (is_view(n)) continue;
-            size_t inside = 0;
-            for (int o : n.src_ops) inside += band_op[static_cast<size_t>(o)] ? 1 : 0;
-            if (n.src_ops.empty() || (inside != 0 && inside != n.src_ops.size())) BAND_GIVE_UP;   // a launch of the batched plan straddles the cut
-            if (inside) { any_band = true; continue; }
-            band_node_runs_[i] = 1;
-            std::vector<int> rd;
-            reads(n, rd);
-            for (int t : rd) {
-                const int o = op_producer[static_cast<size_t>(t)];
-                if (o < 0 || !band_op[static_cast<size_t>(o)]) continue;   // a constant, the graph input, or a tensor of another launch behind the cut
-                const int d = producer[static_cast<size_t>(t)];
-                if (d < 0) BAND_GIVE_UP;   // a tensor inside one of the program's blocks
-                const Storage& sp = plan_.storage[static_cast<size_t>(t)];
-                if (sp.root < 0 || (sp.offset & 3) || (sp.frame_stride & 3)) BAND_GIVE_UP;
-                bool is_out = false;
-                for (int go : g.outputs) is_out = is_out || plan_.storage[static_cast<size_t>(go)].root == sp.root;
-                if (is_out) { if (prog[static_cast<size_t>(d)].dst_base < 0) BAND_GIVE_UP; continue; }   // (already written where the launch reads it)
-                if (plan_.root_offset[static_cast<size_t>(sp.root)] < 0 || (plan_.root_offset[static_cast<size_t>(sp.root)] & 3)) BAND_GIVE_UP;
-                BandStage& pd = prog[static_cast<size_t>(d)];
-                if (pd.dst_base >= 2 && band_ext_[static_cast<size_t>(pd.dst_base - 2)].tensor == t) continue;   // (a second reader of the same tensor)
-                if (pd.dst_base >= 0 || (pd.Co & 3)) BAND_GIVE_UP;
-                pd.dst_base = ext_slot(-1, t); pd.dst_off = 0; pd.dst_fs = sp.frame_stride;
-                if (pd.dst_base < 0) BAND_GIVE_UP;
-            }
-        }
-        if (!any_band || band_node_runs_[static_cast<size_t>(band_first_)]) BAND_GIVE_UP;
-        // the band launch writes its tensors EARLIER than the batched plan's launches would have: a launch that keeps its place in front of the
-        // last node the program stands for may only write graph outputs (an arena slot it writes might be one the program's tensors live in)
-        size_t last_inside = 0;
-        for (size_t i = static_cast<size_t>(band_first_); i < plan_.nodes.size(); i++)
-            if (!is_view(plan_.nodes[i]) && !band_node_runs_[i]) last_inside = i;
-        for (size_t i = static_cast<size_t>(band_first_); i < last_inside; i++) {
-            if (!band_node_runs_[i]) continue;
-            std::vector<int> outs = plan_.nodes[i].extra_out;
-            outs.push_back(plan_.nodes[i].out);
-            for (int t : outs) {
-                bool is_out = false;
-                for (int go : g.outputs) is_out = is_out || plan_.storage[static_cast<size_t>(go)].root == plan_.storage[static_cast<size_t>(t)].root;
-                if (!is_out) BAND_GIVE_UP;
-            }
-        }
-        // the nodes in front of the cut in the level-2 lowering must be exactly the program (nothing the batched plan computes is skipped)
-        for (size_t i = cut; i < p2.nodes.size(); i++)
-            for (int o : p2.nodes[i].src_ops)
-                if (band_op[static_cast<size_t>(o)]) BAND_GIVE_UP;
-    }
-    // every graph output must be written, whole, by the band program or by a launch behind it (the first convolution writes none of them)
-    for (size_t k = 0; k < out_root.size(); k++) {
-        size_t written = 0;
-        for (const BandStage& st : prog)
-            if (st.dst_base >= 2 && band_ext_[static_cast<size_t>(st.dst_base - 2)].out_k == static_cast<int>(k)) written += static_cast<size_t>(st.Ho) * st.Wo * st.Co;
-        bool later = false;
-        for (size_t i = static_cast<size_t>(band_first_); i < plan_.nodes.size(); i++)
-            if (band_node_runs_[i] && plan_.storage[static_cast<size_t>(plan_.nodes[i].out)].root == out_root[k]) later = true;
-        if (!later && written != g.tensors[g.outputs[k]].elems()) BAND_GIVE_UP;
-    }
-    // ---- a program with 2x2 convolutions (the iris network: two branches of 21 stages behind its 8x8 fork) runs branch by branch, not in the
-    // graph's interleaved order: a stage goes behind the newest tensor it can read, so that one branch's skip / middle / output tensors and the
-    // fork tensor the other branch still waits for are all that is alive — four LDS tiles
-    {
-        const int N0 = static_cast<int>(prog.size());
-        bool any_cv2 = false;
-        for (const BandStage& st : prog) any_cv2 = any_cv2 || (st.kind == BAND_PW && st.S == 2);
-        if (any_cv2) {
-            std::vector<int> pos(static_cast<size_t>(N0), -1), order;
-            for (int step = 0; step < N0; step++) {
-                int best = -1, best_pos = -2;
-                for (int k = 0; k < N0; k++) {
-                    const BandStage& st = prog[static_cast<size_t>(k)];
-                    if (pos[static_cast<size_t>(k)] >= 0) continue;
-                    if (st.dep >= 0 && pos[static_cast<size_t>(st.dep)] < 0) continue;
-                    if (st.res_dep >= 0 && pos[static_cast<size_t>(st.res_dep)] < 0) continue;
-                    const int dp = st.dep >= 0 ? pos[static_cast<size_t>(st.dep)] : -1;
-                    if (dp > best_pos) { best = k; best_pos = dp; }
-                }
-                if (best < 0) BAND_GIVE_UP;
-                pos[static_cast<size_t>(best)] = step;
-                order.push_back(best);
-            }
-            std::vector<BandStage> re;
-            for (int k = 0; k < N0; k++) {
-                BandStage st = prog[static_cast<size_t>(order[static_cast<size_t>(k)])];
-                if (st.dep >= 0) st.dep = pos[static_cast<size_t>(st.dep)];
-                if (st.res_dep >= 0) st.res_dep = pos[static_cast<size_t>(st.res_dep)];
-                re.push_back(st);
-            }
-            prog.swap(re);
-            for (int& pr : producer)
-                if (pr >= 0) pr = pos[static_cast<size_t>(pr)];
-        }
-        // ... and (any program: the face mesh's two branches behind its 6x6 tensor as well) the second branch behind a fork goes to the workgroups
-        // the first one leaves idle (BandStage::woff): where a tensor of one-row bands on every 2nd / 4th ... workgroup is the input of two stages, the
-        // later one and everything behind it are run by the workgroups half a group further on, at the same time as the first branch; its first
-        // stage takes its whole input from the packet buffer
-        {
-            if (band_fork_) {
-                for (int k = 0; k < N0; k++) {
-                    const BandStage& fk = prog[static_cast<size_t>(k)];
-                    std::vector<int> readers;
-                    for (int j = 0; j < N0; j++)
-                        if (prog[static_cast<size_t>(j)].dep == k) readers.push_back(j);
-                    if (readers.size() != 2 || fk.R != 1 || fk.wshift < 1 || fk.woff != 0) continue;
-                    bool leaf = false;   // (a reader nobody reads is an output head: those have their own rule below)
-                    for (int r : readers) {
-                        bool is_read = false;
-                        for (int j = 0; j < N0; j++) is_read = is_read || prog[static_cast<size_t>(j)].dep == r || prog[static_cast<size_t>(j)].res_dep == r;
-                        leaf = leaf || !is_read;
-                    }
-                    if (leaf) continue;
-                    const int woff = 1 << (fk.wshift - 1);
-                    std::vector<char> inB(static_cast<size_t>(N0), 0);
-                    inB[static_cast<size_t>(readers[1])] = 1;
-                    for (int j = readers[1] + 1; j < N0; j++)
-                        if (prog[static_cast<size_t>(j)].dep >= 0 && inB[static_cast<size_t>(prog[static_cast<size_t>(j)].dep)]) inB[static_cast<size_t>(j)] = 1;
-                    bool ok = true;
-                    for (int j = 0; j < N0 && ok; j++) {
-                        const BandStage& st = prog[static_cast<size_t>(j)];
-                        if (inB[static_cast<size_t>(j)]) {
-                            ok = st.wshift >= fk.wshift && st.woff == 0 && (st.res_dep < 0 || st.res_dep == k || inB[static_cast<size_t>(st.res_dep)]);
-                        } else if (st.res_dep >= 0 && inB[static_cast<size_t>(st.res_dep)]) {
-                            ok = false;
-                        }
-                    }
-                    const BandStage& root = prog[static_cast<size_t>(readers[1])];
-                    const int rows = root.kind == BAND_BLOCK ? (root.S == 1 ? root.R + 2 : 2 * root.R + 1) : (root.S == 2 ? 2 * root.R : root.R);
-                    if (!ok || rows * root.W * (root.C / 4) > 4 * 512) continue;
-                    for (int j = 0; j < N0; j++)
-                        if (inB[static_cast<size_t>(j)]) prog[static_cast<size_t>(j)].woff = woff;
-                    prog[static_cast<size_t>(readers[1])].Rin = 0;
-                    prog[static_cast<size_t>(readers[1])].cross = 1;
-                }
-            }
-        }
-    }
-    // ---- the output heads (1x1 stages nobody reads: the SSD heads of the detectors) of a tensor of one-row bands go to workgroups the trunk
-    // leaves idle there (BandStage::woff, as the iris network's second branch): they take their input rows from the packet buffer and run beside
-    // the trunk's next stages instead of in front of them; the two heads of one tensor on two different sets of idle workgroups where there are two
-    if (band_fork_) {
-        const int N0 = static_cast<int>(prog.size());
-        std::vector<char> read(static_cast<size_t>(N0), 0);
-        for (const BandStage& st : prog) {
-            if (st.dep >= 0) read[static_cast<size_t>(st.dep)] = 1;
-            if (st.res_dep >= 0) read[static_cast<size_t>(st.res_dep)] = 1;
-        }
-        std::vector<int> moved(static_cast<size_t>(N0), 0);   // heads of a tensor already moved
-        for (int k = 0; k < N0; k++) {
-            BandStage& st = prog[static_cast<size_t>(k)];
-            if (read[static_cast<size_t>(k)] || st.kind != BAND_PW || st.S != 1 || st.dep < 0 || st.woff != 0 || st.cross || st.res_mode != RES_NONE) continue;
-            const BandStage& pd = prog[static_cast<size_t>(st.dep)];
-            if (pd.R != 1 || pd.wshift < 1 || pd.woff != 0 || st.R != 1 || st.wshift != pd.wshift || st.nbands != pd.nbands) continue;
-            if (st.W * (st.C / 4) > 4 * 512) continue;   // its one input row: four 16-byte elements per lane
-            const int j = moved[static_cast<size_t>(st.dep)]++;
-            int woff = 1 << (pd.wshift - 1);
-            if ((j & 1) && pd.wshift >= 2) woff += 1 << (pd.wshift - 2);
-            st.woff = woff;
-            st.Rin = 0;
-            st.cross = 1;
-        }
-    }
-    // ---- the output heads (stages nobody reads) move up behind the first other reader of their input: the two LDS tiles hold a tensor
-    // only until the trunk has moved on twice, and a head costs its workgroups two microseconds wherever it stands
-    {
-        const int N0 = static_cast<int>(prog.size());
-        std::vector<char> read(static_cast<size_t>(N0), 0), placed(static_cast<size_t>(N0), 0);
-        for (const BandStage& st : prog) {
-            if (st.dep >= 0) read[static_cast<size_t>(st.dep)] = 1;
-            if (st.res_dep >= 0) read[static_cast<size_t>(st.res_dep)] = 1;
-        }
-        std::vector<int> order;
-        for (int k = 0; k < N0; k++) {
-            if (placed[static_cast<size_t>(k)]) continue;
-            const bool head = !read[static_cast<size_t>(k)] && prog[static_cast<size_t>(k)].kind == BAND_PW;
-            if (head) continue;   // placed behind a sibling, or at the end
-            order.push_back(k);
-            placed[static_cast<size_t>(k)] = 1;
-            for (int j = 0; j < N0; j++)
-                if (!placed[static_cast<size_t>(j)] && !read[static_cast<size_t>(j)] && prog[static_cast<size_t>(j)].kind == BAND_PW &&
-                    prog[static_cast<size_t>(j)].dep == prog[static_cast<size_t>(k)].dep && prog[static_cast<size_t>(j)].dep >= 0) {
-                    order.push_back(j);
-                    placed[static_cast<size_t>(j)] = 1;
-                }
-        }
-        for (int k = 0; k < N0; k++)
-            if (!placed[static_cast<size_t>(k)]) order.push_back(k);
-        std::vector<int> new_index(static_cast<size_t>(N0), -1);
-        for (int k = 0; k < N0; k++) new_index[static_cast<size_t>(order[static_cast<size_t>(k)])] = k;
-        std::vector<BandStage> re;
-        for (int k = 0; k < N0; k++) {
-            BandStage st = prog[static_cast<size_t>(order[static_cast<size_t>(k)])];
-            if (st.dep >= 0) {
-                st.dep = new_index[static_cast<size_t>(st.dep)];
-                if (st.dep >= k) BAND_GIVE_UP;   // (cannot happen: a head only moves down to behind a reader of its own input)
-            }
-            if (st.res_dep >= 0) {
-                st.res_dep = new_index[static_cast<size_t>(st.res_dep)];
-                if (st.res_dep >= k) BAND_GIVE_UP;
-            }
-            re.push_back(st);
-        }
-        prog.swap(re);
-    }
-    // ---- pass 2: who reads what -> LDS tiles (placed by liveness; a straight chain uses two in turn), packet buffers for the rows other
-    // workgroups read
-    const int NS = static_cast<int>(prog.size());
-    std::vector<int> last_reader(static_cast<size_t>(NS), -1);
-    int input_last_reader = -1;   // ... of the program's input
-    for (int k = 0; k < NS; k++) {
-        const BandStage& st = prog[static_cast<size_t>(k)];
-        if (st.dep >= 0) {
-            BandStage& pd = prog[static_cast<size_t>(st.dep)];
-            // a lateral convolution reads a trunk tensor that is 10 - 30 stages old: its rows are this workgroup's own, so the producer also writes them to
-            // the launch's workspace and this stage reads them back from there (like the program's input) — the tile does not have to stay alive
-            BandStage& me = prog[static_cast<size_t>(k)];
-            if (st.res_mode == RES_UP2X && st.kind == BAND_PW && st.S == 1 && !st.cross && k - st.dep > 2 && pd.R == st.R && pd.wshift == st.wshift && pd.woff == st.woff &&
-                pd.nbands == st.nbands && (pd.dst_base < 0 || pd.far_copy) && (pd.Co & 3) == 0) {
-                me.far_src = 1;
-                pd.far_copy = 1;
-                pd.dst_base = 0;
-            } else {
-            last_reader[static_cast<size_t>(st.dep)] = k;
-            const bool cv2_halo = st.kind == BAND_PW && st.S == 2 && pd.R < 2 * st.R;   // its row 2r + 1 is the next workgroup's
-            if (st.cross) pd.pub_lo = 1;   // (one-row bands: all of the tensor)
-            if ((st.kind == BAND_BLOCK || cv2_halo) && pd.nbands > 1) {
-                pd.pub_lo = 1;
-                if (st.kind == BAND_BLOCK && (st.S == 1 || st.pre) && pd.R > 1) pd.pub_hi = 1;
-            }
-            }
-        } else {
-            input_last_reader = k;
-        }
-        if (st.res_dep >= 0) last_reader[static_cast<size_t>(st.res_dep)] = k;
-        if (st.res_dep == -1) input_last_reader = k;
-        if (st.res_mode == RES_UP2X) {
-            if (st.res_dep < 0) BAND_GIVE_UP;
-            prog[static_cast<size_t>(st.res_dep)].pub_lo = 1;   // (one-row bands: all of the coarse tensor travels)
-        }
-    }
-    long ws = 0;
-    int dw_floats = 0;
-    // LDS tiles, placed by liveness (round 6: an interval allocator — before, up to four equal tiles; full_range's tensors go from 56 KB for a band of
-    // 96x96x32 to 14 KB for one of 96x96x8, and its decoder keeps three 31 KB tensors of 48x48x48 alive): a tensor gets the lowest gap that holds it
-    // when it is produced and keeps it until its last reader has run.  Rows of a tile: the band's own + one above + one below, + one more below where a
-    // stride-2 BLOCK reads the tensor.
-    std::vector<char> read_s2(static_cast<size_t>(NS), 0);
-    for (const BandStage& st : prog)
-        if (st.kind == BAND_BLOCK && st.S == 2 && !st.pre && st.dep >= 0) read_s2[static_cast<size_t>(st.dep)] = 1;
-    struct Alloc { int off, size, stage; };   // stage: producer (-1: the program's input, -3: a far input held for one stage)
-    auto dead_at = [&](const Alloc& al, int k) { return al.stage == -3 || (al.stage == -1 ? input_last_reader <= k : last_reader[static_cast<size_t>(al.stage)] <= k); };
-    // The places are found first, for the smallest arena that takes them: a tensor goes to the lowest or to the highest gap that holds it, whichever leaves
-    // the larger free block (first fit from the bottom alone puts full_range's second 96x96x32 tensor in the middle of the arena, and the third, 56 KB,
-    // behind it: 155 KB for 113 KB of live tensors)
-    std::vector<int> in_off(static_cast<size_t>(NS), -1), out_off(static_cast<size_t>(NS), -1);
-    auto layout = [&](int S, int policy) {
-        std::vector<Alloc> lv;
-        auto put = [&](int need, int stage) {
-            need = static_cast<int>(align_up(std::max(need, 16), 16));
-            std::sort(lv.begin(), lv.end(), [](const Alloc& x, const Alloc& y) { return x.off < y.off; });
-            std::vector<std::pair<int, int>> gaps;   // [begin, end)
-            int at = 0;
-            for (const Alloc& al : lv) { if (al.off > at) gaps.push_back({at, al.off}); at = std::max(at, al.off + al.size); }
-            if (S > at) gaps.push_back({at, S});
-            int best = -1, best_left = -1;
-            for (const auto& gp : gaps) {
-                if (gp.second - gp.first < need) continue;
-                for (int end = 0; end < 2; end++) {
-                    const int off = end ? gp.second - need : gp.first;
-                    int left = 0;   // the largest free block that remains
-                    for (const auto& g2 : gaps) {
-                        if (&g2 != &gp) left = std::max(left, g2.second - g2.first);
-                        else left = std::max(left, std::max(off - g2.first, g2.second - (off + need)));
-                    }
-                    // policy 0: whichever end leaves the larger free block; 1 / 2: wide tensors (>= 32 KB) at the bottom and narrow ones at the top, or the
-                    // other way round (then the first / last gap that fits)
-                    const bool wide_t = need >= 8192;
-                    const int score = policy == 0 ? left : ((policy == 1) == wide_t ? (end ? -1 : S - off) : (end ? off : -1));
-                    if (score > best_left) { best_left = score; best = off; }
-                }
-            }
-            if (best >= 0) lv.push_back(Alloc{best, need, stage});
-            return best;
-        };
-        for (int k = 0; k < NS; k++) {
-            const BandStage& st = prog[static_cast<size_t>(k)];
-            const int keep_src = st.dep >= 0 && !st.far_src ? st.dep : (st.dep < 0 ? -1 : -4);
-            const int keep_res = st.res_mode != RES_UP2X && st.res_dep >= -1 ? st.res_dep : -4;
-            std::vector<Alloc> kept;
-            for (const Alloc& al : lv)
-                if (!dead_at(al, k) || al.stage == keep_src || al.stage == keep_res) kept.push_back(al);
-            lv.swap(kept);
-            in_off[static_cast<size_t>(k)] = out_off[static_cast<size_t>(k)] = -1;
-            if (st.dep < 0) {
-                const int rows = st.kind == BAND_BLOCK ? (st.S == 1 ? st.R + 2 : 2 * st.R + 2) : st.R + 1;
-                if ((in_off[static_cast<size_t>(k)] = put(rows * (st.W + 2) * (st.C + 4), -1)) < 0) return false;
-            } else if (st.far_src) {
-                if ((in_off[static_cast<size_t>(k)] = put((st.R + 1) * (st.W + 2) * (st.C + 4), -3)) < 0) return false;
-            }
-            if (last_reader[static_cast<size_t>(k)] >= 0)
-                if ((out_off[static_cast<size_t>(k)] = put(bandnet_tile_floats(st.R, st.Wo, st.Co, 2 + (read_s2[static_cast<size_t>(k)] ? 1 : 0)), k)) < 0) return false;
-        }
-        return true;
-    };
-    {
-        int S = 4096;
-        bool ok = false;
-        for (; S <= 40960 && !ok; S += ok ? 0 : 64)   // (floats: 16 .. 160 KB in steps of 256 bytes; three placement policies each)
-            for (int policy = 0; policy < 3 && !ok; policy++) ok = layout(S, policy);
-        if (!ok) BAND_GIVE_UP;
-    }
-    std::vector<Alloc> live;
-    int tiles_floats = 0;
-    auto place = [&](int off, int need, int stage) {   // (the place found above)
-        need = static_cast<int>(align_up(std::max(need, 16), 16));
-        live.push_back(Alloc{off, need, stage});
-        tiles_floats = std::max(tiles_floats, off + need);
-        return off;
-    };
-    auto where = [&](int stage) {
-        for (const Alloc& al : live)
-            if (al.stage == stage) return al.off;
-        return -1;
-    };
-    for (int k = 0; k < NS; k++) {
-        BandStage& st = prog[static_cast<size_t>(k)];
-        // what nobody reads any more is free — but for what THIS stage reads (its last reader may be this very stage)
-        {
-            const int keep_src = st.dep >= 0 && !st.far_src ? st.dep : (st.dep < 0 ? -1 : -4);
-            const int keep_res = st.res_mode != RES_UP2X && st.res_dep >= -1 ? st.res_dep : -4;
-            std::vector<Alloc> kept;
-            for (const Alloc& al : live)
-                if (!dead_at(al, k) || al.stage == keep_src || al.stage == keep_res) kept.push_back(al);
-            live.swap(kept);
-        }
-        if (st.dep < 0) {
-            // the program's input comes from global memory into a tile of its own: only its first reader may be such a stage (a skip may read it there later)
-            if (where(-1) >= 0) BAND_GIVE_UP;
-            const int rows = st.kind == BAND_BLOCK ? (st.S == 1 ? st.R + 2 : 2 * st.R + 2) : st.R + 1;
-            st.src_lds = place(in_off[static_cast<size_t>(k)], rows * (st.W + 2) * (st.C + 4), -1);
-            st.src_tile = 0;
-        } else if (st.far_src) {
-            // its own rows come back from the workspace into a free place (held for this stage only)
-            st.src_lds = place(in_off[static_cast<size_t>(k)], (st.R + 1) * (st.W + 2) * (st.C + 4), -3);
-            st.src_tile = 0;
-        } else {
-            st.src_lds = where(st.dep);
-            if (st.src_lds < 0) BAND_GIVE_UP;   // its input is no longer in LDS
-            st.src_tile = 0;
-            st.src_ll = prog[static_cast<size_t>(st.dep)].dst_ll;
-            const BandStage& pd = prog[static_cast<size_t>(st.dep)];
-            const bool cv2_halo = st.kind == BAND_PW && st.S == 2 && pd.R < 2 * st.R;
-            if (((st.kind == BAND_BLOCK || cv2_halo) && st.nbands > 1 && st.src_ll < 0) || (st.cross && st.src_ll < 0)) BAND_GIVE_UP;
-        }
-        if (st.res_mode == RES_UP2X) {
-            const BandStage& cd = prog[static_cast<size_t>(st.res_dep)];
-            if (cd.dst_ll < 0 || cd.R != 1 || cd.Ho * 2 != st.Ho || cd.Wo * 2 != st.Wo || cd.Co != st.Co || st.R != 1) BAND_GIVE_UP;
-            st.res_ll = cd.dst_ll;
-            st.res_stage = st.res_dep;
-            dw_floats = std::max(dw_floats, 2 * cd.Wo * (st.Co + 4));   // its two rows land in the depthwise area (a 1x1 stage does not use it)
-        } else if (st.res_dep >= -1) {
-            st.res_lds = where(st.res_dep);
-            if (st.res_lds < 0) BAND_GIVE_UP;
-            st.res_tile = 1;   // (a flag now: the skip comes from another tile, at res_lds)
-            // the skip is read at the output's pixel positions: its band must have the output's rows (same shape, same owners)
-            if (st.res_mode == RES_MAXPOOL) {
-                // ... or, the 2x2 max of the input of the 2x2 convolution / stride-2 block in front: that stage, run by the same workgroups on the same
-                // bands, left rows 2 r0 .. 2 r0 + 2 R - 1 of the tensor in the tile it read them from
-                if (st.dep < 0 || st.res_dep < 0) BAND_GIVE_UP;
-                const BandStage& cv = prog[static_cast<size_t>(st.dep)];
-                const BandStage& rd = prog[static_cast<size_t>(st.res_dep)];
-                if (cv.S != 2 || cv.dep != st.res_dep || cv.src_lds != st.res_lds || cv.far_src || cv.R != st.R || cv.wshift != st.wshift || cv.nbands != st.nbands)
-                    BAND_GIVE_UP;
-                if (rd.Ho != 2 * st.Ho || rd.Wo != 2 * st.Wo || rd.Co != st.res_c) BAND_GIVE_UP;
-            } else if (st.res_dep >= 0) {
-                const BandStage& rd = prog[static_cast<size_t>(st.res_dep)];
-                if (rd.Ho != st.Ho || rd.Wo != st.Wo || rd.Co != st.res_c || rd.R != st.R || rd.wshift != st.wshift) BAND_GIVE_UP;
-            } else {
-                const BandStage& first = prog[0];   // (the stage that loaded the program's input: own rows at tile rows 1 ..)
-                if (first.dep >= 0 || first.H != st.Ho || first.W != st.Wo || first.C != st.res_c || first.R != st.R || first.wshift != st.wshift || first.S != 1) BAND_GIVE_UP;
-            }
-        }
-        if (last_reader[static_cast<size_t>(k)] >= 0) {
-            st.dst_h3 = read_s2[static_cast<size_t>(k)] ? 1 : 0;
-            st.dst_lds = place(out_off[static_cast<size_t>(k)], bandnet_tile_floats(st.R, st.Wo, st.Co, 2 + st.dst_h3), k);
-            st.dst_tile = 0;   // (a flag now: the output stays in LDS, at dst_lds)
-            if (st.pub_lo || st.pub_hi) {
-                st.dst_ll = ws;
-                ws += align_up(2 * static_cast<long>(st.Ho) * st.Wo * st.Co, 64);
-            }
-        }
-        if (st.far_copy) {   // the plain copy a lateral convolution reads back (frame stride = the workspace's: patched below)
-            st.dst_off = ws;
-            ws += align_up(static_cast<long>(st.Ho) * st.Wo * st.Co, 64);
-        }
-        if (st.far_src) {
-            const BandStage& pd = prog[static_cast<size_t>(st.dep)];
-            if (!pd.far_copy || pd.dst_base != 0) BAND_GIVE_UP;
-            st.src_base = 0;
-            st.src_off = pd.dst_off;
-        }
-        dw_floats = std::max(dw_floats, bandnet_dw_floats(st));
-    }
-    dw_floats = static_cast<int>(align_up(dw_floats, 4));
-    tiles_floats = static_cast<int>(align_up(tiles_floats, 16));
-    band_tiles_floats_ = tiles_floats;
-    band_dw_floats_ = dw_floats;
-    band_cv2_ = false;
-    for (const BandStage& st : prog) band_cv2_ = band_cv2_ || (st.kind == BAND_PW && st.S == 2);
-    band_xb_ = false;
-    for (const BandStage& st : prog) band_xb_ = band_xb_ || (st.kind == BAND_BLOCK && st.cross);
-    if (band_cv2_ && band_xb_) BAND_GIVE_UP;   // (no kernel instantiation for both: the iris network's second branch starts with a 1x1 stage)
-    band_wide_ = false;
-    for (const BandStage& st : prog) band_wide_ = band_wide_ || st.C > 128 || st.Co > 128 || st.res_mode == RES_UP2X || st.pre;
-    if (band_wide_ && (band_cv2_ || band_xb_)) BAND_GIVE_UP;   // (likewise)
-    band_lds_bytes_ = bandnet_lds_bytes(tiles_floats, dw_floats, NS);
-    if (std::getenv("MI_BAND_DEBUG")) {
-        std::fprintf(stderr, "bandnet: %d stages, NW %d, LDS %d B = tiles %d + depthwise %d + constants + program\n", NS, NW, band_lds_bytes_, tiles_floats * 4, dw_floats * 4);
-        for (int k = 0; k < NS; k++) {
-            const BandStage& st = prog[static_cast<size_t>(k)];
-            std::fprintf(stderr, "  stage %2d %s S%d %dx%dx%d -> %dx%dx%d R %d wshift %d src %d dst %d res %d (dep %d, mode %d, c %d) last reader %d\n", k, st.kind == BAND_BLOCK ? "block" : "pw   ", st.S, st.H, st.W, st.C,
-                         st.Ho, st.Wo, st.Co, st.R, st.wshift, st.src_lds * 4, st.dst_tile >= 0 ? st.dst_lds * 4 : -1, st.res_tile >= 0 ? st.res_lds * 4 : -1, st.res_dep, st.res_mode, st.res_c, last_reader[static_cast<size_t>(k)]);
-        }
-    }
-    if (band_lds_bytes_ > 160 * 1024) BAND_GIVE_UP;
-    band_ws_frame_floats_ = std::max<long>(ws, 64);
-    band_nstages_ = NS;
-    consts.resize(consts.size() + 64, 0.f);
-    std::vector<BandPacked> packed(prog.size());
-    for (size_t k = 0; k < prog.size(); k++) {
-        BandStage q = prog[k];
-        if (q.far_copy) q.dst_fs = band_ws_frame_floats_;
-        if (q.far_src) { q.src_fs = band_ws_frame_floats_; q.dep = -1; q.Rin = 0; }   // (the kernel's "input in plain memory" path; the stage order keeps the host's dep)
-        if (!bandnet_pack(q, &packed[k])) BAND_GIVE_UP;
-    }
-    hip_check(hipMalloc(reinterpret_cast<void**>(&d_band_prog_), packed.size() * sizeof(BandPacked)), "hipMalloc band program");
-    hip_check(hipMemcpy(d_band_prog_, packed.data(), packed.size() * sizeof(BandPacked), hipMemcpyHostToDevice), "upload band program");
-    hip_check(hipMalloc(reinterpret_cast<void**>(&d_band_consts_), consts.size() * sizeof(float)), "hipMalloc band constants");
-    hip_check(hipMemcpy(d_band_consts_, consts.data(), consts.size() * sizeof(float), hipMemcpyHostToDevice), "upload band constants");
-    const size_t ws_bytes = static_cast<size_t>(band_ws_frame_floats_) * band_max_frames_ * sizeof(float);
-    band_ws_bytes_ = ws_bytes;
-    hip_check(hipMalloc(reinterpret_cast<void**>(&d_band_ws_), ws_bytes), "hipMalloc band workspace");
-    hip_check(hipMemset(d_band_ws_, 0, ws_bytes), "hipMemset");   // no packet carries a tag yet (tags start at 1)
+    if (!band_ || fuse_level_ < 2) return;
+    BandOptions o;
+    o.nw = band_nw_; o.wide = band_wide_ok_ != 0; o.fork = band_fork_ != 0; o.cu_count = device_cu_count();
+    band_plan_ = build_band_plan(plan_, build_plan(parse_tflite(blob_.data(), blob_.size()), 2), o);
+    upload(d_band_prog_, band_plan_.prog, "hipMalloc band program", "upload band program");
+    upload(d_band_consts_, band_plan_.consts, "hipMalloc band constants", "upload band constants");
+    if (!band_plan_.ready) return;
+    band_ws_bytes_ = static_cast<size_t>(band_plan_.ws_frame_floats) * band_plan_.max_frames * sizeof(float);
+    hip_check(hipMalloc(reinterpret_cast<void**>(&d_band_ws_), band_ws_bytes_), "hipMalloc band workspace");
+    hip_check(hipMemset(d_band_ws_, 0, band_ws_bytes_), "hipMemset");   // no packet carries a tag yet (tags start at 1)
     hip_check(hipMalloc(reinterpret_cast<void**>(&d_band_sync_), 64 * sizeof(unsigned)), "hipMalloc band generation");
     hip_check(hipMemset(d_band_sync_, 0, 64 * sizeof(unsigned)), "hipMemset");
     hip_check(hipHostMalloc(reinterpret_cast<void**>(&h_band_fail_), 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
     *h_band_fail_ = 0;
     hip_check(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_band_fail_), h_band_fail_, 0), "hipHostGetDevicePointer");
-    band_ready_ = true;
 }
-
-#undef BAND_GIVE_UP
 
 void Model::ensure_capacity(int batch) {
     int chunk = chunk_ > 0 ? std::min(chunk_, batch) : batch;
@@ -1183,28 +484,28 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
     for (size_t i = 0; i < plan_.nodes.size(); i++) {
         const Node& n = plan_.nodes[i];
         if (n.kind == Node::Reshape || n.kind == Node::Concat) continue;  // views
-        if (band && static_cast<int>(i) >= band_first_ && !band_node_runs_[i]) {
+        if (band && static_cast<int>(i) >= band_plan_.first && !band_plan_.node_runs[i]) {
             // the single-launch plan: everything behind the first convolution is this one launch (bandnet_kernels.hip), but for the nodes behind
-            // the program's end (band_node_runs_), which keep their launches
-            if (static_cast<int>(i) > band_first_) {
+            // the program's end (band_plan_.node_runs), which keep their launches
+            if (static_cast<int>(i) > band_plan_.first) {
                 if (labels) labels->push_back("(inside the band launch)");
                 mark();
                 continue;
             }
             if (labels) labels->push_back("bandnet_kernel");
             BandLaunch a;
-            a.prog = d_band_prog_; a.nstages = band_nstages_; a.NW = band_nw_used_; a.F = F; a.lds_bytes = band_lds_bytes_;
-            a.tiles_floats = band_tiles_floats_;
-            a.dw_floats = band_dw_floats_; a.ws_frame_floats = band_ws_frame_floats_;
+            a.prog = d_band_prog_; a.nstages = band_plan_.nstages; a.NW = band_plan_.nw; a.F = F; a.lds_bytes = band_plan_.lds_bytes;
+            a.tiles_floats = band_plan_.tiles_floats;
+            a.dw_floats = band_plan_.dw_floats; a.ws_frame_floats = band_plan_.ws_frame_floats;
             long fs = 0;
             a.base[0] = d_band_ws_;
-            a.base[1] = const_cast<float*>(tensor_ptr(band_stem_out_, in, chunk_start, &fs));
-            a.cv2 = band_cv2_ ? 1 : 0;
-            a.xb = band_xb_ ? 1 : 0;
-            a.wide = band_wide_ ? 1 : 0;
-            for (size_t k = 0; k < band_ext_.size(); k++) {
+            a.base[1] = const_cast<float*>(tensor_ptr(band_plan_.stem_out, in, chunk_start, &fs));
+            a.cv2 = band_plan_.cv2 ? 1 : 0;
+            a.xb = band_plan_.xb ? 1 : 0;
+            a.wide = band_plan_.wide ? 1 : 0;
+            for (size_t k = 0; k < band_plan_.ext.size(); k++) {
                 long efs = 0;
-                a.base[2 + k] = band_ext_[k].out_k >= 0 ? d_out_[static_cast<size_t>(band_ext_[k].out_k)] : tensor_ptr_mut(band_ext_[k].tensor, chunk_start, &efs);
+                a.base[2 + k] = band_plan_.ext[k].out_k >= 0 ? d_out_[static_cast<size_t>(band_plan_.ext[k].out_k)] : tensor_ptr_mut(band_plan_.ext[k].tensor, chunk_start, &efs);
             }
             a.consts = d_band_consts_; a.sync = d_band_sync_; a.fail = d_band_fail_;
             a.absent_mod = band_test_absent_;
@@ -1214,7 +515,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
             // launches behind the program that run beside the trunk wait for the node that made their input: every such node inside the
             // program is this launch
             for (size_t j = i; fork && j < plan_.nodes.size(); j++)
-                if (!band_node_runs_[j] && event_after_[j]) hip_check(record_event(node_event(j), trunk), "hipEventRecord");
+                if (!band_plan_.node_runs[j] && event_after_[j]) hip_check(record_event(node_event(j), trunk), "hipEventRecord");
             mark();
             continue;
         }
@@ -1228,7 +529,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t s
         s = trunk;
         // (a whole-frame convolution right behind the band launch stays on the trunk: the face mesh's two heads are 9 + 11 us, a side stream's
         // events cost more than they hide — FaceLandmark::infer 208 us forked, 190 us in line)
-        const bool in_line = band && n.gemm_head && head_wait_[i] >= 0 && !band_node_runs_[static_cast<size_t>(head_wait_[i])];
+        const bool in_line = band && n.gemm_head && head_wait_[i] >= 0 && !band_plan_.node_runs[static_cast<size_t>(head_wait_[i])];
         if (fork && head_slot_[i] >= 0 && !in_line) {
             while (static_cast<int>(head_streams_.size()) <= head_slot_[i]) {
                 hipStream_t st;
@@ -1860,12 +1161,12 @@ void Model::band_before_launch(hipStream_t s) {
 }
 
 bool Model::band_usable(int batch) const {
-    return band_ready_ && band_ > 0 && lanes_ == 1 && batch <= band_max_frames_ && batch <= chunk_cap_;
+    return band_plan_.ready && band_ > 0 && lanes_ == 1 && batch <= band_plan_.max_frames && batch <= chunk_cap_;
 }
 
 int Model::band_workgroups(int batch) {
     if (dirty_) rebuild();
-    return band_ready_ && band_ > 0 && lanes_ == 1 && batch <= band_max_frames_ ? batch * band_nw_used_ : 0;
+    return band_plan_.ready && band_ > 0 && lanes_ == 1 && batch <= band_plan_.max_frames ? batch * band_plan_.nw : 0;
 }
 
 bool Model::band_failed() {
@@ -1897,7 +1198,7 @@ void Model::run_graph_or_eager(const float* in, int batch, hipStream_t s, const 
         for (size_t i = 0; i < plan_.nodes.size(); i++) {
             const Node& n = plan_.nodes[i];
             if (n.kind == Node::Reshape || n.kind == Node::Concat) continue;
-            if (static_cast<int>(i) < band_first_ || band_node_runs_[i]) launches++;
+            if (static_cast<int>(i) < band_plan_.first || band_plan_.node_runs[i]) launches++;
         }
         eager = launches <= 2;
     }

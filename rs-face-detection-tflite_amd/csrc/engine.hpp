@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "bandplan.hpp"
 #include "consts.hpp"
 #include "plan.hpp"
 
@@ -72,8 +73,7 @@ class Model {
     void schedule_side_streams();         // which nodes of plan_ run beside the trunk (head_slot_, head_wait_, event_after_)
     struct Option;                        // one row of the option table (engine.cpp)
     static const Option* find_option(const std::string& key);
-    void build_bandnet();                 // the single-launch plan of the same graph, when its operators have band stages
-    void build_bandnet_try(bool conv2_ok);
+    void build_bandnet();                 // the single-launch plan of the same graph (bandplan.cpp), uploaded, with its workspace
     void free_bandnet();
     bool band_usable(int batch) const;
     void band_before_launch(hipStream_t s);
@@ -127,8 +127,7 @@ class Model {
     // single-launch plan for one_shot runs (bandnet_kernels.hip): the first convolution as in the batched plan, everything behind it ONE launch
     int band_ = 1;                  // option "band": 0 never, 1 one_shot runs, 2 every run of few enough frames (tests, profiling)
     int band_nw_ = 128;             // option "band_nw": most workgroups per frame
-    int band_nw_used_ = 0;          // ... of the program that was built
-    bool band_ready_ = false;       // the graph has a single-launch form
+    BandPlan band_plan_;            // what build_band_plan made of the graph (ready: it has a single-launch form); prog and consts are freed after the upload
     bool band_use_ = false;         // the run being enqueued takes it
     bool band_ran_ = false;         // the last run_device took it
     int band_test_fail_ = 0;        // option "band_test_fail"
@@ -140,16 +139,7 @@ class Model {
     bool band_gen_force_ = false;   // option "band_test_gen"
     int band_wraps_ = 0;            // times the workspace was cleared for that reason
     size_t band_ws_bytes_ = 0;
-    int band_first_ = 0;            // plan_ node the band launch stands for (with every node behind it that band_node_runs_ does not name)
-    int band_stem_out_ = -1;        // tensor the first convolution writes = the band program's input
-    int band_nstages_ = 0, band_lds_bytes_ = 0, band_max_frames_ = 0, band_dw_floats_ = 0;
-    int band_tiles_floats_ = 0;     // LDS floats of the program's tiles
-    long band_ws_frame_floats_ = 0;
-    struct BandExt { int out_k = -1, tensor = -1; };   // BandLaunch::base[2 + j]: graph output out_k, or the arena storage of `tensor` (read by a launch behind the band program)
-    std::vector<BandExt> band_ext_;
-    std::vector<char> band_node_runs_;   // per plan_ node from band_first_ on: 1 = it runs as its own launch behind the band launch (the program stops in front of it)
     int band_fork_ = 1, band_wide_ok_ = 1;   // options "band_fork", "band_wide"
-    bool band_cv2_ = false, band_xb_ = false, band_saw_conv2_ = false, band_wide_ = false;
     BandPacked* d_band_prog_ = nullptr;
     float* d_band_consts_ = nullptr;
     float* d_band_ws_ = nullptr;
