@@ -14,6 +14,7 @@
 
 #include "bandplan.hpp"
 #include "consts.hpp"
+#include "launches.hpp"
 #include "plan.hpp"
 
 namespace mi {
@@ -70,7 +71,6 @@ class Model {
 
    private:
     void rebuild();                       // (re)lower, pack (consts.cpp) + upload weights for the current options
-    void schedule_side_streams();         // which nodes of plan_ run beside the trunk (head_slot_, head_wait_, event_after_)
     struct Option;                        // one row of the option table (engine.cpp)
     static const Option* find_option(const std::string& key);
     void build_bandnet();                 // the single-launch plan of the same graph (bandplan.cpp), uploaded, with its workspace
@@ -79,12 +79,9 @@ class Model {
     void band_before_launch(hipStream_t s);
     void poison_scratch(hipStream_t s);   // option "test_poison"
     void ensure_capacity(int batch);
-    void enqueue_chunk(const float* in, int chunk_start, int frames, hipStream_t s, std::vector<hipEvent_t>* marks = nullptr,
-                       std::vector<std::string>* labels = nullptr);
-    std::string node_label(const Node& n) const;
+    LaunchCtx launch_ctx(const float* in, int chunk_start, int frames) const;   // what lower_chunk (launches.cpp) reads of this handle
+    void enqueue_chunk(const float* in, int chunk_start, int frames, hipStream_t s, std::vector<hipEvent_t>* marks = nullptr, Lowered* keep = nullptr);
     void enqueue_all(const float* in, int batch, hipStream_t s);
-    const float* tensor_ptr(int t, const float* in, int chunk_start, long* frame_stride) const;
-    float* tensor_ptr_mut(int t, int chunk_start, long* frame_stride) const;
     void invalidate_graphs();
 
     int device_ = 0;
@@ -102,11 +99,9 @@ class Model {
     std::vector<hipStream_t> side_streams_;  // lanes 1.. run on their own streams (forked/joined with events)
     std::vector<hipEvent_t> lane_events_;
     // output heads (nodes that only feed graph outputs, after the last trunk node) run on side streams beside the trunk
-    std::vector<int> head_slot_;          // per node: side stream of a forked head, -1 otherwise
-    std::vector<int> head_wait_;          // per forked head: node whose completion it waits for (-1: start of the plan)
-    std::vector<char> event_after_;       // per node: a forked head waits for it
+    SideSchedule sched_;                  // per node: which (schedule_side_streams, launches.cpp)
     std::vector<hipStream_t> head_streams_;
-    std::vector<hipEvent_t> head_events_; // one per node (lazily created) + one per side stream for the join
+    std::vector<hipEvent_t> head_events_; // one per launch (lazily created), one for the start of the plan, one per side stream for the join
     bool dirty_ = true;
 
     float* d_weights_ = nullptr;

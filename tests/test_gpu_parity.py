@@ -1888,3 +1888,21 @@ print(json.dumps({"rows": rows, "total_s": time.perf_counter() - t0, "worst_s": 
         assert res["worst_s"] < 0.25, res          # one bounded wait + the batched plan, never seconds
         assert res["total_s"] < 30, res
     assert wall < 120
+
+
+@pytest.mark.parametrize("frames", [1, 32])
+def test_iris_profile_labels_equal_the_pinned_launch_list(gpu, frames):
+    """The launch list is pinned on the CPU with fake device addresses (tests/test_launch_pins.py); the only thing the selection reads from a
+    pointer is its alignment.  On the device, with real addresses, the iris network (64 x 64 input, the smallest) takes the same branches: the
+    kernel labels profile() returns, in order, are the labels pinned for that model and frame count at the default options."""
+    import json
+    import re
+    import torch
+    pins = json.load(open(os.path.join(GOLDEN, "launch_pins.json")))
+    want = [re.search(r'"(.*)"', line).group(1) for line in pins["iris_landmark.tflite defaults F=%d" % frames] if '"' in line]
+    assert len(want) > 3
+    m = gpu.Model(model_path("iris"))
+    x = seeded_input("iris", frames, 77, m.input_dims[1:3])
+    labels = [r["kernel"] for r in m.profile(torch.from_numpy(x).cuda(), reps=1)]
+    m.close()
+    assert labels == want

@@ -1,5 +1,5 @@
-"""The host-side lowering (plan.cpp), constant packing (consts.cpp) and single-launch planner (bandplan.cpp) under AddressSanitizer, over mutated graphs.  CPU only: it builds the
-HOST side of plan.cpp / consts.cpp / bandplan.cpp / tflite_graph.cpp with hipcc's AddressSanitizer and links the product's other objects; every hipcc line that names -fsanitize= also
+"""The host-side lowering (plan.cpp), constant packing (consts.cpp), single-launch planner (bandplan.cpp) and launch lists (launches.cpp) under AddressSanitizer, over mutated graphs.  CPU only: it builds the
+HOST side of plan.cpp / consts.cpp / bandplan.cpp / launches.cpp / tflite_graph.cpp with hipcc's AddressSanitizer and links the product's other objects; every hipcc line that names -fsanitize= also
 carries -fno-gpu-sanitize, so no device code is instrumented, and none is run."""
 import os
 import subprocess
@@ -17,13 +17,13 @@ def test_lowering_of_mutated_models_under_address_sanitizer(tmp_path):
     its output's shape that way — a four-byte read behind a vector, which crashed the plain build once in twenty runs — and a PRELU on a
     tensor of rank 0."""
     build = os.path.join(ROOT, "rs-face-detection-tflite_amd", "build")
-    objs = sorted(f for f in (os.path.join(build, n) for n in os.listdir(build)) if f.endswith(".o") and os.path.basename(f) not in ("plan.o", "consts.o", "bandplan.o", "tflite_graph.o"))
+    objs = sorted(f for f in (os.path.join(build, n) for n in os.listdir(build)) if f.endswith(".o") and os.path.basename(f) not in ("plan.o", "consts.o", "bandplan.o", "launches.o", "tflite_graph.o"))
     assert len(objs) >= 15, "build the product first (__graft_entry__.build())"
     flags = ["-O1", "-g", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
              "-fsanitize=address", "-fno-gpu-sanitize", "-fno-omit-frame-pointer"]
     hipcc = "/opt/rocm/bin/hipcc"
     mine = []
-    for src in (os.path.join(CSRC, "plan.cpp"), os.path.join(CSRC, "consts.cpp"), os.path.join(CSRC, "bandplan.cpp"), os.path.join(CSRC, "tflite_graph.cpp"), os.path.join(ROOT, "tests", "asan_lowering.cpp")):
+    for src in (os.path.join(CSRC, "plan.cpp"), os.path.join(CSRC, "consts.cpp"), os.path.join(CSRC, "bandplan.cpp"), os.path.join(CSRC, "launches.cpp"), os.path.join(CSRC, "tflite_graph.cpp"), os.path.join(ROOT, "tests", "asan_lowering.cpp")):
         o = str(tmp_path / (os.path.basename(src) + ".o"))
         subprocess.check_call([hipcc] + flags + ["-x", "hip", "-c", src, "-o", o], stderr=subprocess.DEVNULL)
         mine.append(o)
@@ -45,9 +45,11 @@ def test_lowering_of_mutated_models_under_address_sanitizer(tmp_path):
             blobs.append(f)
     r = subprocess.run([exe] + blobs, capture_output=True, text=True, timeout=900, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert r.returncode == 0, r.stderr[-3000:]
-    ok, refused, packed, unpacked, band_ready, band_none, band_threw, planned = (int(v) for v in r.stdout.split()[1::2])
+    ok, refused, packed, unpacked, band_ready, band_none, band_threw, planned, lowered, lower_threw = (int(v) for v in r.stdout.split()[1::2])
     assert ok > 100 and refused > 100
     # every accepted plan went through pack_plan_consts (consts.cpp) as well: it gave a blob or threw, and AddressSanitizer saw no wild read
     assert packed + unpacked == ok and packed > 100
     # every blob that lowered at both levels went through build_band_plan (bandplan.cpp) twice: a program, none, or an exception
     assert band_ready + band_none + band_threw == 2 * planned and planned > 0 and band_ready > 50
+    # every plan that was packed went through lower_chunk (launches.cpp) at 1 and at 32 frames: a launch list, or an exception
+    assert lowered + lower_threw == 2 * packed and lowered > 100
