@@ -167,6 +167,13 @@ extern "C" {
     pub fn mi_pipeline_run(p: *mut mi_pipeline, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,
                            faces: *mut mi_detection, face_counts: *mut c_int, landmarks: *mut c_float, present: *mut c_int,
                            eyes: *mut c_float, mem: c_int, stream: *mut c_void) -> c_int;
+    // ... for the first max_faces faces of every frame, compacted into max_items items (include/mi_face.h)
+    pub fn mi_pipeline_run_faces(p: *mut mi_pipeline, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,
+                                 max_faces: c_int, max_items: c_int, faces: *mut mi_detection, face_counts: *mut c_int,
+                                 item_frame: *mut c_int, item_face: *mut c_int, n_items: *mut c_int, landmarks: *mut c_float,
+                                 present: *mut c_int, eyes: *mut c_float, mem: c_int, stream: *mut c_void) -> c_int;
+    pub fn mi_face_items_layout(face_counts: *const c_int, batch: c_int, max_faces: c_int, max_items: c_int, item_frame: *mut c_int,
+                                item_face: *mut c_int, n_items: *mut c_int) -> c_int;
 
     // render.rs:262-479 on the device
     pub fn mi_render_annotations(device: c_int, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,

@@ -18,6 +18,7 @@ pub mod types;
 pub mod face_detection;
 pub mod face_landmark;
 pub mod iris_landmark;
+pub mod pipeline;
 pub mod render;
 pub mod utils;
 
@@ -25,6 +26,7 @@ pub use face_detection::{FaceDetection, FaceDetectionModel};
 pub use face_landmark::{face_detection_to_roi, FaceLandmark};
 pub use render::{detections_to_render_data, landmarks_to_render_data, render_to_image, Annotation, AnnotationData, Color, Colors};
 pub use iris_landmark::{iris_roi_from_face_landmarks, update_face_landmarks_with_iris_results, IrisLandmark};
+pub use pipeline::{face_items_layout, FacesResults, Pipeline};
 pub use types::{BBox, Detection, Image, IrisResults, Landmark, Rect};
 
 use anyhow::Error;

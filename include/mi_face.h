@@ -317,6 +317,29 @@ int mi_pipeline_set_option(mi_pipeline *p, const char *key, int value);
  * All pointers follow `mem`. */
 int mi_pipeline_run(mi_pipeline *p, const uint8_t *frames, int batch, int width, int height, int stride, mi_detection *faces,
                     int *face_counts, float *landmarks, int *present, float *eyes, int mem, void *stream);
+/* The same flow for EVERY face of a frame (a group photo, a two-person call), still without a host round trip: the detector's first
+ * `max_faces` (1..16) detections of each frame, in the detector's output order, each through face_detection_to_roi -> FaceLandmark::infer ->
+ * iris_roi_from_face_landmarks -> 2 x IrisLandmark::infer exactly as above.  The faces of the batch are compacted on the device into a list of
+ * `max_items` (1..32767) ITEMS, in frame order, then detector order: frame b contributes n_b = min(max(face_counts[b], 0), max_faces) faces, and
+ * item j = (sum of n_b' for b' < b) + k is face k of frame b while j < max_items.
+ *   faces        [batch][max_faces], zeros behind a frame's last detection   face_counts [batch] detections found (may exceed max_faces)
+ *   item_frame   [max_items] frame of item j, -1 for an unused slot           item_face   [max_items] k of faces[frame][k], -1 when unused
+ *   n_items      [2]: slots used = min(total, max_items); faces (within max_faces) that got no slot = total - slots used
+ *   landmarks    f32 [max_items][468][3]   present [max_items]   eyes f32 [max_items][2][76][3]   (zeros in unused slots)
+ * `faces` and `face_counts` cover every frame whatever the budget.  COST: the mesh network always runs on max_items items and the iris network on
+ * 2 * max_items, whatever the detector finds — launch shapes depend on the arguments alone, so the call reads no count back, stays asynchronous
+ * (MI_MEM_DEVICE with a caller's stream: no host synchronisation but the one-off upload when the batch geometry changes) and can be replayed.
+ * max_items is part of that geometry, with width and height: calls that alternate between two budgets on one handle upload and synchronise
+ * every time, so keep one handle per budget where that matters.
+ * Choose max_items for the faces you expect, not batch * max_faces.  This entry always runs the batched plan: it never takes a single-launch
+ * plan, so it claims no CUs and has no retry path.  batch <= 2^26.  max_items beyond 32767 is MI_EINVAL before anything is queued (the
+ * pre-processing launch has one grid row per item, at most 65535 of them, and the iris stage has 2 * max_items items).  All pointers follow `mem`. */
+int mi_pipeline_run_faces(mi_pipeline *p, const uint8_t *frames, int batch, int width, int height, int stride, int max_faces, int max_items,
+                          mi_detection *faces, int *face_counts, int *item_frame, int *item_face, int *n_items, float *landmarks,
+                          int *present, float *eyes, int mem, void *stream);
+/* Host only, no GPU: the item layout the call above produces for these counts (the specification of the device kernel; both go through
+ * the same arithmetic).  MI_EINVAL for a null pointer, max_faces outside 1..16, max_items outside 1..2^20 or batch outside 1..2^26. */
+int mi_face_items_layout(const int *face_counts, int batch, int max_faces, int max_items, int *item_frame, int *item_face, int *n_items);
 /* The same flow from ENCODED pictures, as the reference's own test runs it (lib.rs:18-40: include_bytes!(man.jpg) -> convert_image_to_mat ->
  * FaceDetection::infer -> FaceLandmark::infer -> 2 x IrisLandmark::infer), for a stream of them, two slots (see mi_fd_submit_jpeg): submit decodes the
  * entropy-coded data on the calling thread while the device still works through the other slot's picture, and queues the decoder's sample arithmetic

@@ -325,6 +325,72 @@ inline std::vector<Landmark> update_face_landmarks_with_iris_results(const std::
     return out;
 }
 
+// The item layout of mi_pipeline_run_faces for these detection counts (mi_face_items_layout: host only, no GPU).
+struct FaceItemsLayout {
+    std::vector<int> item_frame, item_face;  // [max_items], -1 in unused slots
+    int n_items = 0, dropped = 0;            // slots used; faces (within max_faces) that got no slot
+};
+inline FaceItemsLayout face_items_layout(const std::vector<int>& face_counts, int max_faces, int max_items) {
+    FaceItemsLayout o;
+    // (the C side refuses max_items outside 1..2^20 before it writes, so this allocation stops there too)
+    o.item_frame.resize(static_cast<std::size_t>(std::min(std::max(max_items, 0), 1 << 20)));
+    o.item_face.resize(o.item_frame.size());
+    int n[2] = {0, 0};
+    detail::check(mi_face_items_layout(face_counts.data(), static_cast<int>(face_counts.size()), max_faces, max_items, o.item_frame.data(),
+                                       o.item_face.data(), n));
+    o.n_items = n[0];
+    o.dropped = n[1];
+    return o;
+}
+
+// The batched detector -> mesh -> iris flow on the device (mi_pipeline_*), results in host memory.
+struct FacesResults {            // mi_pipeline_run_faces: see include/mi_face.h for the layout of the items
+    std::vector<mi_detection> faces;         // [batch][max_faces], zeros behind a frame's last detection
+    std::vector<int> face_counts;            // [batch]
+    std::vector<int> item_frame, item_face;  // [max_items]
+    int n_items = 0, dropped = 0;
+    std::vector<float> landmarks;            // [max_items][468][3]
+    std::vector<int> present;                // [max_items]
+    std::vector<float> eyes;                 // [max_items][2][76][3]
+};
+class Pipeline {
+   public:
+    explicit Pipeline(FaceDetectionModel model_type, std::optional<std::string> model_dir = std::nullopt, int device = 0) {
+        detail::check(mi_pipeline_create(static_cast<int>(model_type), model_dir ? model_dir->c_str() : nullptr, device, &h_));
+    }
+    ~Pipeline() { mi_pipeline_free(h_); }
+    Pipeline(const Pipeline&) = delete;
+    Pipeline& operator=(const Pipeline&) = delete;
+
+    // lib.rs:24-40 for the first max_faces faces of every frame; the mesh and iris networks run on max_items (0: batch * max_faces) items
+    // whatever the detector finds, so choose max_items for the faces you expect.
+    FacesResults run_faces(const std::uint8_t* frames, int batch, int width, int height, int stride, int max_faces = 4, int max_items = 0) const {
+        // the C entry's ranges, checked before anything is sized from them (batch * max_faces must not overflow, and the results are 10 kB an item)
+        if (batch < 1 || batch > (1 << 26) || max_faces < 1 || max_faces > 16) throw std::invalid_argument("run_faces: batch 1..2^26, max_faces 1..16");
+        if (max_items <= 0) max_items = static_cast<int>(std::min<long long>(static_cast<long long>(batch) * max_faces, 1 << 20));
+        if (max_items > 32767) throw std::invalid_argument("run_faces: max_items 1..32767 (0: batch * max_faces)");
+        const std::size_t M = static_cast<std::size_t>(max_items);
+        FacesResults r;
+        r.faces.resize(static_cast<std::size_t>(batch) * max_faces);
+        r.face_counts.resize(static_cast<std::size_t>(batch));
+        r.item_frame.resize(M);
+        r.item_face.resize(M);
+        r.landmarks.resize(M * 3 * MI_NUM_FACE_LANDMARKS);
+        r.present.resize(M);
+        r.eyes.resize(M * 2 * 3 * (MI_NUM_EYE_LANDMARKS + MI_NUM_IRIS_LANDMARKS));
+        int n[2] = {0, 0};
+        detail::check(mi_pipeline_run_faces(h_, frames, batch, width, height, stride, max_faces, max_items, r.faces.data(), r.face_counts.data(),
+                                            r.item_frame.data(), r.item_face.data(), n, r.landmarks.data(), r.present.data(), r.eyes.data(),
+                                            MI_MEM_HOST, nullptr));
+        r.n_items = n[0];
+        r.dropped = n[1];
+        return r;
+    }
+
+   private:
+    mi_pipeline* h_ = nullptr;
+};
+
 // render.rs on the device (include/mi_face.h, "render.rs").  Colors::{BLACK, ...} (render.rs:28-68) as the bytes render_to_image writes.
 struct Colors {
     static constexpr mi_color BLACK = MI_COLOR_BLACK, RED = MI_COLOR_RED, GREEN = MI_COLOR_GREEN, BLUE = MI_COLOR_BLUE, PINK = MI_COLOR_PINK,

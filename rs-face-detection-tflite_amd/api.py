@@ -39,6 +39,7 @@ EXPORTS = [
     "mi_iris_create", "mi_iris_create_from_bytes", "mi_iris_free", "mi_iris_model", "mi_iris_infer_tensor", "mi_iris_infer_images",
     "mi_iris_infer_image",
     "mi_pipeline_create", "mi_pipeline_create_from_bytes", "mi_pipeline_model", "mi_pipeline_free", "mi_pipeline_set_option", "mi_pipeline_run",
+    "mi_pipeline_run_faces", "mi_face_items_layout",
     "mi_bbox_to_roi", "mi_bbox_from_landmarks", "mi_face_detection_to_roi", "mi_iris_roi_from_face_landmarks", "mi_update_face_landmarks_with_iris_results", "mi_image_to_tensor", "mi_jpeg_info", "mi_jpeg_decode_rgb",
     "mi_render_annotations", "mi_render_faces",
 ]
@@ -293,6 +294,8 @@ def lib():
     L.mi_pipeline_free.restype = None
     L.mi_pipeline_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.mi_pipeline_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
+    L.mi_pipeline_run_faces.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
+    L.mi_face_items_layout.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.mi_face_detection_to_roi.argtypes = [C.POINTER(CDetection), C.c_int, C.c_int, C.POINTER(Rect)]
     L.mi_iris_roi_from_face_landmarks.argtypes = [C.POINTER(CLandmark), C.c_int, C.c_int, C.POINTER(Rect), C.POINTER(Rect)]
     L.mi_update_face_landmarks_with_iris_results.argtypes = [C.POINTER(CLandmark)] * 4
@@ -948,6 +951,54 @@ class Pipeline:
         _check(self.L.mi_pipeline_run(self.h, p, B, W, H, stride, _ptr(out["faces"])[0], _ptr(out["face_counts"])[0],
                                       _ptr(out["landmarks"])[0], _ptr(out["present"])[0], _ptr(out["eyes"])[0], mem, C.c_void_p(stream or 0)))
         return out
+
+    def run_faces(self, frames, max_faces=4, max_items=None, stream=None):
+        """The same flow for the first `max_faces` (1..16) faces of every frame (mi_pipeline_run_faces; max_items 1..32767).  frames as in run().  The faces of the
+        batch are compacted into `max_items` items (None: B * max_faces) in frame order, then detector order; the mesh and iris networks run on
+        exactly max_items / 2 * max_items items whatever the detector finds, so choose max_items for the faces you expect.
+        Returns dict(faces [B,max_faces,17], face_counts [B], item_frame [M], item_face [M] (-1 in unused slots), landmarks [M,468,3],
+        present [M], eyes [M,2,76,3], counts [2] = (n_items, dropped), n_items = slots used, dropped = faces within max_faces that got no slot).
+        n_items and dropped are ints for host frames; for device frames they are 0-d views of `counts` (nothing is read back)."""
+        B, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        F = int(max_faces)
+        M = B * F if max_items is None else int(max_items)
+        if not (1 <= F <= 16 and 1 <= M <= 32767):   # (before the outputs are sized by them; the C entry checks again)
+            raise MiError(-1, "max_faces must be 1..16 and max_items 1..32767")   # MI_EINVAL
+        shapes = dict(faces=((B, F, 17), "float32"), face_counts=((B,), "int32"), item_frame=((M,), "int32"), item_face=((M,), "int32"),
+                      counts=((2,), "int32"), landmarks=((M, 468, 3), "float32"), present=((M,), "int32"), eyes=((M, 2, 76, 3), "float32"))
+        if _is_torch(frames) and frames.is_cuda:
+            import torch
+            mem = MI_MEM_DEVICE
+            out = {k: torch.zeros(sh, dtype=getattr(torch, dt), device=frames.device) for k, (sh, dt) in shapes.items()}
+            p = C.c_void_p(frames.data_ptr())
+            stride = int(frames.stride(1))
+            if frames.dim() != 4 or frames.shape[3] != 3 or frames.stride(2) != 3 or frames.stride(3) != 1 or frames.stride(0) != stride * H:
+                raise ValueError("frames must be [B,H,W,3] with dense pixels and frames stride*H bytes apart")
+            _device_ready(frames, self.device, None, "uint8")
+        else:
+            frames = np.ascontiguousarray(frames, np.uint8)
+            mem = MI_MEM_HOST
+            out = {k: np.zeros(sh, getattr(np, dt)) for k, (sh, dt) in shapes.items()}
+            p = C.c_void_p(frames.ctypes.data)
+            stride = int(frames.strides[1])
+        _check(self.L.mi_pipeline_run_faces(self.h, p, B, W, H, stride, F, M, _ptr(out["faces"])[0], _ptr(out["face_counts"])[0],
+                                            _ptr(out["item_frame"])[0], _ptr(out["item_face"])[0], _ptr(out["counts"])[0], _ptr(out["landmarks"])[0],
+                                            _ptr(out["present"])[0], _ptr(out["eyes"])[0], mem, C.c_void_p(stream or 0)))
+        # host frames: ints; device frames: 0-d views of `counts` on the device (nothing is read back)
+        out["n_items"], out["dropped"] = (int(out["counts"][0]), int(out["counts"][1])) if mem == MI_MEM_HOST else (out["counts"][0], out["counts"][1])
+        return out
+
+
+def face_items_layout(face_counts, max_faces, max_items):
+    """mi_face_items_layout (host only, no GPU): the item layout Pipeline.run_faces produces for these detection counts.
+    -> (item_frame int32 [max_items], item_face int32 [max_items], n_items, dropped)."""
+    counts = np.ascontiguousarray(face_counts, np.int32).reshape(-1)
+    M = int(max_items)
+    # (the C entry writes max_items entries and refuses a max_items it would not write: the arrays need never be larger than its limit)
+    item_frame, item_face, n = np.zeros((max(min(M, 1 << 20), 1),), np.int32), np.zeros((max(min(M, 1 << 20), 1),), np.int32), np.zeros((2,), np.int32)
+    _check(lib().mi_face_items_layout(C.c_void_p(counts.ctypes.data), int(counts.size), int(max_faces), M, C.c_void_p(item_frame.ctypes.data),
+                                      C.c_void_p(item_face.ctypes.data), C.c_void_p(n.ctypes.data)))
+    return item_frame, item_face, int(n[0]), int(n[1])
 
 
 def _picture(x, channels, what):

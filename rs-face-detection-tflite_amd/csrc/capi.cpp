@@ -22,6 +22,7 @@
 #include <thread>
 
 #include "engine.hpp"
+#include "face_items.hpp"
 #include "launch.hpp"
 #include "host_glue.hpp"
 #include "kernels.hpp"
@@ -359,6 +360,10 @@ struct mi_pipeline {
     DeviceBuf geom_det;                              // the detector's letterbox geometry of `geom_B` pictures of geom_w x geom_h (no ROI: uploaded once)
     int geom_B = 0, geom_w = 0, geom_h = 0;
     int sizes_B = 0, sizes_w = 0, sizes_h = 0;  // what `sizes` holds (uploaded once per batch geometry, not per call)
+    // mi_pipeline_run_faces: ROI and valid flag of every item slot, and the image sizes of its max_items items (as `sizes`, kept apart so that
+    // alternating calls of the two entries upload nothing)
+    DeviceBuf roi_item, valid_item, sizes_item;
+    int sizes_item_N = 0, sizes_item_w = 0, sizes_item_h = 0;
     // the streamed form from encoded pictures (mi_pipeline_submit_jpeg / mi_pipeline_collect_jpeg): per slot the decoder's state and picture, the
     // results' device block and its pinned image
     struct PipeJpegSlot {
@@ -614,13 +619,18 @@ int mi_fd_anchors(const mi_fd* h, float* out_xy, int cap) {
 }
 
 // shared tail: raw device outputs -> detections
+// what the batched pipelines ask of the post-processing launch on top of the detections (device results only)
+struct FdPostPipeline {
+    mi::RectD* face_rois = nullptr;   // [batch] or null: faces[0]'s ROI (face_detection_to_roi on a picture of image_w x image_h) from the same launch
+    int* face_valid = nullptr;        // [batch], with face_rois
+    int image_w = 0, image_h = 0;
+};
 static void fd_post(mi_fd* h, const float* d_boxes, const float* d_scores, int batch, const double* padding, mi_detection* out,
-                    int cap, int* counts, int mem, hipStream_t s, mi::RectD* d_face_rois = nullptr, int* d_face_valid = nullptr, int image_w = 0,
-                    int image_h = 0) {
+                    int cap, int* counts, int mem, hipStream_t s, const FdPostPipeline* pipe = nullptr) {
     mi::PostArgs a;
-    if (d_face_rois) {   // (device results only: the batched pipeline) zeros behind the last detection and faces[0]'s ROI from the same launch
+    if (pipe) {   // zeros behind a frame's last detection (no memset in front of the launch) and, when asked for, faces[0]'s ROI
         a.zero_rest = 1;
-        a.face_rois = d_face_rois; a.face_valid = d_face_valid; a.image_w = image_w; a.image_h = image_h;
+        a.face_rois = pipe->face_rois; a.face_valid = pipe->face_valid; a.image_w = pipe->image_w; a.image_h = pipe->image_h;
     }
     a.raw_boxes = d_boxes;
     a.raw_scores = d_scores;
@@ -1567,31 +1577,37 @@ struct PipeLayout {        // one block: faces | counts | landmarks | present | 
 };
 }  // namespace
 
-// One pass of the flow of lib.rs:24-40 over B frames that are in device memory: everything is queued on `s`, nothing is waited for (but the
-// upload of the per-item image sizes when the batch geometry changes).  The caller holds the three handles (Use) and, for one_shot, the CUs.
-static void pipeline_enqueue(mi_pipeline* p, const uint8_t* d_frames, int B, int width, int height, int stride, const PipeOut& o, bool one_shot, hipStream_t s) {
-    mi::Model& fdm = *p->fd->model.m;
-    mi::Model& flm = *p->fl->model.m;
-    mi::Model& irm = *p->iris->model.m;
-    const int cap = kPipeCap;
-    const long eye_fs = kEyeFs;
-    const size_t frame_bytes = static_cast<size_t>(stride) * height;
-    auto* d_geom = static_cast<mi::PreGeom*>(p->geom.get(sizeof(mi::PreGeom) * 2 * B));
-    // (w, h) of the source image of every ROI, for Rect::scaled in project_landmarks
-    int* d_sizes = static_cast<int*>(p->sizes.get(sizeof(int) * 4 * B));
-    if (p->sizes_B != B || p->sizes_w != width || p->sizes_h != height) {  // a host round trip only when the batch geometry changes
-        std::vector<int> hs(4 * static_cast<size_t>(B));
-        for (int i = 0; i < 2 * B; i++) { hs[2 * i] = width; hs[2 * i + 1] = height; }
-        p->sizes_B = 0;
+// (w, h) of the source image of every ROI of a pass over N mesh items (2 N eyes), for Rect::scaled in project_landmarks: a host round trip only
+// when the batch geometry changes.  `have_*` say what `buf` holds.
+static int* pipeline_sizes(DeviceBuf& buf, int& have_N, int& have_w, int& have_h, int N, int width, int height, hipStream_t s) {
+    int* d_sizes = static_cast<int*>(buf.get(sizeof(int) * 4 * N));
+    if (have_N != N || have_w != width || have_h != height) {
+        std::vector<int> hs(4 * static_cast<size_t>(N));
+        for (int i = 0; i < 2 * N; i++) { hs[2 * i] = width; hs[2 * i + 1] = height; }
+        have_N = 0;
         mi::hip_check(hipMemcpyAsync(d_sizes, hs.data(), hs.size() * sizeof(int), hipMemcpyHostToDevice, s), "H2D sizes");
         mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");  // hs is a host temporary
-        p->sizes_B = B; p->sizes_w = width; p->sizes_h = height;
+        have_N = N; have_w = width; have_h = height;
     }
-    static const bool ptrace = getenv("MI_PIPE_TRACE") != nullptr;
-    auto t_start = std::chrono::steady_clock::now();
-    auto tr = [&](const char* what) { if (ptrace) std::fprintf(stderr, "  %-22s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count()); };
-    // ---- 1. detector: image_to_tensor(frame, None, (w,h), keep_aspect = true, (-1,1)) -> net -> decode + NMS
-    mi::PreItems it{};
+    return d_sizes;
+}
+
+struct PipeTrace {   // MI_PIPE_TRACE=1: host-side step times of a pass, to stderr
+    const bool on;
+    std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    PipeTrace() : on(enabled()) {}
+    static bool enabled() { static const bool e = getenv("MI_PIPE_TRACE") != nullptr; return e; }
+    void operator()(const char* what) const {
+        if (on) std::fprintf(stderr, "  %-22s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count());
+    }
+};
+
+// The detector's stage of a pass over B frames in device memory: image_to_tensor(frame, None, (w,h), keep_aspect = true, (-1,1)) -> net.  Sets up
+// `it` (the frames; the later stages change the item fields) and returns the letterbox paddings [B][4] the post-processing launch needs.
+static double* pipeline_detect(mi_pipeline* p, mi::PreItems& it, const uint8_t* d_frames, int B, int width, int height, int stride, bool one_shot, hipStream_t s,
+                               const PipeTrace& tr) {
+    mi::Model& fdm = *p->fd->model.m;
+    const size_t frame_bytes = static_cast<size_t>(stride) * height;
     it.frames = d_frames; it.frame_bytes = static_cast<long>(frame_bytes); it.width = width; it.height = height; it.stride = stride;
     it.items_per_frame = 1; it.N = B; it.out_w = p->fd->in_w; it.out_h = p->fd->in_h; it.keep_aspect = 1;
     it.range_min = -1.0; it.range_max = 1.0;
@@ -1608,56 +1624,83 @@ static void pipeline_enqueue(mi_pipeline* p, const uint8_t* d_frames, int B, int
     tr("pre det");
     fdm.run_device(d_in_det, B, s, one_shot);
     tr("det run_device");
-    float* d_dets = static_cast<float*>(p->dets.get(sizeof(mi_detection) * cap * B));
-    // ---- 2. faces[0] -> face_detection_to_roi -> image_to_tensor(frame, roi, (192,192), false, (0,1)) -> mesh net
-    // (the post-processing launch writes zeros behind a frame's last detection — frames without a face report zeros — and faces[0]'s ROI)
-    auto* d_roi_face = static_cast<mi::RectD*>(p->roi_face.get(sizeof(mi::RectD) * B));
-    int* d_valid_face = static_cast<int*>(p->valid_face.get(sizeof(int) * B));
-    fd_post(p->fd.get(), fdm.output_device(0), fdm.output_device(1), B, d_pad_det, reinterpret_cast<mi_detection*>(d_dets), cap, o.counts,
-            MI_MEM_DEVICE, s, d_roi_face, d_valid_face, width, height);
-    tr("fd_post");
-    it.rois = d_roi_face; it.roi_valid = d_valid_face; it.out_w = p->fl->in_w; it.out_h = p->fl->in_h; it.keep_aspect = 0;
+    return d_pad_det;
+}
+
+// The mesh and iris stages of a pass for N items whose face ROIs (and valid flags) are in device memory: item i reads frame i of `it`, or frame
+// it.item_frame[i] when that is set.  d_sizes: pipeline_sizes() of N items.
+static void pipeline_mesh_iris(mi_pipeline* p, mi::PreItems& it, int N, const mi::RectD* d_roi_face, const int* d_valid_face, const int* d_sizes, float* lm,
+                               int* present, float* eyes, bool one_shot, hipStream_t s, const PipeTrace& tr) {
+    mi::Model& flm = *p->fl->model.m;
+    mi::Model& irm = *p->iris->model.m;
+    const int width = it.width, height = it.height;
+    const long eye_fs = kEyeFs;
+    auto* d_geom = static_cast<mi::PreGeom*>(p->geom.get(sizeof(mi::PreGeom) * 2 * N));
+    // ---- 2. face -> face_detection_to_roi -> image_to_tensor(frame, roi, (192,192), false, (0,1)) -> mesh net
+    it.rois = d_roi_face; it.roi_valid = d_valid_face; it.items_per_frame = 1; it.N = N; it.out_w = p->fl->in_w; it.out_h = p->fl->in_h; it.keep_aspect = 0;
     it.range_min = 0.0; it.range_max = 1.0;
-    float* d_in_lm = static_cast<float*>(p->in_lm.get(flm.input_elems() * sizeof(float) * B));
+    float* d_in_lm = static_cast<float*>(p->in_lm.get(flm.input_elems() * sizeof(float) * N));
     mi::launch_pre_geom(it, d_geom, nullptr, s);
     mi::launch_pre_tensor(it, d_geom, d_in_lm, s);
     tr("pre mesh");
-    flm.run_device(d_in_lm, B, s, one_shot);
+    flm.run_device(d_in_lm, N, s, one_shot);
     tr("mesh run_device");
     {
         mi::ProjArgs a;
-        a.B = B; a.n = MI_NUM_FACE_LANDMARKS; a.tensor_w = p->fl->in_w; a.tensor_h = p->fl->in_h;
+        a.B = N; a.n = MI_NUM_FACE_LANDMARKS; a.tensor_w = p->fl->in_w; a.tensor_h = p->fl->in_h;
         a.roi = d_roi_face; a.image_size = d_sizes; a.gate = d_valid_face;
-        a.out = o.lm; a.present = o.present;
+        a.out = lm; a.present = present;
         project_mesh(flm, a, s);
     }
     // ---- 3. iris_roi_from_face_landmarks -> image_to_tensor(frame, eye roi, (64,64), true, (0,1), flip = right eye) -> iris net
-    auto* d_roi_eye = static_cast<mi::RectD*>(p->roi_eye.get(sizeof(mi::RectD) * 2 * B));
-    int* d_valid_eye = static_cast<int*>(p->valid_eye.get(sizeof(int) * 2 * B));
-    int* d_flip_eye = static_cast<int*>(p->flip_eye.get(sizeof(int) * 2 * B));
-    mi::launch_iris_rois(o.lm, o.present, B, width, height, d_roi_eye, d_valid_eye, d_flip_eye, s);
-    it.rois = d_roi_eye; it.roi_valid = d_valid_eye; it.flip = d_flip_eye; it.items_per_frame = 2; it.N = 2 * B;
+    auto* d_roi_eye = static_cast<mi::RectD*>(p->roi_eye.get(sizeof(mi::RectD) * 2 * N));
+    int* d_valid_eye = static_cast<int*>(p->valid_eye.get(sizeof(int) * 2 * N));
+    int* d_flip_eye = static_cast<int*>(p->flip_eye.get(sizeof(int) * 2 * N));
+    mi::launch_iris_rois(lm, present, N, width, height, d_roi_eye, d_valid_eye, d_flip_eye, s);
+    it.rois = d_roi_eye; it.roi_valid = d_valid_eye; it.flip = d_flip_eye; it.items_per_frame = 2; it.N = 2 * N;
     it.out_w = p->iris->in_w; it.out_h = p->iris->in_h; it.keep_aspect = 1;
-    double* d_pad_eye = static_cast<double*>(p->pad_eye.get(sizeof(double) * 8 * B));
-    float* d_in_eye = static_cast<float*>(p->in_eye.get(irm.input_elems() * sizeof(float) * 2 * B));
+    double* d_pad_eye = static_cast<double*>(p->pad_eye.get(sizeof(double) * 8 * N));
+    float* d_in_eye = static_cast<float*>(p->in_eye.get(irm.input_elems() * sizeof(float) * 2 * N));
     mi::launch_pre_geom(it, d_geom, d_pad_eye, s);
     mi::launch_pre_tensor(it, d_geom, d_in_eye, s);
     tr("pre iris");
-    irm.run_device(d_in_eye, 2 * B, s, one_shot);
+    irm.run_device(d_in_eye, 2 * N, s, one_shot);
     tr("iris run_device");
     {   // contour and iris landmarks of both eyes in one launch
         mi::ProjArgs a;
-        a.B = 2 * B; a.n = MI_NUM_EYE_LANDMARKS; a.n2 = MI_NUM_IRIS_LANDMARKS; a.tensor_w = p->iris->in_w; a.tensor_h = p->iris->in_h;
+        a.B = 2 * N; a.n = MI_NUM_EYE_LANDMARKS; a.n2 = MI_NUM_IRIS_LANDMARKS; a.tensor_w = p->iris->in_w; a.tensor_h = p->iris->in_h;
         a.roi = d_roi_eye; a.image_size = d_sizes; a.padding = d_pad_eye; a.flip = d_flip_eye; a.gate = d_valid_eye;
         a.raw = irm.output_device(0); a.raw_fs = static_cast<long>(irm.output_elems(0));
         a.raw2 = irm.output_device(1); a.raw2_fs = static_cast<long>(irm.output_elems(1));
-        a.out = o.eyes; a.out_fs = eye_fs;
-        a.out2 = o.eyes + 3 * MI_NUM_EYE_LANDMARKS; a.out2_fs = eye_fs;
+        a.out = eyes; a.out_fs = eye_fs;
+        a.out2 = eyes + 3 * MI_NUM_EYE_LANDMARKS; a.out2_fs = eye_fs;
         int rc = mi::launch_project(a, s);
         if (rc) throw std::runtime_error(std::string("projection kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
     }
-    // ---- top-1 faces out (strided gather [B][cap][17] -> [B][17])
     tr("projections");
+}
+
+// One pass of the flow of lib.rs:24-40 over B frames that are in device memory: everything is queued on `s`, nothing is waited for (but the
+// upload of the per-item image sizes when the batch geometry changes).  The caller holds the three handles (Use) and, for one_shot, the CUs.
+static void pipeline_enqueue(mi_pipeline* p, const uint8_t* d_frames, int B, int width, int height, int stride, const PipeOut& o, bool one_shot, hipStream_t s) {
+    mi::Model& fdm = *p->fd->model.m;
+    const int cap = kPipeCap;
+    const int* d_sizes = pipeline_sizes(p->sizes, p->sizes_B, p->sizes_w, p->sizes_h, B, width, height, s);
+    const PipeTrace tr;
+    // ---- 1. detector -> decode + NMS
+    mi::PreItems it{};
+    double* d_pad_det = pipeline_detect(p, it, d_frames, B, width, height, stride, one_shot, s, tr);
+    float* d_dets = static_cast<float*>(p->dets.get(sizeof(mi_detection) * cap * B));
+    // ---- 2. faces[0] -> face_detection_to_roi -> mesh, 3. both eyes -> iris
+    // (the post-processing launch writes zeros behind a frame's last detection — frames without a face report zeros — and faces[0]'s ROI)
+    auto* d_roi_face = static_cast<mi::RectD*>(p->roi_face.get(sizeof(mi::RectD) * B));
+    int* d_valid_face = static_cast<int*>(p->valid_face.get(sizeof(int) * B));
+    const FdPostPipeline top1{d_roi_face, d_valid_face, width, height};
+    fd_post(p->fd.get(), fdm.output_device(0), fdm.output_device(1), B, d_pad_det, reinterpret_cast<mi_detection*>(d_dets), cap, o.counts,
+            MI_MEM_DEVICE, s, &top1);
+    tr("fd_post");
+    pipeline_mesh_iris(p, it, B, d_roi_face, d_valid_face, d_sizes, o.lm, o.present, o.eyes, one_shot, s, tr);
+    // ---- top-1 faces out (strided gather [B][cap][17] -> [B][17])
     mi::hip_check(hipMemcpy2DAsync(o.faces, sizeof(mi_detection), d_dets, sizeof(mi_detection) * cap, sizeof(mi_detection), B,
                                    hipMemcpyDeviceToDevice, s), "gather faces");
     tr("gather");
@@ -1723,6 +1766,126 @@ int mi_pipeline_run(mi_pipeline* p, const uint8_t* frames, int batch, int width,
         };
         with_band_retry(claim && claim->ok, [&] { return pipeline_band_failed(p); }, network);
         if (mem == MI_MEM_HOST) pipeline_hand_out(p->out, L, B, faces, face_counts, landmarks, present, eyes);
+    });
+}
+
+// ---- every face of a frame (mi_pipeline_run_faces): the detector's first max_faces detections per frame, compacted on the device into a list of
+// max_items (frame, face) items (face_items.hpp), mesh and iris on exactly max_items / 2 * max_items items.  Batched plan only.
+namespace {
+struct FacesOut {   // DEVICE pointers of one pass
+    mi_detection* faces;   // [B][max_faces]
+    int* counts;           // [B]
+    int* item_frame;       // [M]
+    int* item_face;        // [M]
+    int* n_items;          // [2]
+    float* lm;             // [M][468][3]
+    int* present;          // [M]
+    float* eyes;           // [M][2][76][3]
+};
+struct FacesLayout {       // one block (host memory calls): faces | counts | item_frame | item_face | n_items | landmarks | present | eyes
+    size_t faces, counts, item_frame, item_face, n_items, lm, present, eyes, bytes;
+    FacesLayout(int B, int max_faces, int M) {
+        auto up16 = [](size_t v) { return (v + 15) & ~static_cast<size_t>(15); };
+        faces = 0;
+        counts = up16(faces + sizeof(mi_detection) * B * max_faces);
+        item_frame = up16(counts + sizeof(int) * B);
+        item_face = up16(item_frame + sizeof(int) * M);
+        n_items = up16(item_face + sizeof(int) * M);
+        lm = up16(n_items + sizeof(int) * 2);
+        present = up16(lm + sizeof(float) * 3 * MI_NUM_FACE_LANDMARKS * M);
+        eyes = up16(present + sizeof(int) * M);
+        bytes = up16(eyes + sizeof(float) * kEyeFs * 2 * M);
+    }
+    FacesOut in(char* base) const {
+        return FacesOut{reinterpret_cast<mi_detection*>(base + faces), reinterpret_cast<int*>(base + counts), reinterpret_cast<int*>(base + item_frame),
+                        reinterpret_cast<int*>(base + item_face), reinterpret_cast<int*>(base + n_items), reinterpret_cast<float*>(base + lm),
+                        reinterpret_cast<int*>(base + present), reinterpret_cast<float*>(base + eyes)};
+    }
+};
+void require_face_items(int batch, int max_faces, int max_items, int items_limit, const char* items_msg) {
+    require(batch > 0 && batch <= mi::kFaceItemsMaxBatch, "batch must be 1..2^26");
+    require(max_faces >= 1 && max_faces <= mi::kFaceItemsMaxFaces, "max_faces must be 1..16");
+    require(max_items >= 1 && max_items <= items_limit, items_msg);
+}
+}  // namespace
+
+int mi_face_items_layout(const int* face_counts, int batch, int max_faces, int max_items, int* item_frame, int* item_face, int* n_items) {
+    return guarded([&] {
+        require(face_counts && item_frame && item_face && n_items, "null argument");
+        require_face_items(batch, max_faces, max_items, mi::kFaceItemsMaxItems, "max_items must be 1..2^20");
+        int total = 0;
+        for (int b = 0; b < batch; b++) {
+            const int n = mi::face_items_of_frame(face_counts[b], max_faces);
+            for (int k = 0; k < n; k++) {
+                const int j = mi::face_items_slot(total, k, max_items);
+                if (j < 0) break;
+                item_frame[j] = b;
+                item_face[j] = k;
+            }
+            total += n;
+        }
+        mi::face_items_totals(total, max_items, n_items);
+        for (int j = n_items[0]; j < max_items; j++) item_frame[j] = item_face[j] = -1;
+    });
+}
+
+int mi_pipeline_run_faces(mi_pipeline* p, const uint8_t* frames, int batch, int width, int height, int stride, int max_faces, int max_items,
+                          mi_detection* faces, int* face_counts, int* item_frame, int* item_face, int* n_items, float* landmarks, int* present,
+                          float* eyes, int mem, void* stream) {
+    return guarded([&] {
+        // (a budget the launches cannot take is refused here, before anything is queued)
+        require_face_items(batch, max_faces, max_items, mi::kFaceItemsMaxRunItems, "max_items must be 1..32767 (2 * max_items eyes, one per grid row of a launch)");
+        require(p && frames && faces && face_counts && item_frame && item_face && n_items && landmarks && present && eyes, "null argument");
+        require(width > 0 && height > 0 && stride >= 3 * width, "bad frame geometry");
+        require(mem == MI_MEM_HOST || mem == MI_MEM_DEVICE, "mem must be MI_MEM_HOST or MI_MEM_DEVICE");
+        mi::Model& fdm = *p->fd->model.m;
+        mi::hip_check(hipSetDevice(fdm.device()), "hipSetDevice");
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fdm.stream();
+        Use use_fd(p->fd->model, s), use_fl(p->fl->model, s), use_ir(p->iris->model, s);  // the pipeline's own three handles, fixed order
+        const int B = batch, M = max_items;
+        const FacesLayout L(B, max_faces, M);
+        const uint8_t* d_frames = frames;
+        FacesOut o{faces, face_counts, item_frame, item_face, n_items, landmarks, present, eyes};
+        if (mem == MI_MEM_HOST) {
+            o = L.in(static_cast<char*>(p->results.get(L.bytes)));
+            p->out.reserve(L.bytes);
+            d_frames = static_cast<const uint8_t*>(p->frames.get(static_cast<size_t>(stride) * height * B));
+            mi::hip_check(hipMemcpyAsync(const_cast<uint8_t*>(d_frames), frames, frames_bytes(B, width, height, stride), hipMemcpyHostToDevice, s), "H2D frames");
+        }
+        const int* d_sizes = pipeline_sizes(p->sizes_item, p->sizes_item_N, p->sizes_item_w, p->sizes_item_h, M, width, height, s);
+        const PipeTrace tr;
+        // ---- 1. detector -> decode + NMS, max_faces records per frame straight into `faces` (zeros behind a frame's last detection)
+        mi::PreItems it{};
+        double* d_pad_det = pipeline_detect(p, it, d_frames, B, width, height, stride, false, s, tr);
+        const FdPostPipeline no_top1{};   // (the item kernel computes every face's ROI)
+        fd_post(p->fd.get(), fdm.output_device(0), fdm.output_device(1), B, d_pad_det, o.faces, max_faces, o.counts, MI_MEM_DEVICE, s, &no_top1);
+        tr("fd_post");
+        // ---- the item list: frame, face and face_detection_to_roi of every slot
+        mi::FaceItemsArgs fa{};
+        fa.dets = reinterpret_cast<const float*>(o.faces); fa.counts = o.counts;
+        fa.B = B; fa.max_faces = max_faces; fa.max_items = M; fa.image_w = width; fa.image_h = height;
+        fa.item_frame = o.item_frame; fa.item_face = o.item_face; fa.n_items = o.n_items;
+        fa.rois = static_cast<mi::RectD*>(p->roi_item.get(sizeof(mi::RectD) * M));
+        fa.valid = static_cast<int*>(p->valid_item.get(sizeof(int) * M));
+        mi::launch_face_items(fa, s);
+        tr("face items");
+        // ---- 2. every item's face -> mesh, 3. both eyes -> iris: item i reads frame item_frame[i]
+        it.item_frame = o.item_frame;
+        pipeline_mesh_iris(p, it, M, fa.rois, fa.valid, d_sizes, o.lm, o.present, o.eyes, false, s, tr);
+        if (mem == MI_MEM_HOST) mi::hip_check(hipMemcpyAsync(p->out.host, p->results.p, L.bytes, hipMemcpyDeviceToHost, s), "D2H results");
+        if (mem == MI_MEM_HOST || !stream) mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        if (mem == MI_MEM_HOST) {
+            const OneShot& h = p->out;
+            std::memcpy(faces, h.h<char>(L.faces), sizeof(mi_detection) * B * max_faces);
+            std::memcpy(face_counts, h.h<char>(L.counts), sizeof(int) * B);
+            std::memcpy(item_frame, h.h<char>(L.item_frame), sizeof(int) * M);
+            std::memcpy(item_face, h.h<char>(L.item_face), sizeof(int) * M);
+            std::memcpy(n_items, h.h<char>(L.n_items), sizeof(int) * 2);
+            std::memcpy(landmarks, h.h<char>(L.lm), sizeof(float) * 3 * MI_NUM_FACE_LANDMARKS * M);
+            std::memcpy(present, h.h<char>(L.present), sizeof(int) * M);
+            std::memcpy(eyes, h.h<char>(L.eyes), sizeof(float) * kEyeFs * 2 * M);
+            check_letterbox(face_counts, B);
+        }
     });
 }
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "face_items.hpp"
 #include "roi_dev.hpp"
 
 namespace mi {
@@ -284,7 +285,9 @@ __device__ __forceinline__ void pre_tensor_px(const PreItems& it, const PreGeom&
     const int y = idx / it.out_w, x = idx - y * it.out_w;
     float* o = out + ((long)i * it.out_h * it.out_w + idx) * 3;
     if (!g.valid) { o[0] = o[1] = o[2] = 0.f; return; }
-    const uint8_t* src = it.frames + (long)(i / it.items_per_frame) * it.frame_bytes;
+    // (behind the g.valid test: the frame of an unused slot of mi_pipeline_run_faces is -1)
+    const int slot = i / it.items_per_frame;
+    const uint8_t* src = it.frames + (long)(it.item_frame ? it.item_frame[slot] : slot) * it.frame_bytes;
     const int sx_out = flip ? it.out_w - 1 - x : x;   // cv::flip(…, 1) of the final image
     const int sw = it.width, sh = it.height, ss = it.stride;
     auto warped = [&](int yy, int xx) { return warp_px(g, src, sw, sh, ss, yy, xx); };
@@ -354,6 +357,55 @@ __global__ void iris_roi_kernel(const float* lm, const int* present, int B, int 
     flip[i] = eye;  // right eye is flipped (lib.rs:39)
 }
 
+// The item list of mi_pipeline_run_faces.  ONE workgroup: frames in chunks of 256, per chunk an exclusive scan of n_b (shuffles within a wave,
+// the four wave totals through LDS), the running sum carried from chunk to chunk in a register every lane holds.  No atomics: item j is
+// face k of frame b by arithmetic alone (face_items.hpp), so the order is the frames' and the detector's.
+constexpr int kFaceItemsThreads = 256;
+__global__ __launch_bounds__(kFaceItemsThreads) void face_items_kernel(FaceItemsArgs a) {
+    __shared__ int s_wave[kFaceItemsThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int total = 0;   // faces of the frames before this chunk (uniform)
+    for (int b0 = 0; b0 < a.B; b0 += kFaceItemsThreads) {
+        const int b = b0 + tid;
+        const int n = b < a.B ? face_items_of_frame(a.counts[b], a.max_faces) : 0;
+        int incl = n;   // inclusive scan within the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int before = 0, chunk = 0;
+#pragma unroll
+        for (int w = 0; w < kFaceItemsThreads / 64; w++) {
+            const int t = s_wave[w];
+            before += w < wave ? t : 0;
+            chunk += t;
+        }
+        __syncthreads();   // (s_wave is written again by the next chunk)
+        const int first = total + before + incl - n;
+        for (int k = 0; k < n; k++) {
+            const int j = face_items_slot(first, k, a.max_items);
+            if (j < 0) break;
+            RectD r;
+            a.valid[j] = face_roi_dev(a.dets + (long)b * a.max_faces * 17, n, a.image_w, a.image_h, &r, k);   // roi_dev.hpp
+            a.rois[j] = r;
+            a.item_frame[j] = b;
+            a.item_face[j] = k;
+        }
+        total += chunk;
+    }
+    int n_items[2];
+    face_items_totals(total, a.max_items, n_items);
+    for (int j = n_items[0] + tid; j < a.max_items; j += kFaceItemsThreads) {   // the unused slots
+        a.item_frame[j] = -1;
+        a.item_face[j] = -1;
+        a.valid[j] = 0;
+    }
+    if (tid == 0) { a.n_items[0] = n_items[0]; a.n_items[1] = n_items[1]; }
+}
+
 size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 }  // namespace
@@ -393,6 +445,11 @@ void launch_iris_rois(const float* d_landmarks, const int* d_present, int B, int
                       hipStream_t s) {
     hipLaunchKernelGGL(iris_roi_kernel, dim3((2 * B + 63) / 64), dim3(64), 0, s, d_landmarks, d_present, B, image_w, image_h, d_rois, d_valid, d_flip);
     hip_check(hipGetLastError(), "iris_roi kernel launch");
+}
+
+void launch_face_items(const FaceItemsArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(face_items_kernel, dim3(1), dim3(kFaceItemsThreads), 0, s, a);
+    hip_check(hipGetLastError(), "face_items kernel launch");
 }
 
 size_t image_to_tensor_scratch_bytes(int width, int height, int stride, const mi_rect*, int, int, bool) {

@@ -32,6 +32,8 @@ struct PreItems {               // batch description (device pointers unless sta
     const int* roi_valid;       // [N] or null
     const int* flip;            // [N] or null
     int items_per_frame;        // item i reads frame i / items_per_frame
+    const int* item_frame;      // [N / items_per_frame] or null: item i reads frame item_frame[i / items_per_frame] instead (mi_pipeline_run_faces:
+                                // several items per frame, compacted); a -1 entry belongs to an item whose roi_valid is 0 and is never used
     int N, out_w, out_h, keep_aspect;
     double range_min, range_max;
 };
@@ -64,5 +66,20 @@ void launch_face_rois(const float* d_dets /*[B][cap][17]*/, const int* d_counts,
                       RectD* d_rois, int* d_valid, hipStream_t s);
 void launch_iris_rois(const float* d_landmarks /*[B][468][3]*/, const int* d_present, int B, int image_w, int image_h,
                       RectD* d_rois /*[B][2] left,right*/, int* d_valid /*[B][2]*/, int* d_flip /*[B][2]*/, hipStream_t s);
+
+// The item list of mi_pipeline_run_faces (face_items.hpp states the rule), from what the detector's post-processing launch left in device memory:
+// one launch of one workgroup, no atomics.  Slot j < n_items[0] gets its frame, its face, face_detection_to_roi of that face and valid = 1 (0 for a
+// box that is not normalised); the slots behind get -1 / -1 / valid = 0 (their ROI is not written: every reader asks `valid` first).
+struct FaceItemsArgs {
+    const float* dets;      // [B][max_faces][17]
+    const int* counts;      // [B]
+    int B, max_faces, max_items, image_w, image_h;
+    int* item_frame;        // [max_items]
+    int* item_face;         // [max_items]
+    int* n_items;           // [2]
+    RectD* rois;            // [max_items]
+    int* valid;             // [max_items]
+};
+void launch_face_items(const FaceItemsArgs& a, hipStream_t s);
 
 }  // namespace mi

@@ -28,11 +28,13 @@ __device__ inline bool bbox_to_roi_dev(const double bbox[4], int image_w, int im
     return true;
 }
 
-// face_detection_to_roi of faces[0] (lib.rs:29, face_landmark.rs:30,189): d = the frame's first detection (17 floats), count = its detections
-__device__ inline int face_roi_dev(const float* d, int count, int image_w, int image_h, RectD* out) {
+// face_detection_to_roi of faces[k] (lib.rs:29, face_landmark.rs:30,189): d = the frame's first detection (records of 17 floats), count = its
+// detections; k = 0 is the top-1 flow, mi_pipeline_run_faces asks for every k below its max_faces
+__device__ inline int face_roi_dev(const float* d, int count, int image_w, int image_h, RectD* out, int k = 0) {
     RectD r = {0.5, 0.5, 1.0, 1.0, 0.0, 1, 0};
     int ok = 0;
-    if (count > 0) {  // Detection::scaled_by_image_size multiplies in f32 (types.rs:237-245)
+    d += 17 * k;
+    if (count > k) {  // Detection::scaled_by_image_size multiplies in f32 (types.rs:237-245)
         const float w = (float)image_w, h = (float)image_h;
         const double kp[4] = {(double)__fmul_rn(d[4], w), (double)__fmul_rn(d[5], h), (double)__fmul_rn(d[6], w), (double)__fmul_rn(d[7], h)};
         const double bbox[4] = {(double)d[0], (double)d[1], (double)d[2], (double)d[3]};
