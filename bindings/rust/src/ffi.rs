@@ -86,6 +86,18 @@ pub struct mi_render_style {
     pub eye_thickness: c_float,
 }
 
+/// `mi_render_style` plus the arguments of `iris_landmarks_to_render_data` — iris_landmark.rs:330-335
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mi_render_items_style {
+    pub base: mi_render_style,
+    pub draw_iris_oval: c_int,
+    pub iris_oval_color: mi_color,
+    pub draw_iris_points: c_int,
+    pub iris_landmark_color: mi_color,
+    pub iris_thickness: c_double,
+}
+
 #[repr(C)] pub struct mi_fd { _private: [u8; 0] }
 #[repr(C)] pub struct mi_fl { _private: [u8; 0] }
 #[repr(C)] pub struct mi_iris { _private: [u8; 0] }
@@ -183,4 +195,10 @@ extern "C" {
                            faces: *const mi_detection, face_counts: *const c_int, faces_per_frame: c_int, landmarks: *const c_float,
                            present: *const c_int, eyes: *const c_float, style: *const mi_render_style, out: *mut u8, out_channels: c_int,
                            out_stride: c_int, skipped: *mut c_int, mem: c_int, stream: *mut c_void) -> c_int;
+    // ... for the item list of mi_pipeline_run_faces: every face of a frame, with both irises (iris_landmark.rs:330-377)
+    pub fn mi_render_face_items(device: c_int, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,
+                                faces: *const mi_detection, face_counts: *const c_int, max_faces: c_int, item_frame: *const c_int,
+                                n_items: *const c_int, max_items: c_int, landmarks: *const c_float, present: *const c_int,
+                                eyes: *const c_float, style: *const mi_render_items_style, out: *mut u8, out_channels: c_int,
+                                out_stride: c_int, skipped: *mut c_int, mem: c_int, stream: *mut c_void) -> c_int;
 }

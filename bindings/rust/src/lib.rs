@@ -24,7 +24,10 @@ pub mod utils;
 
 pub use face_detection::{FaceDetection, FaceDetectionModel};
 pub use face_landmark::{face_detection_to_roi, FaceLandmark};
-pub use render::{detections_to_render_data, landmarks_to_render_data, render_to_image, Annotation, AnnotationData, Color, Colors};
+pub use render::{
+    detections_to_render_data, iris_landmarks_to_render_data, landmarks_to_render_data, render_face_items, render_to_image, Annotation,
+    AnnotationData, Color, Colors, FaceItems,
+};
 pub use iris_landmark::{iris_roi_from_face_landmarks, update_face_landmarks_with_iris_results, IrisLandmark};
 pub use pipeline::{face_items_layout, FacesResults, Pipeline};
 pub use types::{BBox, Detection, Image, IrisResults, Landmark, Rect};

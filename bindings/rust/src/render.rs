@@ -8,7 +8,9 @@
 //! changes — which keeps the reference's drawing order item for item.  Deviations from the reference (both reported by the C
 //! entry's `skipped` count, returned here next to the picture): empty rectangles are not drawn instead of panicking, and lines
 //! with an end point beyond 2^20 px are not drawn instead of being walked for up to 2^32 steps.
-//! A caller whose results are already in device memory uses `ffi::mi_render_faces` and never builds annotations at all.
+//! A caller whose results are already in device memory uses `ffi::mi_render_faces` and never builds annotations at all;
+//! `render_face_items` draws the item list of `mi_pipeline_run_faces` (every face of a frame, both irises included) the same way
+//! from host memory, and `iris_landmarks_to_render_data` (iris_landmark.rs:330-377) is the host builder of the iris annotations.
 use crate::ffi;
 use crate::types::{Detection, Image, Landmark};
 use anyhow::Error;
@@ -279,4 +281,113 @@ where
         )
     })?;
     Ok(RgbaImage { data: out, width: w, height: h, skipped })
+}
+
+/// iris_landmark.rs:330-377: the oval annotation (when `oval_color` is given; needs an image of at least 2 x 2), then the points
+/// annotation (when `landmark_color` is given), both normalised and of `thickness` (1.0 when None).
+pub fn iris_landmarks_to_render_data(
+    iris_landmarks: Vec<Landmark>, landmark_color: Option<Color>, oval_color: Option<Color>, thickness: Option<f64>,
+    image_size: Option<(i32, i32)>, output: Option<Vec<Annotation>>,
+) -> Result<Vec<Annotation>, Error> {
+    let thickness = thickness.unwrap_or(1.0);
+    let (w, h) = image_size.unwrap_or((-1, -1));
+    let mut out = output.unwrap_or_default();
+    if let Some(color) = oval_color {
+        if w < 2 || h < 2 {
+            return Err(Error::msg("oval_color requires a valid image_size arg"));
+        }
+        let (wf, hf) = (w as f64, h as f64);
+        // IrisIndex: Center 0, Left 1, Top 2, Right 3, Bottom 4; get_iris_diameter (iris_landmark.rs:401-418) in pixels
+        let span = |a: usize, b: usize| -> f64 {
+            let (p, q) = (&iris_landmarks[a], &iris_landmarks[b]);
+            let (dx, dy) = (p.x * wf - q.x * wf, p.y * hf - q.y * hf);
+            (dx * dx + dy * dy).sqrt()
+        };
+        let radius = (span(2, 4) + span(1, 3)) / 2. / 2.0;
+        let (rh, rv) = (radius / wf, radius / hf);
+        let c = &iris_landmarks[0];
+        let oval = RectOrOval::new(c.x - rh, c.y - rv, c.x + rh, c.y + rv, true);
+        out.push(Annotation::new(vec![AnnotationData::RectOrOval(oval)], true, thickness, color));
+    }
+    if let Some(color) = landmark_color {
+        let points = iris_landmarks.iter().map(|l| AnnotationData::Point(Point::new(l.x, l.y))).collect();
+        out.push(Annotation::new(points, true, thickness, color));
+    }
+    Ok(out)
+}
+
+/// The item list of `mi_pipeline_run_faces`, in host memory, as `render_face_items` reads it (include/mi_face.h).  Every group may be left
+/// out, as the C entry allows: `faces` (with its counts and `max_faces`), the item list itself, and `landmarks`, `present`, `eyes` inside it.
+pub struct FaceItems<'a> {
+    /// (faces [batch][max_faces], face_counts [batch], max_faces 1..16)
+    pub faces: Option<(&'a [ffi::mi_detection], &'a [i32], i32)>,
+    /// (item_frame [max_items], n_items: the slots used first)
+    pub items: Option<(&'a [i32], &'a [i32])>,
+    /// f32 [max_items][468][3]
+    pub landmarks: Option<&'a [f32]>,
+    /// [max_items]; None: every used slot is drawn
+    pub present: Option<&'a [i32]>,
+    /// f32 [max_items][2][76][3]
+    pub eyes: Option<&'a [f32]>,
+}
+
+fn ptr_or_null<T>(s: Option<&[T]>) -> *const T {
+    s.map_or(std::ptr::null(), |s| s.as_ptr())
+}
+
+/// `mi_render_face_items` on device 0 for `batch` tightly packed RGB frames in host memory: boxes and key points of every frame,
+/// then mesh, eyes and irises of every item of the frame.  Returns one RGBA picture per frame.
+pub fn render_face_items(
+    frames: &[u8], batch: i32, width: i32, height: i32, items: &FaceItems, style: &ffi::mi_render_items_style,
+) -> Result<Vec<RgbaImage>, Error> {
+    if batch < 1 || width < 1 || height < 1 {
+        return Err(Error::msg("batch, width and height must be positive"));
+    }
+    let b = batch as usize;
+    let frame_bytes = 3 * width as usize * height as usize;
+    if frames.len() < b * frame_bytes {
+        return Err(Error::msg("frames must hold batch tightly packed RGB pictures"));
+    }
+    let max_faces = match items.faces {
+        Some((faces, counts, f)) => {
+            if !(1..=16).contains(&f) || faces.len() < b * f as usize || counts.len() < b {
+                return Err(Error::msg("faces need max_faces in 1..16, batch * max_faces detections and batch counts"));
+            }
+            f
+        }
+        None => 1,
+    };
+    // the size every per-item array must have; 1 (and unused) without an item list
+    let m = match items.items {
+        Some((item_frame, n_items)) => {
+            if item_frame.is_empty() || item_frame.len() > 32767 || n_items.is_empty() {
+                return Err(Error::msg("item_frame must hold 1..32767 slots and n_items at least the count of used slots"));
+            }
+            item_frame.len()
+        }
+        None => {
+            if items.landmarks.is_some() || items.eyes.is_some() {
+                return Err(Error::msg("landmarks and eyes need the item list"));
+            }
+            1
+        }
+    };
+    let short = |s: Option<usize>, need: usize| s.map_or(false, |len| len < need);
+    if short(items.landmarks.map(|s| s.len()), m * 468 * 3) || short(items.eyes.map(|s| s.len()), m * 2 * 76 * 3)
+        || short(items.present.map(|s| s.len()), m)
+    {
+        return Err(Error::msg("an item array is shorter than max_items items"));
+    }
+    let out_bytes = 4 * width as usize * height as usize;
+    let mut out = vec![0u8; b * out_bytes];
+    let mut skipped = vec![0i32; b];
+    crate::check(unsafe {
+        ffi::mi_render_face_items(
+            0, frames.as_ptr(), batch, width, height, 3 * width, ptr_or_null(items.faces.map(|f| f.0)), ptr_or_null(items.faces.map(|f| f.1)),
+            max_faces, ptr_or_null(items.items.map(|i| i.0)), ptr_or_null(items.items.map(|i| i.1)), m as i32, ptr_or_null(items.landmarks),
+            ptr_or_null(items.items.and(items.present)), ptr_or_null(items.eyes), style, out.as_mut_ptr(), 4, 4 * width, skipped.as_mut_ptr(),
+            ffi::MI_MEM_HOST, std::ptr::null_mut(),
+        )
+    })?;
+    Ok(out.chunks(out_bytes).zip(skipped).map(|(px, s)| RgbaImage { data: px.to_vec(), width, height, skipped: s }).collect())
 }

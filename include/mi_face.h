@@ -481,6 +481,53 @@ int mi_render_faces(int device, const uint8_t *frames, int batch, int width, int
                     const mi_render_style *style, uint8_t *out, int out_channels, int out_stride, int *skipped, int mem,
                     void *stream);
 
+/* mi_render_style plus the arguments of iris_landmarks_to_render_data (iris_landmark.rs:330-377): draw_iris_oval = 0 / draw_iris_points = 0 are
+ * the reference's `None` for oval_color / landmark_color (:331,339,358); iris_thickness is its Option<f64>, 1.0 when None (:335).  `base` is
+ * read exactly as mi_render_faces reads its style. */
+typedef struct mi_render_items_style {
+    mi_render_style base;
+    int draw_iris_oval;
+    mi_color iris_oval_color;
+    int draw_iris_points;
+    mi_color iris_landmark_color;
+    double iris_thickness;
+} mi_render_items_style;
+
+/* The drawing of mi_render_faces for what mi_pipeline_run_faces left in memory: EVERY face of a frame with its mesh, both eyes and both
+ * irises — detections_to_render_data, then per face face_landmarks_to_render_data + 2 x eye_landmarks_to_render_data + 2 x
+ * iris_landmarks_to_render_data (lib.rs:10,42-83), then render_to_image; with MI_MEM_DEVICE no coordinate and no count visits the host.
+ * Canvas arguments, out_channels 3 or 4, the in-place rule (out may BE frames with out_channels 3 and out_stride == stride; any other overlap
+ * is MI_EINVAL), the drawing rules, skipped[batch] (may be NULL) and the two deviations counted in it (a rectangle whose of_size width or
+ * height is 0 is not drawn; a line's walk is bounded by the canvas and a line or hollow rectangle with |coordinate| > 2^20 after the i32 cast
+ * is not drawn) are those of mi_render_annotations.
+ *   faces       [batch][max_faces] + face_counts [batch], max_faces 1..16: exactly as faces / face_counts / faces_per_frame of mi_render_faces.
+ *               The three may be NULL / NULL / anything together.
+ *   item_frame  [max_items] and n_items as mi_pipeline_run_faces / mi_face_items_layout write them (max_items 1..32767); only n_items[0] is
+ *               read.  The used slots are the first clamp(n_items[0], 0, max_items), their frame indices non-decreasing.  Frame b draws the
+ *               contiguous run of slots [lower_bound(b), lower_bound(b + 1)) of that prefix (the halving search for the first slot whose frame
+ *               is not below its argument), in ascending slot order.  item_frame values are only ever compared, never used as an address: a
+ *               list that breaks the ordering draws some subset of its items (a slot inside a frame's run is drawn only where its frame IS
+ *               that frame) and never reads or writes outside the arrays' stated sizes.
+ *   landmarks   f32 [max_items][468][3], eyes f32 [max_items][2][76][3] (71 contour rows, then the 5 iris rows: Center, Left, Top, Right,
+ *               Bottom — IrisIndex), present [max_items]: item j is drawn only where present[j] != 0; present NULL: every used slot.
+ *               landmarks and eyes may each be NULL; either of them without item_frame and n_items is MI_EINVAL.
+ * The annotation list of frame b, in this order (all positions normalised, f32 widened to f64 before the multiply, every cast Rust's `as`):
+ *   1. the bounds annotation, then the keypoints annotation of the frame's faces, as mi_render_faces;
+ *   2. for each item of the frame, in slot order, each group gated by its draw_* flag: mesh lines, mesh points; left-eye lines, points;
+ *      right-eye lines, points; left iris oval, left iris points; right iris oval, right iris points.
+ *   iris oval   iris_landmark.rs:339-356 with get_iris_diameter (:401-418), in f64, W = width, H = height:
+ *               d(a, b) = sqrt((ax*W - bx*W)^2 + (ay*H - by*H)^2); radius = (d(Top, Bottom) + d(Left, Right)) / 2 / 2; radius_h = radius / W,
+ *               radius_v = radius / H; one RectOrOval(cx - radius_h, cy - radius_v, cx + radius_h, cy + radius_v), normalised, thickness
+ *               iris_thickness, drawn as render_to_image draws an oval: the hollow rectangle (render.rs:446-462).  The divide by W and the
+ *               later multiply by W are both done, as in the reference (two roundings).  draw_iris_oval with width < 2 or height < 2 is
+ *               MI_EINVAL (the reference's Err, :342-344).
+ *   iris points the five iris landmarks as one points annotation (:358-369), thickness iris_thickness: half = max(thickness as u32 / 2, 1).
+ * With MI_MEM_DEVICE and a caller stream the call is asynchronous; MI_MEM_HOST stages its operands as mi_render_faces does. */
+int mi_render_face_items(int device, const uint8_t *frames, int batch, int width, int height, int stride, const mi_detection *faces,
+                         const int *face_counts, int max_faces, const int *item_frame, const int *n_items, int max_items,
+                         const float *landmarks, const int *present, const float *eyes, const mi_render_items_style *style, uint8_t *out,
+                         int out_channels, int out_stride, int *skipped, int mem, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU: the one exchange of the sharded path — the frozen .tflite bytes go once from `root` to
  * every rank over RCCL (ncclBroadcast, ncclUint8, xGMI inside a node); every rank then builds its handles with

@@ -422,5 +422,15 @@ inline void render_faces(const std::uint8_t* frames, int batch, int width, int h
     detail::check(mi_render_faces(device, frames, batch, width, height, stride, faces, face_counts, faces_per_frame, landmarks, present, eyes, &style,
                                   out, out_channels, out_stride, skipped, mem, stream));
 }
+// The same for the item list of mi_pipeline_run_faces: every face of a frame with its mesh, both eyes and both irises
+// (iris_landmarks_to_render_data, iris_landmark.rs:330-377).  faces / face_counts, landmarks, present and eyes may be null.
+inline void render_face_items(const std::uint8_t* frames, int batch, int width, int height, int stride, const mi_detection* faces,
+                              const int* face_counts, int max_faces, const int* item_frame, const int* n_items, int max_items,
+                              const float* landmarks, const int* present, const float* eyes, const mi_render_items_style& style, std::uint8_t* out,
+                              int out_channels, int out_stride, int* skipped = nullptr, int mem = MI_MEM_HOST, void* stream = nullptr,
+                              int device = 0) {
+    detail::check(mi_render_face_items(device, frames, batch, width, height, stride, faces, face_counts, max_faces, item_frame, n_items, max_items,
+                                       landmarks, present, eyes, &style, out, out_channels, out_stride, skipped, mem, stream));
+}
 
 }  // namespace mi_face

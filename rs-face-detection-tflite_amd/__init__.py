@@ -10,4 +10,5 @@ from .api import (  # noqa: F401
     FaceLandmark, IrisLandmark, IrisResults, Landmark, MiError, Model, PinnedBuffer, Pipeline, Rect, device_count, face_detection_to_roi, face_items_layout,
     bbox_from_landmarks, bbox_to_roi, convert_image_to_mat, image_to_tensor, iris_roi_from_face_landmarks, jpeg_info, lib, plan_describe, dist_broadcast_bytes, streams_create_distinct, streams_destroy, update_face_landmarks_with_iris_results,
     ANN_FILLED_RECTS, ANN_LINES, ANN_POINTS, ANN_RECTS, Annotation, Color, Colors, RenderStyle, render_annotations, render_faces,
+    RenderItemsStyle, render_face_items,
 )

@@ -41,7 +41,7 @@ EXPORTS = [
     "mi_pipeline_create", "mi_pipeline_create_from_bytes", "mi_pipeline_model", "mi_pipeline_free", "mi_pipeline_set_option", "mi_pipeline_run",
     "mi_pipeline_run_faces", "mi_face_items_layout",
     "mi_bbox_to_roi", "mi_bbox_from_landmarks", "mi_face_detection_to_roi", "mi_iris_roi_from_face_landmarks", "mi_update_face_landmarks_with_iris_results", "mi_image_to_tensor", "mi_jpeg_info", "mi_jpeg_decode_rgb",
-    "mi_render_annotations", "mi_render_faces",
+    "mi_render_annotations", "mi_render_faces", "mi_render_face_items",
 ]
 
 
@@ -121,6 +121,18 @@ class RenderStyle(C.Structure):
                          int(keypoint_color is not None), keypoint_color or Colors.BLACK, int(point_width),
                          int(bool(mesh)), red(mesh_landmark_color), red(mesh_connection_color), float(mesh_thickness),
                          int(bool(eyes)), red(eye_landmark_color), red(eye_connection_color), float(eye_thickness))
+
+
+class RenderItemsStyle(C.Structure):
+    """mi_render_items_style: a RenderStyle (`base`, read as render_faces reads it) plus the arguments of iris_landmarks_to_render_data
+    (iris_landmark.rs:330-335).  A colour of None is the reference's None: that group is not drawn.  iris_thickness None is its default, 1.0."""
+    _fields_ = [("base", RenderStyle), ("draw_iris_oval", C.c_int), ("iris_oval_color", Color),
+                ("draw_iris_points", C.c_int), ("iris_landmark_color", Color), ("iris_thickness", C.c_double)]
+
+    def __init__(self, base=None, iris_oval_color=None, iris_landmark_color=None, iris_thickness=None):
+        super().__init__(base if base is not None else RenderStyle(), int(iris_oval_color is not None), iris_oval_color or Colors.BLACK,
+                         int(iris_landmark_color is not None), iris_landmark_color or Colors.BLACK,
+                         1.0 if iris_thickness is None else float(iris_thickness))
 
 
 class FaceDetectionModel(enum.IntEnum):
@@ -309,6 +321,8 @@ def lib():
                                         C.c_int, vp, C.c_int, vp]
     L.mi_render_faces.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.POINTER(RenderStyle), vp, C.c_int,
                                   C.c_int, vp, C.c_int, vp]
+    L.mi_render_face_items.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp,
+                                       C.POINTER(RenderItemsStyle), vp, C.c_int, C.c_int, vp, C.c_int, vp]
     _lib = L
     return L
 
@@ -1097,6 +1111,51 @@ def render_faces(frames, faces=None, face_counts=None, landmarks=None, present=N
     skipped = _skipped_buffer(mem, B, frames)
     _check(lib().mi_render_faces(device, p, B, W, H, stride, pf, pn, per_frame, pl, pp, pe, C.byref(style), po, out_channels, ostride,
                                  _ptr(skipped)[0], mem, C.c_void_p(stream or 0)))
+    return out, skipped
+
+
+def render_face_items(frames, result, style=None, out=None, out_channels=4, device=0, stream=None):
+    """mi_render_face_items: draws what Pipeline.run_faces returned — `result` is its dict, numpy arrays or CUDA tensors, in the memory of the
+    frames: faces [B,F,17] + face_counts [B] (boxes and key points of every frame), then for every item of a frame its mesh, both eyes and both
+    irises (iris_landmarks_to_render_data, iris_landmark.rs:330-377) from item_frame [M], counts [2] (only counts[0], the slots used, is read —
+    on the device), landmarks [M,468,3], present [M] and eyes [M,2,76,3].  Keys that are missing or None leave their group out.  style:
+    RenderItemsStyle.  With CUDA tensors no coordinate or count visits the host, and with a caller stream the call is asynchronous.
+    -> (out, skipped int32 [B])."""
+    p, mem, B, H, W, stride = _picture(frames, 3, "frames")
+    if mem == MI_MEM_DEVICE:
+        _device_ready(frames, device, None, "uint8")
+    out, po, ostride = _render_out(frames, mem, B, H, W, out, out_channels)
+    get = lambda k: result.get(k) if result is not None else None
+    faces, face_counts, item_frame, counts = get("faces"), get("face_counts"), get("item_frame"), get("counts")
+    landmarks, present, eyes = get("landmarks"), get("present"), get("eyes")
+    shape = lambda x: tuple(int(v) for v in x.shape)
+    F = 1
+    if faces is not None:
+        if faces.ndim != 3 or shape(faces)[0] != B or shape(faces)[2] != 17 or face_counts is None:
+            raise ValueError("faces must be [B,F,17] and come with face_counts [B]")
+        F = shape(faces)[1]
+    M = 1
+    if item_frame is not None:
+        if item_frame.ndim != 1 or counts is None or counts.ndim != 1 or shape(counts)[0] < 1:
+            raise ValueError("item_frame must be [M] and come with counts [2] (the slots used first)")
+        M = shape(item_frame)[0]
+    elif landmarks is not None or eyes is not None:
+        raise ValueError("landmarks and eyes need item_frame and counts")
+    for x, want, what in ((landmarks, (M, NUM_FACE_LANDMARKS, 3), "landmarks"), (eyes, (M, 2, NUM_EYE_LANDMARKS + NUM_IRIS_LANDMARKS, 3), "eyes"),
+                          (face_counts, (B,), "face_counts"), (present, (M,), "present")):
+        if x is not None and shape(x) != want:
+            raise ValueError("%s must have shape %s" % (what, list(want)))
+    pf, faces = _render_operand(faces, mem, device, "float32", "faces")
+    pn, face_counts = _render_operand(face_counts if faces is not None else None, mem, device, "int32", "face_counts")
+    pi, item_frame = _render_operand(item_frame, mem, device, "int32", "item_frame")
+    pc, counts = _render_operand(counts if item_frame is not None else None, mem, device, "int32", "counts")
+    pl, landmarks = _render_operand(landmarks, mem, device, "float32", "landmarks")
+    pp, present = _render_operand(present if item_frame is not None else None, mem, device, "int32", "present")
+    pe, eyes = _render_operand(eyes, mem, device, "float32", "eyes")
+    style = style if style is not None else RenderItemsStyle()
+    skipped = _skipped_buffer(mem, B, frames)
+    _check(lib().mi_render_face_items(device, p, B, W, H, stride, pf, pn, F, pi, pc, M, pl, pp, pe, C.byref(style), po, out_channels, ostride,
+                                      _ptr(skipped)[0], mem, C.c_void_p(stream or 0)))
     return out, skipped
 
 

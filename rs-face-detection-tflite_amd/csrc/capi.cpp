@@ -2406,4 +2406,41 @@ int mi_render_faces(int device, const uint8_t* frames, int batch, int width, int
     });
 }
 
+int mi_render_face_items(int device, const uint8_t* frames, int batch, int width, int height, int stride, const mi_detection* faces,
+                         const int* face_counts, int max_faces, const int* item_frame, const int* n_items, int max_items, const float* landmarks,
+                         const int* present, const float* eyes, const mi_render_items_style* style, uint8_t* out, int out_channels, int out_stride,
+                         int* skipped, int mem, void* stream) {
+    return guarded([&] {
+        render_check_canvas(frames, batch, width, height, stride, out, out_channels, out_stride, mem);
+        require(style, "null argument");
+        require(!faces || (face_counts && max_faces >= 1 && max_faces <= 16), "faces need face_counts and max_faces in 1..16");
+        require(max_items >= 1 && max_items <= 32767, "max_items must be 1..32767");
+        require((item_frame != nullptr) == (n_items != nullptr), "item_frame and n_items come together");
+        require(item_frame || !(landmarks || eyes), "landmarks and eyes need item_frame and n_items");
+        // iris_landmark.rs:342-344: "oval_color requires a valid image_size arg"
+        require(!style->draw_iris_oval || (width >= 2 && height >= 2), "draw_iris_oval needs width >= 2 and height >= 2");
+        DeviceBuf b_faces, b_counts, b_item_frame, b_n_items, b_landmarks, b_present, b_eyes;
+        render_run(device, frames, batch, width, height, stride, out, out_channels, out_stride, skipped, mem, stream, false,
+                   [&](const mi::RenderCanvas& cv, int* d_skipped, hipStream_t s) {
+                       auto staged = [&](DeviceBuf& buf, const void* p, size_t bytes) -> const void* {
+                           if (!p || mem == MI_MEM_DEVICE) return p;
+                           void* d = buf.get(bytes);
+                           mi::hip_check(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, s), "H2D results");
+                           return d;
+                       };
+                       const size_t B = static_cast<size_t>(batch), M = static_cast<size_t>(max_items);
+                       auto* d_faces = static_cast<const mi_detection*>(staged(b_faces, faces, sizeof(mi_detection) * B * (faces ? max_faces : 0)));
+                       auto* d_counts = static_cast<const int*>(staged(b_counts, faces ? face_counts : nullptr, sizeof(int) * B));
+                       auto* d_item_frame = static_cast<const int*>(staged(b_item_frame, item_frame, sizeof(int) * M));
+                       auto* d_n_items = static_cast<const int*>(staged(b_n_items, n_items, sizeof(int)));
+                       auto* d_landmarks = static_cast<const float*>(staged(b_landmarks, landmarks, sizeof(float) * M * MI_NUM_FACE_LANDMARKS * 3));
+                       auto* d_present = static_cast<const int*>(staged(b_present, item_frame ? present : nullptr, sizeof(int) * M));
+                       auto* d_eyes = static_cast<const float*>(staged(b_eyes, eyes, sizeof(float) * M * 2 * (MI_NUM_EYE_LANDMARKS + MI_NUM_IRIS_LANDMARKS) * 3));
+                       hipError_t e = mi::launch_render_face_items(cv, d_faces, d_counts, max_faces, d_item_frame, d_n_items, max_items, d_landmarks,
+                                                                   d_present, d_eyes, *style, d_skipped, s);
+                       if (e != hipSuccess) throw std::runtime_error(std::string("render kernel launch failed: ") + hipGetErrorString(e));
+                   });
+    });
+}
+
 }  // extern "C"

@@ -30,5 +30,11 @@ hipError_t launch_render_annotations(const RenderCanvas& cv, const mi_annotation
 hipError_t launch_render_faces(const RenderCanvas& cv, const mi_detection* d_faces, const int* d_face_counts, int faces_per_frame,
                                const float* d_landmarks, const int* d_present, const float* d_eyes, const mi_render_style& style,
                                int* d_skipped, hipStream_t s);
+// Draw phase of mi_render_face_items: the frame's detections, then the mesh, eyes and irises of every item of the frame (the run of the frame's
+// index in d_item_frame[0, clamp(d_n_items[0], 0, max_items)), found on the device).  d_faces with d_face_counts, d_item_frame with d_n_items,
+// d_landmarks, d_present and d_eyes may be null.
+hipError_t launch_render_face_items(const RenderCanvas& cv, const mi_detection* d_faces, const int* d_face_counts, int max_faces,
+                                    const int* d_item_frame, const int* d_n_items, int max_items, const float* d_landmarks, const int* d_present,
+                                    const float* d_eyes, const mi_render_items_style& style, int* d_skipped, hipStream_t s);
 
 }  // namespace mi

@@ -327,6 +327,43 @@ __global__ __launch_bounds__(kDrawThreads) void render_annotations_kernel(Render
     store_skipped(skipped, b, mine);
 }
 
+// detections_to_render_data (render.rs:262-313) for the n faces at `d`: the bounds annotation, then the keypoints annotation.  (sx, sy) = the
+// canvas size.  Returns what was not drawn.
+__device__ __forceinline__ int detection_groups(const Frame& f, const mi_detection* d, int n, double sx, double sy, const mi_render_style& st) {
+    int mine = 0;
+    if (st.draw_bounds && st.line_width > 0) {
+        // Detection::bbox (types.rs:219-225): data[0] = (xmin, ymin), data[1] = (xmax, ymax), widened to f64
+        mine += draw_rects(f, n, false, pack(st.bounds_color), [=](int i) {
+            const float* v = d[i].data;
+            return P4{static_cast<double>(v[0]) * sx, static_cast<double>(v[1]) * sy, static_cast<double>(v[2]) * sx, static_cast<double>(v[3]) * sy};
+        });
+        next_annotation();
+    }
+    if (st.draw_keypoints && st.point_width > 0) {
+        draw_points(f, 8 * n, static_cast<double>(st.point_width), pack(st.keypoint_color), [=](int i) {
+            const float* v = d[i >> 3].data + 2 * (i & 7);  // every row of `data`, the box corners included (render.rs:289-299)
+            return P2{static_cast<double>(v[0]) * sx, static_cast<double>(v[1]) * sy};
+        });
+        next_annotation();
+    }
+    return mine;
+}
+
+// landmarks_to_render_data (render.rs:315-359) over rows of (x, y, z) f32: the lines annotation, then the points annotation; thickness f32 -> f64.
+// What was not drawn is added to `mine`.
+__device__ __forceinline__ void landmark_group(const Frame& f, double sx, double sy, int& mine, const float* lm, int n_points, int n_lines, bool face,
+                                               double thickness, mi_color line_color, mi_color point_color) {
+    mine += draw_lines(f, n_lines, pack(line_color), [=](int i) {
+        const int s = face ? kFaceConnections[i][0] : kEyeConnections[i][0], e = face ? kFaceConnections[i][1] : kEyeConnections[i][1];
+        return P4{static_cast<double>(lm[3 * s]) * sx, static_cast<double>(lm[3 * s + 1]) * sy, static_cast<double>(lm[3 * e]) * sx,
+                  static_cast<double>(lm[3 * e + 1]) * sy};
+    });
+    next_annotation();
+    draw_points(f, n_points, thickness, pack(point_color),
+                [=](int i) { return P2{static_cast<double>(lm[3 * i]) * sx, static_cast<double>(lm[3 * i + 1]) * sy}; });
+    next_annotation();
+}
+
 __global__ __launch_bounds__(kDrawThreads) void render_faces_kernel(RenderCanvas cv, const mi_detection* faces, const int* face_counts,
                                                                     int faces_per_frame, const float* landmarks, const int* present,
                                                                     const float* eyes, mi_render_style st, int* skipped) {
@@ -334,46 +371,98 @@ __global__ __launch_bounds__(kDrawThreads) void render_faces_kernel(RenderCanvas
     const Frame f = frame_of(cv, b);
     const double sx = cv.width, sy = cv.height;
     int mine = 0;
-    if (faces) {  // detections_to_render_data, render.rs:262-313
+    if (faces) {
         int n = face_counts[b];
         n = n < 0 ? 0 : (n > faces_per_frame ? faces_per_frame : n);
-        const mi_detection* d = faces + static_cast<long>(b) * faces_per_frame;
-        if (st.draw_bounds && st.line_width > 0) {
-            // Detection::bbox (types.rs:219-225): data[0] = (xmin, ymin), data[1] = (xmax, ymax), widened to f64
-            mine += draw_rects(f, n, false, pack(st.bounds_color), [=](int i) {
-                const float* v = d[i].data;
-                return P4{static_cast<double>(v[0]) * sx, static_cast<double>(v[1]) * sy, static_cast<double>(v[2]) * sx, static_cast<double>(v[3]) * sy};
-            });
-            next_annotation();
-        }
-        if (st.draw_keypoints && st.point_width > 0) {
-            draw_points(f, 8 * n, static_cast<double>(st.point_width), pack(st.keypoint_color), [=](int i) {
-                const float* v = d[i >> 3].data + 2 * (i & 7);  // every row of `data`, the box corners included (render.rs:289-299)
-                return P2{static_cast<double>(v[0]) * sx, static_cast<double>(v[1]) * sy};
-            });
-            next_annotation();
-        }
+        mine += detection_groups(f, faces + static_cast<long>(b) * faces_per_frame, n, sx, sy, st);
     }
     const bool there = present ? present[b] != 0 : true;
-    // landmarks_to_render_data (render.rs:315-359): the lines annotation, then the points annotation; thickness f32 -> f64
-    auto landmark_group = [&](const float* lm, int n_points, int n_lines, bool face, double thickness, mi_color line_color, mi_color point_color) {
-        mine += draw_lines(f, n_lines, pack(line_color), [=](int i) {
-            const int s = face ? kFaceConnections[i][0] : kEyeConnections[i][0], e = face ? kFaceConnections[i][1] : kEyeConnections[i][1];
-            return P4{static_cast<double>(lm[3 * s]) * sx, static_cast<double>(lm[3 * s + 1]) * sy, static_cast<double>(lm[3 * e]) * sx,
-                      static_cast<double>(lm[3 * e + 1]) * sy};
-        });
-        next_annotation();
-        draw_points(f, n_points, thickness, pack(point_color),
-                    [=](int i) { return P2{static_cast<double>(lm[3 * i]) * sx, static_cast<double>(lm[3 * i + 1]) * sy}; });
-        next_annotation();
-    };
     if (landmarks && st.draw_mesh && there)  // face_landmark.rs:324-339
-        landmark_group(landmarks + static_cast<long>(b) * MI_NUM_FACE_LANDMARKS * 3, MI_NUM_FACE_LANDMARKS, kFaceConnectionCount, true,
+        landmark_group(f, sx, sy, mine, landmarks + static_cast<long>(b) * MI_NUM_FACE_LANDMARKS * 3, MI_NUM_FACE_LANDMARKS, kFaceConnectionCount, true,
                        static_cast<double>(st.mesh_thickness), st.mesh_connection_color, st.mesh_landmark_color);
     if (eyes && st.draw_eyes && there)       // iris_landmark.rs:312-331, left eye then right eye
         for (int e = 0; e < 2; e++)
-            landmark_group(eyes + (static_cast<long>(b) * 2 + e) * kEyeRows * 3, kEyeContourPoints, kEyeConnectionCount, false,
+            landmark_group(f, sx, sy, mine, eyes + (static_cast<long>(b) * 2 + e) * kEyeRows * 3, kEyeContourPoints, kEyeConnectionCount, false,
                            static_cast<double>(st.eye_thickness), st.eye_connection_color, st.eye_landmark_color);
+    store_skipped(skipped, b, mine);
+}
+
+// iris_landmarks_to_render_data (iris_landmark.rs:330-377) for one eye; iris = rows 71..75 of the eye, [5][3] f32 (IrisIndex: Center 0, Left 1,
+// Top 2, Right 3, Bottom 4).  The oval annotation, then the points annotation, both of thickness `st.iris_thickness`.
+__device__ __forceinline__ int iris_groups(const Frame& f, double W, double H, const float* iris, const mi_render_items_style& st) {
+    int mine = 0;
+    if (st.draw_iris_oval) {
+        mine += draw_rects(f, 1, false, pack(st.iris_oval_color), [=](int) {
+            // get_iris_diameter (iris_landmark.rs:401-418): both end points are scaled before they are subtracted
+            auto dist = [=](int a, int b) {
+                const double x0 = static_cast<double>(iris[3 * a]) * W, y0 = static_cast<double>(iris[3 * a + 1]) * H;
+                const double x1 = static_cast<double>(iris[3 * b]) * W, y1 = static_cast<double>(iris[3 * b + 1]) * H;
+                return __dsqrt_rn((x0 - x1) * (x0 - x1) + (y0 - y1) * (y0 - y1));
+            };
+            const double radius = (dist(2, 4) + dist(1, 3)) / 2.0 / 2.0;  // (vert + horiz) / 2. (:417), then / 2.0 (:340)
+            // :345-346 divide by the size, render.rs:368-406 multiplies by it again: two roundings, kept
+            const double radius_h = radius / W, radius_v = radius / H;
+            const double cx = static_cast<double>(iris[0]), cy = static_cast<double>(iris[1]);
+            return P4{(cx - radius_h) * W, (cy - radius_v) * H, (cx + radius_h) * W, (cy + radius_v) * H};
+        });
+        next_annotation();
+    }
+    if (st.draw_iris_points) {
+        draw_points(f, MI_NUM_IRIS_LANDMARKS, st.iris_thickness, pack(st.iris_landmark_color),
+                    [=](int i) { return P2{static_cast<double>(iris[3 * i]) * W, static_cast<double>(iris[3 * i + 1]) * H}; });
+        next_annotation();
+    }
+    return mine;
+}
+
+// first slot of item_frame[0, used) whose frame is not below b.  item_frame is only compared: whatever it holds, the result is in [0, used]
+__device__ __forceinline__ int first_slot_of(const int* item_frame, int used, int b) {
+    int lo = 0, hi = used;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (item_frame[mid] < b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The draw phase of mi_render_face_items: the frame's detections, then every item of the frame in slot order.  Everything that decides whether
+// an annotation is drawn (the slot range, present, the style) is the same for all lanes of the workgroup, as next_annotation() needs.
+__global__ __launch_bounds__(kDrawThreads) void render_face_items_kernel(RenderCanvas cv, const mi_detection* faces, const int* face_counts,
+                                                                         int max_faces, const int* item_frame, const int* n_items, int max_items,
+                                                                         const float* landmarks, const int* present, const float* eyes,
+                                                                         mi_render_items_style st, int* skipped) {
+    const int b = blockIdx.x;
+    const Frame f = frame_of(cv, b);
+    const double sx = cv.width, sy = cv.height;
+    int mine = 0;
+    if (faces) {
+        int n = face_counts[b];
+        n = n < 0 ? 0 : (n > max_faces ? max_faces : n);
+        mine += detection_groups(f, faces + static_cast<long>(b) * max_faces, n, sx, sy, st.base);
+    }
+    if (item_frame) {
+        int used = n_items[0];
+        used = used < 0 ? 0 : (used > max_items ? max_items : used);
+        const int first = first_slot_of(item_frame, used, b), last = first_slot_of(item_frame, used, b + 1);
+        for (int j = first; j < last; j++) {
+            // (a list out of order: a slot of another frame inside the range is left out)
+            const bool there = item_frame[j] == b && (present ? present[j] != 0 : true);
+            if (!there) continue;
+            const mi_render_style& base = st.base;
+            if (landmarks && base.draw_mesh)  // face_landmark.rs:324-339
+                landmark_group(f, sx, sy, mine, landmarks + static_cast<long>(j) * MI_NUM_FACE_LANDMARKS * 3, MI_NUM_FACE_LANDMARKS, kFaceConnectionCount,
+                               true, static_cast<double>(base.mesh_thickness), base.mesh_connection_color, base.mesh_landmark_color);
+            if (!eyes) continue;
+            const float* eye = eyes + static_cast<long>(j) * 2 * kEyeRows * 3;
+            if (base.draw_eyes)               // iris_landmark.rs:312-331, left eye then right eye
+                for (int e = 0; e < 2; e++)
+                    landmark_group(f, sx, sy, mine, eye + e * kEyeRows * 3, kEyeContourPoints, kEyeConnectionCount, false,
+                                   static_cast<double>(base.eye_thickness), base.eye_connection_color, base.eye_landmark_color);
+            for (int e = 0; e < 2; e++)       // iris_landmark.rs:330-377, left iris then right iris
+                mine += iris_groups(f, sx, sy, eye + (e * kEyeRows + MI_NUM_EYE_LANDMARKS) * 3, st);
+        }
+    }
     store_skipped(skipped, b, mine);
 }
 
@@ -398,6 +487,13 @@ hipError_t launch_render_faces(const RenderCanvas& cv, const mi_detection* d_fac
                                int* d_skipped, hipStream_t s) {
     return launch_kernel(render_faces_kernel, dim3(cv.batch), dim3(kDrawThreads), 0, s, cv, d_faces, d_face_counts, faces_per_frame, d_landmarks,
                          d_present, d_eyes, style, d_skipped);
+}
+
+hipError_t launch_render_face_items(const RenderCanvas& cv, const mi_detection* d_faces, const int* d_face_counts, int max_faces,
+                                    const int* d_item_frame, const int* d_n_items, int max_items, const float* d_landmarks, const int* d_present,
+                                    const float* d_eyes, const mi_render_items_style& style, int* d_skipped, hipStream_t s) {
+    return launch_kernel(render_face_items_kernel, dim3(cv.batch), dim3(kDrawThreads), 0, s, cv, d_faces, d_face_counts, max_faces, d_item_frame,
+                         d_n_items, max_items, d_landmarks, d_present, d_eyes, style, d_skipped);
 }
 
 }  // namespace mi
