@@ -124,8 +124,11 @@ size_t mi_model_describe(const mi_model *m, char *buf, size_t cap);
  * gave up waiting for its CUs), "band_nw" (workgroups per frame of that plan, 8..256), "band_wide" (0 = its program ends in front of the first stage of
  * more than 128 channels); "stem_fuse" (0 = the face mesh's first convolution keeps a launch of its own instead of running inside the launch of the
  * block pair behind it, from 32 f32 pictures on), "pair_fuse" (0 = two plain BlazeBlocks in a row keep a launch each where one launch has a form for
- * both: the face mesh's 48x48x32 blocks), "mdb_band" (rows per band of those launches, 0 = chosen per launch), "stem_mfma" (0 = the detectors' 5x5 first
- * convolution (f32 tensors) stays on the packed-FMA kernel instead of the matrix cores; bit-identical results).
+ * both: the face mesh's 48x48x32 blocks), "mdb_band" (rows per band of those launches, 0 = chosen per launch), "stem_mfma" (the detectors' 5x5 first
+ * convolution on f32 tensors, bit-identical results in all three: 1 = on the matrix cores with the window's picture rows kept in registers down a column
+ * of 64-pixel tiles (default), 2 = on the matrix cores row-wise, every tile loading the five picture rows of its window, 0 = the packed-FMA kernel;
+ * every other value is taken as 1), "stem_run" (output rows per column run of form 1, 1..32; 0 = chosen per launch so that the runs fill the chip, and
+ * the row-wise form where that leaves one row per run: a handful of frames).
  * Test hook "test_poison" (0 = off, the default; 1 = 0xFF bytes, a NaN; 2 = 0x7F bytes, 3.39e38): before every run the handle fills its activation
  * arena, its small-batch scratch, its output buffers and, in mi_model_run with host input, its input stage beyond the call's frames — a kernel that
  * reads a byte it did not write first turns up in the results. Weights, programs and the single-launch plan's workspace are never touched.

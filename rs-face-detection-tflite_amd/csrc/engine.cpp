@@ -74,7 +74,8 @@ struct Model::Option {
            kKeepGraphs = 4,  // touches neither graphs nor arena
            kOneOf = 8,       // lo is a set instead: bit v says that v is accepted, every other value is stored as 0
            kKiB = 16 /* set and read in KiB, stored in bytes */, kWriteOnly = 32, kReadOnly = 64,
-           kBandGen = 128 }; // stored in band_gen_, and the next band launch takes the wrap path (band_gen_force_)
+           kBandGen = 128,   // stored in band_gen_, and the next band launch takes the wrap path (band_gen_force_)
+           kForms = 256 };   // a switch that grew further positions: lo .. hi are accepted, every other value is stored as 1
     const char* key;
     int Model::*field;
     int lo, hi, flags;
@@ -95,7 +96,10 @@ const Model::Option* Model::find_option(const std::string& key) {
         {"pipe_band", &Model::pipe_band_, 0, 4096, 0},  // rows per band of the row pipelines (0: automatic)
         {"strip", &Model::strip_, 0, 1, 0},  // 0: none of the strip / operand-layout kernels runs (blocks stay on the block kernel and its fused forms)
         {"stem_fuse", &Model::stem_fuse_, 0, 1, 0},  // 0: the first convolution keeps its own launch in front of the face mesh's block pair (mdblock_kernel<stem+pair>)
-        {"stem_mfma", &Model::stem_mfma_, 0, 1, 0},  // 0: the detectors' 5x5 first convolution stays on stem_conv_kernel (packed VALU FMAs) at every batch size (bit-identical)
+        // the detectors' 5x5 first convolution (bit-identical in all three): 1 = stem_mfma_kernel, the window's picture rows kept in registers down a column of tiles;
+        // 2 = the row-wise MFMA form (every tile loads its five rows); 0 = stem_conv_kernel (packed VALU FMAs) at every batch size
+        {"stem_mfma", &Model::stem_mfma_, 0, 2, O::kForms},
+        {"stem_run", &Model::stem_run_, 0, 32, 0},  // output rows per column run of stem_mfma_kernel (0: chosen per launch, the row-wise form where a run would be one row)
         {"pair_fuse", &Model::pair_fuse_, 0, 1, 0},  // 0: two plain blocks in a row keep a launch each (the face mesh's 48x48x32 blocks: mwalk_kernel), no mdblock_kernel<pair>
         {"mdb_band", &Model::mdb_band_, 0, 4096, 0},  // rows per band of the mdblock_kernel launches (0: chosen per launch)
         {"mchain", &Model::mchain_, 0, 1, 0},  // 0: the 32x32x48 blocks run one launch each (mstrip_kernel) instead of one launch per run
@@ -127,6 +131,7 @@ void Model::set_option(const std::string& key, int value) {
     if (!o || (o->flags & Option::kReadOnly)) throw std::runtime_error("unknown option '" + key + "'");
     int v = (o->lo == 0 && o->hi == 1) ? value != 0 : std::min(o->hi, std::max(o->lo, value));
     if (o->flags & Option::kOneOf) v = (value >= 0 && value < 31 && (o->lo >> value & 1)) ? value : 0;
+    if (o->flags & Option::kForms) v = (value >= o->lo && value <= o->hi) ? value : 1;
     if (o->flags & Option::kKiB) v *= 1024;
     if (o->flags & Option::kBandGen) { band_gen_ = static_cast<unsigned>(v); band_gen_force_ = true; }
     else this->*o->field = v;
@@ -336,7 +341,7 @@ LaunchCtx Model::launch_ctx(const float* in, int chunk_start, int frames) const 
     c.band_prog = d_band_prog_; c.band_consts = d_band_consts_; c.band_ws = d_band_ws_; c.band_sync = d_band_sync_; c.band_fail = d_band_fail_;
     c.chunk_cap = chunk_cap_; c.chunk_start = chunk_start; c.F = frames;
     c.u8_frames = u8_.frames; c.u8_lut = u8_.lut; c.u8_frame_bytes = u8_.frame_bytes; c.u8_row_bytes = u8_.row_bytes;
-    c.strip = strip_; c.pair_fuse = pair_fuse_; c.stem_fuse = stem_fuse_; c.stem_mfma = stem_mfma_; c.mchain = mchain_;
+    c.strip = strip_; c.pair_fuse = pair_fuse_; c.stem_fuse = stem_fuse_; c.stem_mfma = stem_mfma_; c.stem_run = stem_run_; c.mchain = mchain_;
     c.small_chain = small_chain_; c.lanes = lanes_;
     c.pipe_rows = pipe_rows_; c.pipe_band = pipe_band_; c.mdb_band = mdb_band_; c.tail_pre = tail_pre_; c.tail_g = tail_g_;
     // (with several lanes the chunks already overlap; the head streams and node events are one set per model, and sharing

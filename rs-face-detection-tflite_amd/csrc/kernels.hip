@@ -308,6 +308,8 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(ConvArgs a) {
 // Measured (BackCamera, 256 frames; profiles/r06_stem_mfma.txt): 0.182 -> 0.165 ms (one frame: 8.9 -> 7.0 us).  What bounds it now is memory, not the matrix cores: without its MFMAs the
 // kernel takes 0.140 ms (201 MB in + 403 MB out = 4.3 TB/s), without its stores 0.147, its 29.5 M MFMAs alone are 0.105 ms at the 8.2 cycles
 // tools/probes/mfma4_probe.hip measures for this stream; the tensor it writes is read once more by the first row pipeline.
+// This row-wise form (a wave takes consecutive tiles, every tile loads its five picture rows) is engine option "stem_mfma" = 2, and what = 1 launches where a column run
+// would be a single row (a handful of frames); the default is the column-run form below it.
 typedef float sv4f __attribute__((ext_vector_type(4)));
 typedef unsigned su4 __attribute__((ext_vector_type(4)));
 typedef unsigned su3 __attribute__((ext_vector_type(3)));
@@ -325,8 +327,11 @@ __device__ __forceinline__ void dfor_tiles_impl(F&& f, std::integer_sequence<int
 template <int N, class F>
 __device__ __forceinline__ void dfor_tiles(F&& f) { dfor_tiles_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
+// Timing ablations of the row-wise form (development only: -DMI_ABL_STEM_NOLOAD / _NOMFMA / _NOSTORE through build.sh's MI_EXTRA_FLAGS; the ablated kernel
+// computes wrong values, only its time counts; profiles/stem_rows.txt): no picture loads (the B operands are weight registers), one VALU add per window value
+// instead of its six MFMAs, no global stores (a store the compiler cannot rule out, never taken).
 template <bool RELU>
-__global__ __launch_bounds__(256) void stem_mfma_kernel(ConvArgs a, int tiles, int tpr) {
+__global__ __launch_bounds__(256) void stem_mfma_rowwise_kernel(ConvArgs a, int tiles, int tpr) {
     constexpr int KW3 = 15, NK = 75, CQ = 6, NA = (NK * CQ + 15) / 16;   // 29 weight registers
     const int lane = threadIdx.x & 63;
     // Workgroup i runs on XCD i % 8, each with an L2 of its own: the workgroups of one XCD take CONSECUTIVE tiles (the rows of one stretch of a frame: a picture
@@ -376,6 +381,11 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(ConvArgs a, int tiles, i
     auto load_row = [&](const Tile& c, int ky, float (&x)[KW3]) {
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in + (long)c.b * a.in_fs), 0, a.H * rowb, 0x00020000);
         const int vo = (2 * c.y - 1 + ky) * rowb + c.lane_off;   // row -1: negative = far outside; rows >= H: outside
+#ifdef MI_ABL_STEM_NOLOAD
+#pragma unroll
+        for (int e = 0; e < KW3; e++) x[e] = wa[e + (vo & 1)];
+        return;
+#endif
         const su4 q0 = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0), q1 = __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 16, 0, 0),
                   q2 = __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 32, 0, 0);
         const su3 q3 = __builtin_amdgcn_raw_buffer_load_b96(rs, vo + 48, 0, 0);
@@ -404,6 +414,10 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(ConvArgs a, int tiles, i
 #pragma unroll
                 for (int e = 0; e < KW3; e++) x[e] = c.right ? (e < 9 ? x[e + 6] : 0.f) : x[e];
             }
+#ifdef MI_ABL_STEM_NOMFMA
+#pragma unroll
+            for (int e = 0; e < KW3; e++) D[e % CQ].x += x[e];
+#else
 #pragma unroll
             for (int e = 0; e < KW3; e++)
 #pragma unroll
@@ -411,6 +425,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(ConvArgs a, int tiles, i
                     const int n = (ky * KW3 + e) * CQ + q;
                     D[q] = stem_mfma4(wa[n >> 4], x[e], D[q], n & 15);
                 }
+#endif
         }
         // The tile's 64 x 24 results are 6 KB of consecutive addresses, but a lane holds ONE pixel's 96 bytes: stored from the registers, each of the six
         // 16-byte store instructions touches every line of the tile (partial sectors at the memory side: loads + stores alone took 0.22 ms).  Through LDS
@@ -429,6 +444,9 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(ConvArgs a, int tiles, i
         }
         __builtin_amdgcn_wave_barrier();   // (the tile is this wave's own: LDS operations of a wave execute in order)
         float* op = a.out + (long)c.b * a.out_fs + ((long)c.y * a.Wo + 64 * c.half) * 24;
+#ifdef MI_ABL_STEM_NOSTORE
+        if (a.B >= 0) return;   // (always: a condition the compiler cannot fold)
+#endif
 #pragma unroll
         for (int q = 0; q < CQ; q++)
             *reinterpret_cast<float4*>(op + (q * 64 + lane) * 4) = *reinterpret_cast<const float4*>(ot + (q * 64 + lane) * 4);
@@ -456,9 +474,131 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(ConvArgs a, int tiles, i
     }
 }
 
+// ---- the same convolution with the window's picture rows kept in registers down a column of tiles (the default form; the row-wise one above is engine option
+// "stem_mfma" = 2).  Row-wise, a tile loads the five picture rows of its window although the tile below shares three of them (stride 2): every picture value
+// went through the vector-memory path 2.5 times vertically (and 2.5 times horizontally: a lane's 15 floats at a 6-float lane stride) — 1.26 GB of loads per
+// launch for 201 MB of pictures.  Here a wave takes a RUN: R consecutive output rows y0 .. y0 + R - 1 of one 64-pixel column of one frame.  The window is five
+// row buffers of 15 floats per lane; a step down loads only the two new picture rows, into the buffers of the two rows the step has just finished with (window
+// row ky of step s lives in buffer (ky + 2 s) mod 5: the step loop is unrolled five times and the roles rotate, nothing is copied).  The two loads are issued
+// behind the MFMAs of window rows 0 and 1 and are first used as rows 3 and 4 of the NEXT step: six to seven rows of 90 MFMAs between request and use.  A run
+// starts with a full five-row load (3 rows more than it strictly needs: 35 row loads per 16 output rows against 80 row-wise); the step below the run's last
+// loads two rows it never uses (inside the frame or, below it, outside the buffer resource: no branch around a load).  The edge lanes' shifted windows are
+// repaired once per picture row — when the row is first used — instead of once per use.  Arithmetic, order of the k chain, epilogue and stores are those of the
+// row-wise form: bit-identical results (tests/test_stem_rows_gpu.py).  75 + 29 + 24 registers of window, filter and accumulators: two workgroups per CU.
+// Runs in the order (frame, run of rows, column) over the workgroups of an XCD, as the tiles above: neighbouring runs share their picture rows in that XCD's L2.
+// Measured (profiles/stem_rows.txt; BackCamera, 256 frames): 0.156 -> 0.138 ms by rocprofv3, the step 1.194 -> 1.183 ms with two batches in flight, 1.267 -> 1.253 with one.  Not for the
+// bytes it no longer loads (the row-wise form without ANY picture load is 2.6 % shorter): 8 instead of 20 load instructions per tile, requested far ahead.
+template <bool RELU>
+__global__ __launch_bounds__(256) void stem_mfma_kernel(ConvArgs a, int runs, int R) {
+    constexpr int KW3 = 15, NK = 75, CQ = 6, NA = (NK * CQ + 15) / 16, NR = 5;
+    const int lane = threadIdx.x & 63;
+    const int G = (int)gridDim.x, wg = (G & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3);
+    const int wv = __builtin_amdgcn_readfirstlane(wg * 4 + (int)(threadIdx.x >> 6)), nwv = G * 4;
+    if (wv >= runs) return;
+    float wa[NA];   // as in the row-wise form
+#pragma unroll
+    for (int r = 0; r < NA; r++) {
+        const int n = 16 * r + (lane >> 2), k = n / CQ, t = n - CQ * k;
+        wa[r] = n < NK * CQ ? a.w[k * 24 + 4 * t + (lane & 3)] : 0.f;
+    }
+    const float hi = a.ep.act == ACT_RELU6 ? 6.f : INFINITY, base_slope = a.ep.act == ACT_NONE ? 1.f : 0.f;
+    const bool prelu = a.ep.act == ACT_PRELU;
+    float bs[24], sl[RELU ? 1 : 24];
+    {
+        const float* __restrict__ bias = a.ep.bias;
+        const float* __restrict__ al = prelu ? a.ep.alpha : a.ep.bias;   // always a readable array
+#pragma unroll
+        for (int i = 0; i < 24; i++) bs[i] = bias[i];
+        if constexpr (!RELU) {
+#pragma unroll
+            for (int i = 0; i < 24; i++) sl[i] = prelu ? al[i] : base_slope;
+        }
+    }
+    const int rowb = a.W * 12, tpr = a.Wo >> 6, rpf = ((a.Ho + R - 1) / R) * tpr;   // bytes of a picture row; tiles per row; runs per frame
+    __shared__ __attribute__((aligned(16))) float otile[4 * 64 * 24];
+    float* const ot = otile + (threadIdx.x >> 6) * (64 * 24);
+    float xb[NR][KW3];
+    for (int run = wv; run < runs; run += nwv) {
+        const int b = run / rpf, rem = run - b * rpf, half = rem % tpr, y0 = (rem / tpr) * R, yend = min(y0 + R, a.Ho);   // wave-uniform
+        const int px = 64 * half + lane;
+        const bool left = px == 0, right = px == a.Wo - 1, has_left = half == 0, has_right = half == tpr - 1;
+        // the window of pixel px starts at column 2 px - 1: the edge lanes read columns 0 .. 4 / W - 5 .. W - 1 instead
+        const int lane_off = (2 * px - 1 + (left ? 1 : 0) - (right ? 2 : 0)) * 12;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in + (long)b * a.in_fs), 0, a.H * rowb, 0x00020000);
+        auto load_row = [&](int row, float (&x)[KW3]) {   // picture row `row`: -1 (a negative offset = far outside) and rows >= H read as zeros
+            const int vo = (int)((unsigned)row * (unsigned)rowb + (unsigned)lane_off);
+            const su4 q0 = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0), q1 = __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 16, 0, 0),
+                      q2 = __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 32, 0, 0);
+            const su3 q3 = __builtin_amdgcn_raw_buffer_load_b96(rs, vo + 48, 0, 0);
+            x[0] = __uint_as_float(q0.x); x[1] = __uint_as_float(q0.y); x[2] = __uint_as_float(q0.z); x[3] = __uint_as_float(q0.w);
+            x[4] = __uint_as_float(q1.x); x[5] = __uint_as_float(q1.y); x[6] = __uint_as_float(q1.z); x[7] = __uint_as_float(q1.w);
+            x[8] = __uint_as_float(q2.x); x[9] = __uint_as_float(q2.y); x[10] = __uint_as_float(q2.z); x[11] = __uint_as_float(q2.w);
+            x[12] = __uint_as_float(q3.x); x[13] = __uint_as_float(q3.y); x[14] = __uint_as_float(q3.z);
+        };
+        auto fix_edges = [&](float (&x)[KW3]) {
+            if (has_left) {     // lane 0 holds columns 0 .. 4, its window is (zero), 0 .. 3
+#pragma unroll
+                for (int e = KW3 - 1; e >= 0; e--) x[e] = left ? (e >= 3 ? x[e - 3] : 0.f) : x[e];
+            }
+            if (has_right) {    // lane 63 holds columns W - 5 .. W - 1, its window is W - 3 .. W - 1, (zero), (zero)
+#pragma unroll
+                for (int e = 0; e < KW3; e++) x[e] = right ? (e < 9 ? x[e + 6] : 0.f) : x[e];
+            }
+        };
+#pragma unroll
+        for (int ky = 0; ky < NR; ky++) load_row(2 * y0 - 1 + ky, xb[ky]);
+#pragma unroll
+        for (int ky = 0; ky < 3; ky++) fix_edges(xb[ky]);   // (rows 3 and 4 of every step are new: repaired there)
+        float* op = a.out + (long)b * a.out_fs + ((long)y0 * a.Wo + 64 * half) * 24;
+        for (int y = y0;;) {
+            bool done = false;
+            dfor_tiles<NR>([&](auto sc) {
+                constexpr int S = decltype(sc)::value;
+                if (done) return;
+                sv4f D[CQ];
+#pragma unroll
+                for (int q = 0; q < CQ; q++) D[q] = sv4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ky = 0; ky < NR; ky++) {
+                    float (&x)[KW3] = xb[(ky + 2 * S) % NR];
+                    if (ky >= 3) fix_edges(x);
+#pragma unroll
+                    for (int e = 0; e < KW3; e++)
+#pragma unroll
+                        for (int q = 0; q < CQ; q++) {
+                            const int n = (ky * KW3 + e) * CQ + q;
+                            D[q] = stem_mfma4(wa[n >> 4], x[e], D[q], n & 15);
+                        }
+                    if (ky < 2) load_row(2 * y + 4 + ky, x);   // window rows 3 and 4 of output row y + 1, into the buffer this row leaves
+                }
+                // through LDS, as in the row-wise form: every store instruction writes 1 KB of consecutive addresses
+#pragma unroll
+                for (int q = 0; q < CQ; q++) {
+                    float r[4] = {D[q].x, D[q].y, D[q].z, D[q].w};
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        const float v = r[i] + bs[4 * q + i];
+                        if constexpr (RELU) r[i] = fmaxf(v, 0.f);
+                        else r[i] = fminf(fmaxf(v, 0.f) + sl[4 * q + i] * fminf(v, 0.f), hi);
+                    }
+                    *reinterpret_cast<float4*>(ot + lane * 24 + 4 * q) = make_float4(r[0], r[1], r[2], r[3]);
+                }
+                __builtin_amdgcn_wave_barrier();   // (the tile is this wave's own: LDS operations of a wave execute in order)
+#pragma unroll
+                for (int q = 0; q < CQ; q++)
+                    *reinterpret_cast<float4*>(op + (q * 64 + lane) * 4) = *reinterpret_cast<const float4*>(ot + (q * 64 + lane) * 4);
+                __builtin_amdgcn_wave_barrier();
+                op += a.Wo * 24;
+                if (++y >= yend) done = true;
+            });
+            if (done) break;
+        }
+    }
+}
+
 static bool stem_mfma_applicable(const ConvArgs& a) {
     static const bool off = getenv("MI_NO_STEM_MFMA") != nullptr;   // tuning aid
-    if (off || a.no_mfma || a.in_u8 || a.KH != 5 || a.KW != 5 || a.C != 3 || a.Co != 24 || a.Cop != 24 || a.sh != 2 || a.sw != 2 || a.pt != 1 || a.pl != 1) return false;
+    if (off || a.no_mfma == 1 || a.in_u8 || a.KH != 5 || a.KW != 5 || a.C != 3 || a.Co != 24 || a.Cop != 24 || a.sh != 2 || a.sw != 2 || a.pt != 1 || a.pl != 1) return false;
     if (a.W != 2 * a.Wo || a.H != 2 * a.Ho || a.Wo % 64 || a.W < 8 || !a.ep.bias || a.ep.res_mode != RES_NONE) return false;
     if ((reinterpret_cast<uintptr_t>(a.in) & 15) || (a.in_fs & 3) || (reinterpret_cast<uintptr_t>(a.out) & 15) || (a.out_fs & 3)) return false;
     if ((long)a.H * a.W * 12 > 0x7fffffffL) return false;
@@ -467,11 +607,26 @@ static bool stem_mfma_applicable(const ConvArgs& a) {
 
 static int launch_stem_mfma(const ConvArgs& a, hipStream_t s) {
     const int tpr = a.Wo / 64, tiles = a.B * a.Ho * tpr;
+    // The column-run form at two workgroups per CU (its waves hold the window: 162 registers with ReLU, 200 without).  Rows per run: what gives every wave of that grid one run,
+    // a power of two up to 32 (BackCamera at 256 frames: 2 048 runs of 32 rows, Short / Front: 2 048 of 8) — or option "stem_run".  Below two rows per run the
+    // row-wise split already fills the chip and a run would be one tile behind a five-row load: the row-wise form, as with option "stem_mfma" = 2.
+    const int run_cu = 2;
+    int R = a.stem_run;
+    if (R <= 0 && a.no_mfma == 0)
+        for (R = 1; R < 32 && (long)tiles >= 2L * R * 4 * run_cu * device_cu_count(); R *= 2) {}
+    if (a.no_mfma == 0 && (R >= 2 || a.stem_run > 0)) {
+        R = std::min(R, a.Ho);
+        const int runs = a.B * ((a.Ho + R - 1) / R) * tpr;
+        unsigned grid = (unsigned)std::min<long>((runs + 3) / 4, (long)run_cu * device_cu_count());
+        if (grid >= 64) grid &= ~7u;   // (a multiple of the XCD count: the kernel's run order assumes it)
+        if (a.ep.act == ACT_RELU) return (int)launch_kernel(stem_mfma_kernel<true>, dim3(grid), dim3(256), 0, s, a, runs, R);
+        return (int)launch_kernel(stem_mfma_kernel<false>, dim3(grid), dim3(256), 0, s, a, runs, R);
+    }
     const int per_cu = 4;   // workgroups of four waves (2 .. 6 per CU measured alike: 0.165 - 0.168 ms)
     unsigned grid = (unsigned)std::min<long>((tiles + 3) / 4, (long)per_cu * device_cu_count());
     if (grid >= 64) grid &= ~7u;   // (a multiple of the XCD count: the kernel's tile order assumes it)
-    if (a.ep.act == ACT_RELU) return (int)launch_kernel(stem_mfma_kernel<true>, dim3(grid), dim3(256), 0, s, a, tiles, tpr);
-    return (int)launch_kernel(stem_mfma_kernel<false>, dim3(grid), dim3(256), 0, s, a, tiles, tpr);
+    if (a.ep.act == ACT_RELU) return (int)launch_kernel(stem_mfma_rowwise_kernel<true>, dim3(grid), dim3(256), 0, s, a, tiles, tpr);
+    return (int)launch_kernel(stem_mfma_rowwise_kernel<false>, dim3(grid), dim3(256), 0, s, a, tiles, tpr);
 }
 
 template <int K, int CO>

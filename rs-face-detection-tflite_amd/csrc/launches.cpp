@@ -343,7 +343,8 @@ struct Lowering {
         if (n.padding == Padding::Same) { same_pad(a.H, a.KH, a.sh, a.Ho, &a.pt); same_pad(a.W, a.KW, a.sw, a.Wo, &a.pl); }
         if (n.ept >= 0) { a.pt = n.ept; a.pl = n.epl; }
         a.ep = ep;
-        a.no_mfma = c.stem_mfma ? 0 : 1;
+        a.no_mfma = c.stem_mfma == 0 ? 1 : c.stem_mfma == 2 ? 2 : 0;
+        a.stem_run = c.stem_run;
         if (c.u8_frames && plan.storage[n.in[0]].root == plan.storage[g.inputs[0]].root) {
             if (!conv_takes_u8(a)) throw std::runtime_error("plan: this graph's first convolution has no u8 input form");
             a.in_u8 = c.u8_frames + static_cast<long>(c.chunk_start) * c.u8_frame_bytes;

@@ -46,7 +46,7 @@ struct LaunchCtx {
     long u8_frame_bytes = 0;
     int u8_row_bytes = 0;
     // options (engine.cpp, find_option)
-    int strip = 1, pair_fuse = 1, stem_fuse = 1, stem_mfma = 1, mchain = 1, small_chain = 16, lanes = 1;
+    int strip = 1, pair_fuse = 1, stem_fuse = 1, stem_mfma = 1, stem_run = 0, mchain = 1, small_chain = 16, lanes = 1;
     int pipe_rows = 0, pipe_band = 0, mdb_band = 0, tail_pre = 0, tail_g = 0;
     bool fork = true;                    // nodes of the side schedule leave the trunk (false: everything in line, no events)
     int cu_count = 256;
