@@ -1,0 +1,139 @@
+//! face_embeddings.rs:22-109 of the reference.  The MODEL IS THE CALLER'S: the reference ships no `face_embeddings.tflite` (its README
+//! tells users to download one), none is shipped here, and the reference's own model has never been run on this engine.  Any graph of
+//! the operators the engine lowers that maps `[1,112,112,3]` to one output of `D` values per frame loads.
+use crate::pipeline::FacesResults;
+use crate::types::{BBox, Detection, Image};
+use crate::{check, ffi};
+use anyhow::Error;
+use std::ffi::CString;
+
+/// `IMG_SIZE` — face_embeddings.rs:20
+pub const IMG_SIZE: i32 = 112;
+
+pub struct FaceEmbeddings {
+    handle: *mut ffi::mi_fe,
+    features: usize,
+}
+
+unsafe impl Send for FaceEmbeddings {}
+unsafe impl Sync for FaceEmbeddings {}
+
+/// What `infer_items` returns: one row per item of `Pipeline::run_faces`, zeros where `valid` is 0.
+pub struct ItemEmbeddings {
+    pub features: usize,
+    /// `[max_items][features]`, l2-normalised
+    pub embeddings: Vec<f32>,
+    /// `[max_items]`: 1 = the item has an embedding (a used slot whose box lies inside its frame)
+    pub valid: Vec<i32>,
+    /// `[max_items][features]` when asked for: the network's output before `l2_norm`
+    pub raw: Vec<f32>,
+    /// `[max_items][112][112][3]` when asked for: the network's input
+    pub chips: Vec<f32>,
+}
+
+impl FaceEmbeddings {
+    /// `FaceEmbeddings::new(model_path)` — face_embeddings.rs:30-44.  `model_path` is the model FILE (default
+    /// "./models/face_embeddings.tflite", :36).
+    pub fn new(model_path: Option<String>) -> Result<FaceEmbeddings, Error> {
+        Self::new_on_device(model_path, 0)
+    }
+
+    pub fn new_on_device(model_path: Option<String>, device: i32) -> Result<FaceEmbeddings, Error> {
+        let path = match model_path {
+            Some(p) => Some(CString::new(p)?),
+            None => None,
+        };
+        let mut handle: *mut ffi::mi_fe = std::ptr::null_mut();
+        check(unsafe { ffi::mi_fe_create(path.as_ref().map_or(std::ptr::null(), |p| p.as_ptr()), device, &mut handle) })?;
+        let mut d: i32 = 0;
+        let rc = unsafe { ffi::mi_fe_features(handle, &mut d) };
+        if rc != ffi::MI_OK {
+            unsafe { ffi::mi_fe_free(handle) };
+            return Err(crate::last_error(rc));
+        }
+        Ok(FaceEmbeddings { handle, features: d.max(0) as usize })
+    }
+
+    /// `D`: 128 or 512 by the reference's doc comment (face_embeddings.rs:29); whatever the caller's graph produces here.
+    pub fn features(&self) -> usize {
+        self.features
+    }
+
+    /// `infer(&self, image, bbox) -> Result<Array2<f32>>` — face_embeddings.rs:46-89, the `[1, D]` array as its row: `bbox` in absolute
+    /// pixels (`faces[0].bbox().scale(size)`, :128), `crop_image_to_bbox`, `image_to_tensor(crop, None, (112, 112), false, (0, 1), false)`,
+    /// the network, `l2_norm`.  Where the reference panics (`Mat::roi(..).unwrap()`, :107: a box that leaves the image) this is an `Err`.
+    pub fn infer<'a, I>(&self, image: I, bbox: BBox) -> Result<Vec<f32>, Error>
+    where
+        I: TryInto<Image<'a>>,
+        I::Error: Into<Error>,
+    {
+        let image: Image<'a> = image.try_into().map_err(Into::into)?;
+        let b = [bbox.xmin, bbox.ymin, bbox.xmax, bbox.ymax];
+        let mut out = vec![0f32; self.features];
+        check(unsafe {
+            ffi::mi_fe_infer_image(self.handle, image.data.as_ptr(), image.width, image.height, image.stride, b.as_ptr(), out.as_mut_ptr(),
+                                   out.len() as i32)
+        })?;
+        Ok(out)
+    }
+
+    /// `infer` for every item of what `Pipeline::run_faces` returned for these frames (`mi_fe_infer_face_items`): chips, network and
+    /// `l2_norm` on the device, one call.
+    pub fn infer_items(&self, frames: &[u8], batch: usize, width: i32, height: i32, stride: i32, faces: &FacesResults, want_raw: bool,
+                       want_chips: bool) -> Result<ItemEmbeddings, Error> {
+        let m = faces.item_frame.len();
+        // FacesResults holds the detections of a frame as a Vec of its own: back to the [batch][max_faces] block the C entry reads
+        let max_faces = faces.faces.iter().map(|f| f.len()).max().unwrap_or(0).max(1);
+        if batch == 0 || m == 0 || m > 32767 || faces.item_face.len() != m || faces.faces.len() != batch || max_faces > 16 {
+            return Err(Error::msg("the result of run_faces on these frames is expected (max_faces 1..16, max_items 1..32767)"));
+        }
+        let mut dets = vec![ffi::mi_detection { data: [0.0; 16], score: 0.0 }; batch * max_faces];
+        for (b, frame) in faces.faces.iter().enumerate() {
+            for (k, det) in frame.iter().enumerate() {
+                dets[b * max_faces + k] = det.to_mi();
+            }
+        }
+        if width <= 0 || height <= 0 || stride <= 0 || (stride as i64) < 3 * width as i64 {
+            return Err(Error::msg("frames must hold batch frames of height rows of stride bytes"));
+        }
+        let (w, h, s) = (width as usize, height as usize, stride as usize);
+        let need = s.checked_mul(h).and_then(|f| f.checked_mul(batch - 1)).and_then(|x| x.checked_add(s * (h - 1))).and_then(|x| x.checked_add(3 * w));
+        if need.map_or(true, |x| frames.len() < x) {
+            return Err(Error::msg("frames must hold batch frames of height rows of stride bytes"));
+        }
+        let d = self.features;
+        let chip = 3 * (IMG_SIZE as usize) * (IMG_SIZE as usize);
+        let mut out = ItemEmbeddings {
+            features: d,
+            embeddings: vec![0f32; m * d],
+            valid: vec![0i32; m],
+            raw: vec![0f32; if want_raw { m * d } else { 0 }],
+            chips: vec![0f32; if want_chips { m * chip } else { 0 }],
+        };
+        check(unsafe {
+            ffi::mi_fe_infer_face_items(self.handle, frames.as_ptr(), batch as i32, width, height, stride, dets.as_ptr(), max_faces as i32,
+                                        faces.item_frame.as_ptr(), faces.item_face.as_ptr(), m as i32,
+                                        out.embeddings.as_mut_ptr(), out.valid.as_mut_ptr(),
+                                        if want_raw { out.raw.as_mut_ptr() } else { std::ptr::null_mut() },
+                                        if want_chips { out.chips.as_mut_ptr() } else { std::ptr::null_mut() }, ffi::MI_MEM_HOST,
+                                        std::ptr::null_mut())
+        })?;
+        Ok(out)
+    }
+}
+
+impl Drop for FaceEmbeddings {
+    fn drop(&mut self) {
+        unsafe { ffi::mi_fe_free(self.handle) }
+    }
+}
+
+/// The rectangle `crop_image_to_bbox` (face_embeddings.rs:101-109) cuts for `detection.bbox().scale(image_size)`: `(x, y, width, height)`
+/// and whether `Mat::roi` takes it (and it is not empty).  Host only.
+pub fn face_chip_rect(detection: &Detection, image_size: (i32, i32)) -> Result<((i32, i32, i32, i32), bool), Error> {
+    let det = detection.to_mi();
+    let mut rect = [0i32; 4];
+    let mut valid: i32 = 0;
+    check(unsafe { ffi::mi_face_chip_rect(&det, image_size.0, image_size.1, rect.as_mut_ptr(), &mut valid) })?;
+    Ok(((rect[0], rect[1], rect[2], rect[3]), valid != 0))
+}

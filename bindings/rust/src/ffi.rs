@@ -102,6 +102,7 @@ pub struct mi_render_items_style {
 #[repr(C)] pub struct mi_fl { _private: [u8; 0] }
 #[repr(C)] pub struct mi_iris { _private: [u8; 0] }
 #[repr(C)] pub struct mi_pipeline { _private: [u8; 0] }
+#[repr(C)] pub struct mi_fe { _private: [u8; 0] }
 
 extern "C" {
     pub fn mi_last_error() -> *const c_char;
@@ -201,4 +202,21 @@ extern "C" {
                                 n_items: *const c_int, max_items: c_int, landmarks: *const c_float, present: *const c_int,
                                 eyes: *const c_float, style: *const mi_render_items_style, out: *mut u8, out_channels: c_int,
                                 out_stride: c_int, skipped: *mut c_int, mem: c_int, stream: *mut c_void) -> c_int;
+
+    // FaceEmbeddings — face_embeddings.rs:22-109, with l2_norm / similarity_score (utils.rs:30-50); the model is the caller's
+    pub fn mi_fe_create(model_path: *const c_char, device: c_int, out: *mut *mut mi_fe) -> c_int;
+    pub fn mi_fe_create_from_bytes(tflite: *const u8, nbytes: usize, device: c_int, out: *mut *mut mi_fe) -> c_int;
+    pub fn mi_fe_free(h: *mut mi_fe);
+    pub fn mi_fe_features(h: *const mi_fe, features: *mut c_int) -> c_int;
+    pub fn mi_face_chip_rect(det: *const mi_detection, width: c_int, height: c_int, rect: *mut c_int, valid: *mut c_int) -> c_int;
+    pub fn mi_fe_infer_image(h: *mut mi_fe, rgb: *const u8, width: c_int, height: c_int, stride: c_int, bbox: *const c_double,
+                             embedding: *mut c_float, cap: c_int) -> c_int;
+    pub fn mi_fe_infer_face_items(h: *mut mi_fe, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,
+                                  faces: *const mi_detection, max_faces: c_int, item_frame: *const c_int, item_face: *const c_int,
+                                  max_items: c_int, embeddings: *mut c_float, valid: *mut c_int, raw: *mut c_float, chips: *mut c_float,
+                                  mem: c_int, stream: *mut c_void) -> c_int;
+    pub fn mi_l2_norm(input: *const c_float, n: c_int, out: *mut c_float) -> c_int;
+    pub fn mi_similarity_score(a: *const c_float, b: *const c_float, n: c_int, out: *mut c_float) -> c_int;
+    pub fn mi_similarity_matrix(device: c_int, a: *const c_float, n: c_int, b: *const c_float, m: c_int, features: c_int, out: *mut c_float,
+                                mem: c_int, stream: *mut c_void) -> c_int;
 }

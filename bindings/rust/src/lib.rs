@@ -7,7 +7,8 @@
 //!
 //! Reference files mirrored (paths relative to the reference's `src/face_detection_lite/`):
 //! `types.rs` -> [`types`], `face_detection.rs:117-267` -> [`face_detection`], `face_landmark.rs:168-306` ->
-//! [`face_landmark`], `iris_landmark.rs:115-292,380-398` -> [`iris_landmark`], `utils.rs:8-21` -> [`utils`], `render.rs` -> [`render`].
+//! [`face_landmark`], `iris_landmark.rs:115-292,380-398` -> [`iris_landmark`], `utils.rs:8-50` -> [`utils`], `render.rs` -> [`render`],
+//! `face_embeddings.rs` -> [`face_embeddings`] (the embedding model is the caller's: the reference ships none).
 //!
 //! Concurrency: the reference's handles are immutable after `new`, and `infer(&self)` may run on several threads.  The
 //! handles here own device state (activation arena, replay graphs), so libmiface serialises the calls made on one handle
@@ -16,6 +17,7 @@ pub mod ffi;
 pub mod types;
 
 pub mod face_detection;
+pub mod face_embeddings;
 pub mod face_landmark;
 pub mod iris_landmark;
 pub mod pipeline;
@@ -23,6 +25,7 @@ pub mod render;
 pub mod utils;
 
 pub use face_detection::{FaceDetection, FaceDetectionModel};
+pub use face_embeddings::{face_chip_rect, FaceEmbeddings, ItemEmbeddings};
 pub use face_landmark::{face_detection_to_roi, FaceLandmark};
 pub use render::{
     detections_to_render_data, iris_landmarks_to_render_data, landmarks_to_render_data, render_face_items, render_to_image, Annotation,
@@ -31,6 +34,7 @@ pub use render::{
 pub use iris_landmark::{iris_roi_from_face_landmarks, update_face_landmarks_with_iris_results, IrisLandmark};
 pub use pipeline::{face_items_layout, FacesResults, Pipeline};
 pub use types::{BBox, Detection, Image, IrisResults, Landmark, Rect};
+pub use utils::{l2_norm, similarity_matrix, similarity_score};
 
 use anyhow::Error;
 use std::ffi::CStr;

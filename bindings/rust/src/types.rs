@@ -90,6 +90,10 @@ impl BBox {
     pub fn normalized(&self) -> bool {
         self.xmin >= -1.0 && self.xmax < 2.0 && self.ymin >= -1.0
     }
+    /// types.rs:162-165
+    pub fn scale(&self, size: (f64, f64)) -> BBox {
+        BBox::new(self.xmin * size.0, self.ymin * size.1, self.xmax * size.0, self.ymax * size.1)
+    }
 }
 
 /// types.rs:176-187

@@ -353,6 +353,68 @@ int mi_pipeline_collect_jpeg(mi_pipeline *p, int slot, mi_detection *face, int *
                              int *width, int *height);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * L1 — FaceEmbeddings (face_embeddings.rs:22-109) with l2_norm / similarity_score (utils.rs:30-50)
+ *
+ * The MODEL IS THE CALLER'S: the reference does not ship face_embeddings.tflite (its README tells users to download one), so none is
+ * shipped here either, the reference's own model could not be fetched, its operators are unknown and it has never been run on this
+ * engine.  Any graph made of the operators the engine lowers loads; another operator is refused with the planner's message.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct mi_fe mi_fe;
+
+#define MI_FE_CHIP_SIZE 112 /* IMG_SIZE, face_embeddings.rs:20 */
+
+/* FaceEmbeddings::new(model_path) — face_embeddings.rs:30-44. model_path is a FILE path (NULL = "./models/face_embeddings.tflite", :36).
+ * MI_EINVAL with a message unless the graph maps [1,112,112,3] to ONE output of D >= 1 values per frame ([1,D], as :83-84 reads it, and
+ * [1,1,1,D] are both taken); an operator the planner does not lower is MI_EMODEL with the planner's message, which names the operator code. */
+int mi_fe_create(const char *model_path, int device, mi_fe **out);
+int mi_fe_create_from_bytes(const uint8_t *tflite, size_t nbytes, int device, mi_fe **out);
+void mi_fe_free(mi_fe *h);
+mi_model *mi_fe_model(mi_fe *h); /* borrowed */
+/* D: the doc comment at face_embeddings.rs:29 says 128 or 512; any D >= 1 is taken. */
+int mi_fe_features(const mi_fe *h, int *features);
+
+/* Host only, no GPU: the rectangle crop_image_to_bbox cuts for a detection (face_embeddings.rs:101-109 on
+ * `faces[k].bbox().scale((width as f64, height as f64))`, types.rs:162-165,219-225) — the specification of the device code; both go
+ * through the same arithmetic.  Each of xmin, ymin, xmax, ymax is the detection's f32 widened to f64, times the picture size;
+ * rect = {x: xmin as i32, y: ymin as i32, width: (xmax - xmin) as i32, height: (ymax - ymin) as i32}, the differences taken in f64, every
+ * cast Rust's `as` (toward zero, saturating, NaN -> 0).  *valid = 0 for a rectangle OpenCV's Mat::roi refuses (0 <= x, 0 <= width,
+ * x + width <= cols, likewise for rows: the reference panics on the unwrap at :107) and for width <= 0 or height <= 0. */
+int mi_face_chip_rect(const mi_detection *det, int width, int height, int rect[4], int *valid);
+
+/* FaceEmbeddings::infer(&Mat, BBox) — face_embeddings.rs:46-89: bbox = {xmin, ymin, xmax, ymax} in absolute pixels (what the reference's
+ * test passes: bbox().scale(size), :128).  crop_image_to_bbox, image_to_tensor(crop, None, (112,112), false, (0,1), false) — the crop is an
+ * image of its own: BORDER_CONSTANT 0 applies at the crop's edge, no pixel next to the box is sampled —, the network, l2_norm.
+ * rgb = 8UC3 RGB rows of `stride` bytes, host memory; embedding = D floats, host memory.  MI_ERANGE where the reference panics (a
+ * rectangle Mat::roi refuses, or an empty one); MI_EINVAL for cap < D. */
+int mi_fe_infer_image(mi_fe *h, const uint8_t *rgb, int width, int height, int stride, const double bbox[4], float *embedding, int cap);
+
+/* The same for EVERY item of what mi_pipeline_run_faces left in memory, as it lies there: frames [batch] (8UC3, rows of `stride` bytes,
+ * frames stride*height bytes apart), faces [batch][max_faces] (max_faces 1..16), item_frame / item_face [max_items] (max_items 1..32767).
+ * Item j is faces[item_frame[j]][item_face[j]]: its rectangle as mi_face_chip_rect, its chip, the network on all max_items chips, l2_norm.
+ *   embeddings  f32 [max_items][D]            valid  [max_items]: 1 = the item has an embedding
+ *   raw         f32 [max_items][D], may be NULL: the network's output before l2_norm (embeddings[j] == mi_l2_norm(raw[j]) bit for bit)
+ *   chips       f32 [max_items][112][112][3], may be NULL: the network's input
+ * An item is invalid when its item_frame is -1 (an unused slot), when item_frame / item_face point outside the arrays, or when its rectangle
+ * is invalid: valid = 0, its rows of all three outputs are zeros, and neither its frame nor its detection is dereferenced.  A norm of zero
+ * gives what the reference gives (IEEE division: NaN).  COST: the network always runs on max_items items — launch shapes depend on the
+ * arguments alone, no count is read back, and with MI_MEM_DEVICE and a caller's stream nothing synchronises with the host but the allocation
+ * of scratch when max_items grows.  All pointers follow `mem`. */
+int mi_fe_infer_face_items(mi_fe *h, const uint8_t *frames, int batch, int width, int height, int stride, const mi_detection *faces,
+                           int max_faces, const int *item_frame, const int *item_face, int max_items, float *embeddings, int *valid,
+                           float *raw, float *chips, int mem, void *stream);
+
+/* utils::l2_norm(arr) — utils.rs:30-33: out = in / sqrt(sum in^2), the sum in f32, in index order, the square and the add rounded
+ * separately (iter().map().sum::<f32>()).  Host only, bit-identical to the reference's order of operations; out may alias in. */
+int mi_l2_norm(const float *in, int n, float *out);
+/* utils::similarity_score(a, b) — utils.rs:44-50: dot / (norm_a * norm_b), all three sums f32 and sequential.  Host only. */
+int mi_similarity_score(const float *a, const float *b, int n, float *out);
+/* out[i][j] = similarity_score(a_i, b_j) for a [n][features] against a gallery b [m][features], on the f32 matrix cores
+ * (v_mfma_f32_32x32x2_f32): the norms are the reference's sums bit for bit, the dot products are k-ordered fma chains — within
+ * (4 * features + 8) * 2^-24 of the sequential evaluation.  n, m >= 1, features 1..4096; a / b / out follow `mem`.  With MI_MEM_DEVICE and a
+ * caller stream the call is asynchronous. */
+int mi_similarity_matrix(int device, const float *a, int n, const float *b, int m, int features, float *out, int mem, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Host-side helpers the reference exports next to the three structs
  * ---------------------------------------------------------------------------------------------------------------- */
 /* transform::bbox_to_roi(bbox, image_size, rotation_keypoints, scale, mode) — transform.rs:44-109.  bbox = {xmin, ymin, xmax,

@@ -50,6 +50,7 @@ struct BBox {
     double xmin, ymin, xmax, ymax;
     double width() const { return xmax - xmin; }
     double height() const { return ymax - ymin; }
+    BBox scale(std::pair<double, double> size) const { return BBox{xmin * size.first, ymin * size.second, xmax * size.first, ymax * size.second}; }   // types.rs:162-165
 };
 
 // types.rs:176-187
@@ -390,6 +391,87 @@ class Pipeline {
    private:
     mi_pipeline* h_ = nullptr;
 };
+
+// FaceEmbeddings (face_embeddings.rs:22-109).  The model is the CALLER'S: the reference ships no face_embeddings.tflite, none is shipped here,
+// and the reference's own model has never been run on this engine; any graph of the operators the engine lowers that maps [1,112,112,3] to
+// one output of D values per frame loads.
+struct FaceItemEmbeddings {       // mi_fe_infer_face_items, results in host memory
+    int features = 0;
+    std::vector<float> embeddings;   // [max_items][D], zeros where valid is 0
+    std::vector<int> valid;          // [max_items]
+    std::vector<float> raw;          // [max_items][D] when asked for: the network's output before l2_norm
+    std::vector<float> chips;        // [max_items][112][112][3] when asked for: the network's input
+};
+class FaceEmbeddings {
+   public:
+    // FaceEmbeddings::new(model_path): a FILE path, default "./models/face_embeddings.tflite" (face_embeddings.rs:30-37)
+    explicit FaceEmbeddings(std::optional<std::string> model_path = std::nullopt, int device = 0) {
+        detail::check(mi_fe_create(model_path ? model_path->c_str() : nullptr, device, &h_));
+        detail::check(mi_fe_features(h_, &features_));
+    }
+    ~FaceEmbeddings() { mi_fe_free(h_); }
+    FaceEmbeddings(const FaceEmbeddings&) = delete;
+    FaceEmbeddings& operator=(const FaceEmbeddings&) = delete;
+    int features() const { return features_; }
+
+    // FaceEmbeddings::infer(&Mat, BBox) -> Array2<f32> [1, D], l2-normalised; bbox in absolute pixels (face_embeddings.rs:46-89).  Throws
+    // Error (MI_ERANGE) where the reference panics: a box that leaves the image.
+    std::vector<float> infer(const Image& image, const BBox& bbox) const {
+        std::vector<float> out(static_cast<std::size_t>(features_));
+        const double b[4] = {bbox.xmin, bbox.ymin, bbox.xmax, bbox.ymax};
+        detail::check(mi_fe_infer_image(h_, image.rgb, image.width, image.height, image.stride, b, out.data(), features_));
+        return out;
+    }
+    // every item of what Pipeline::run_faces returned, frames in host memory
+    FaceItemEmbeddings infer_items(const std::uint8_t* frames, int batch, int width, int height, int stride, const FacesResults& r,
+                                   bool want_raw = false, bool want_chips = false) const {
+        const std::size_t M = r.item_frame.size(), D = static_cast<std::size_t>(features_);
+        if (batch < 1 || M < 1 || M > 32767 || r.item_face.size() != M || r.faces.size() % static_cast<std::size_t>(batch) != 0)
+            throw std::invalid_argument("infer_items: the result of run_faces on these frames is expected (max_items 1..32767)");
+        FaceItemEmbeddings o;
+        o.features = features_;
+        o.embeddings.resize(M * D);
+        o.valid.resize(M);
+        if (want_raw) o.raw.resize(M * D);
+        if (want_chips) o.chips.resize(M * 3 * MI_FE_CHIP_SIZE * MI_FE_CHIP_SIZE);
+        detail::check(mi_fe_infer_face_items(h_, frames, batch, width, height, stride, r.faces.data(), static_cast<int>(r.faces.size() / batch),
+                                             r.item_frame.data(), r.item_face.data(), static_cast<int>(M), o.embeddings.data(), o.valid.data(),
+                                             want_raw ? o.raw.data() : nullptr, want_chips ? o.chips.data() : nullptr, MI_MEM_HOST, nullptr));
+        return o;
+    }
+
+   private:
+    mi_fe* h_ = nullptr;
+    int features_ = 0;
+};
+
+// crop_image_to_bbox's rectangle for a detection (face_embeddings.rs:101-109 on bbox().scale(size)); host only.  -> {x, y, w, h}, valid
+inline std::pair<std::array<int, 4>, bool> face_chip_rect(const Detection& d, std::pair<int, int> image_size) {
+    mi_detection c{};
+    std::copy(d.data.begin(), d.data.end(), c.data);
+    c.score = d.score;
+    std::array<int, 4> rect{};
+    int valid = 0;
+    detail::check(mi_face_chip_rect(&c, image_size.first, image_size.second, rect.data(), &valid));
+    return {rect, valid != 0};
+}
+// utils::l2_norm / utils::similarity_score (utils.rs:30-50), bit-identical to the reference's order of operations; host only
+inline std::vector<float> l2_norm(const std::vector<float>& arr) {
+    std::vector<float> out(arr.size());
+    detail::check(mi_l2_norm(arr.data(), static_cast<int>(arr.size()), out.data()));
+    return out;
+}
+inline float similarity_score(const std::vector<float>& a, const std::vector<float>& b) {
+    if (a.size() != b.size()) throw std::invalid_argument("similarity_score: vectors of one length are expected");
+    float out = 0.f;
+    detail::check(mi_similarity_score(a.data(), b.data(), static_cast<int>(a.size()), &out));
+    return out;
+}
+// similarity_score of every row of a [n][features] against every row of a gallery b [m][features], on the GPU; pointers follow `mem`
+inline void similarity_matrix(const float* a, int n, const float* b, int m, int features, float* out, int mem = MI_MEM_HOST, void* stream = nullptr,
+                              int device = 0) {
+    detail::check(mi_similarity_matrix(device, a, n, b, m, features, out, mem, stream));
+}
 
 // render.rs on the device (include/mi_face.h, "render.rs").  Colors::{BLACK, ...} (render.rs:28-68) as the bytes render_to_image writes.
 struct Colors {

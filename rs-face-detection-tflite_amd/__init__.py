@@ -11,4 +11,5 @@ from .api import (  # noqa: F401
     bbox_from_landmarks, bbox_to_roi, convert_image_to_mat, image_to_tensor, iris_roi_from_face_landmarks, jpeg_info, lib, plan_describe, dist_broadcast_bytes, streams_create_distinct, streams_destroy, update_face_landmarks_with_iris_results,
     ANN_FILLED_RECTS, ANN_LINES, ANN_POINTS, ANN_RECTS, Annotation, Color, Colors, RenderStyle, render_annotations, render_faces,
     RenderItemsStyle, render_face_items,
+    FE_CHIP_SIZE, FaceEmbeddings, face_chip_rect, l2_norm, similarity_score, similarity_matrix,
 )

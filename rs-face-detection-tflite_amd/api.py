@@ -42,6 +42,8 @@ EXPORTS = [
     "mi_pipeline_run_faces", "mi_face_items_layout",
     "mi_bbox_to_roi", "mi_bbox_from_landmarks", "mi_face_detection_to_roi", "mi_iris_roi_from_face_landmarks", "mi_update_face_landmarks_with_iris_results", "mi_image_to_tensor", "mi_jpeg_info", "mi_jpeg_decode_rgb",
     "mi_render_annotations", "mi_render_faces", "mi_render_face_items",
+    "mi_fe_create", "mi_fe_create_from_bytes", "mi_fe_free", "mi_fe_model", "mi_fe_features", "mi_face_chip_rect", "mi_fe_infer_image",
+    "mi_fe_infer_face_items", "mi_l2_norm", "mi_similarity_score", "mi_similarity_matrix",
 ]
 
 
@@ -323,6 +325,19 @@ def lib():
                                   C.c_int, vp, C.c_int, vp]
     L.mi_render_face_items.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp,
                                        C.POINTER(RenderItemsStyle), vp, C.c_int, C.c_int, vp, C.c_int, vp]
+    L.mi_fe_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
+    L.mi_fe_create_from_bytes.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.mi_fe_free.argtypes = [vp]
+    L.mi_fe_free.restype = None
+    L.mi_fe_model.argtypes = [vp]
+    L.mi_fe_model.restype = vp
+    L.mi_fe_features.argtypes = [vp, ip]
+    L.mi_face_chip_rect.argtypes = [C.POINTER(CDetection), C.c_int, C.c_int, ip, ip]
+    L.mi_fe_infer_image.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dp, vp, C.c_int]
+    L.mi_fe_infer_face_items.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp]
+    L.mi_l2_norm.argtypes = [vp, C.c_int, vp]
+    L.mi_similarity_score.argtypes = [vp, vp, C.c_int, fp]
+    L.mi_similarity_matrix.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]
     _lib = L
     return L
 
@@ -1157,6 +1172,143 @@ def render_face_items(frames, result, style=None, out=None, out_channels=4, devi
     _check(lib().mi_render_face_items(device, p, B, W, H, stride, pf, pn, F, pi, pc, M, pl, pp, pe, C.byref(style), po, out_channels, ostride,
                                       _ptr(skipped)[0], mem, C.c_void_p(stream or 0)))
     return out, skipped
+
+
+FE_CHIP_SIZE = 112   # IMG_SIZE, face_embeddings.rs:20
+
+
+class FaceEmbeddings:
+    """Face embeddings — mirrors face_embeddings.rs:22-109.  The MODEL IS THE CALLER'S: the reference ships no face_embeddings.tflite (its
+    README tells users to download one), none is shipped here, and the reference's own model has never been run on this engine.  Any graph
+    of the operators the engine lowers that maps [1,112,112,3] to one output of D values per frame loads; `features` is D."""
+
+    def __init__(self, model_path=None, device=0, model_bytes=None):
+        self.L = lib()
+        self.h = C.c_void_p()
+        if model_bytes is not None:
+            _check(self.L.mi_fe_create_from_bytes(model_bytes, len(model_bytes), device, C.byref(self.h)))
+        else:
+            # None: the reference's default, "./models/face_embeddings.tflite" relative to the working directory (face_embeddings.rs:36)
+            _check(self.L.mi_fe_create(os.fsencode(model_path) if model_path is not None else None, device, C.byref(self.h)))
+        self.device = device
+        self.model = Model(handle=self.L.mi_fe_model(self.h), owner=self, device=device)
+        n = C.c_int()
+        _check(self.L.mi_fe_features(self.h, C.byref(n)))
+        self.features = n.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mi_fe_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def infer(self, image, bbox, cap=None):
+        """FaceEmbeddings::infer(&Mat, BBox) -> float32 [1, D], l2-normalised: bbox = (xmin, ymin, xmax, ymax) in absolute pixels (what the
+        reference's test passes: faces[0].bbox().scale(size)).  MiError (MI_ERANGE) where the reference panics: a box that leaves the image."""
+        image, w, h, stride = _image_args(image)
+        box = (C.c_double * 4)(*[float(v) for v in bbox])
+        cap = self.features if cap is None else int(cap)
+        out = np.zeros((1, max(cap, 1)), np.float32)
+        _check(self.L.mi_fe_infer_image(self.h, C.c_void_p(image.ctypes.data), w, h, stride, box, C.c_void_p(out.ctypes.data), cap))
+        return out[:, :self.features]
+
+    def infer_items(self, frames, result, want_raw=False, want_chips=False, stream=None):
+        """mi_fe_infer_face_items on what Pipeline.run_faces returned (`result`: its dict; faces [B,F,17], item_frame [M], item_face [M] are
+        read), numpy arrays or CUDA tensors in the memory of the frames.  Returns dict(embeddings [M,D], valid [M]) plus raw [M,D] (the
+        network's output before l2_norm) and chips [M,112,112,3] (its input) when asked for; rows of invalid items (unused slots, boxes that
+        leave the frame) are zeros.  With CUDA tensors nothing visits the host, and with a caller stream the call is asynchronous."""
+        p, mem, B, H, W, stride = _picture(frames, 3, "frames")
+        if mem == MI_MEM_DEVICE:
+            _device_ready(frames, self.device, None, "uint8")
+        faces, item_frame, item_face = result["faces"], result["item_frame"], result["item_face"]
+        shape = lambda x: tuple(int(v) for v in x.shape)
+        if faces.ndim != 3 or shape(faces)[0] != B or shape(faces)[2] != 17:
+            raise ValueError("faces must be [B,F,17]")
+        F, M = shape(faces)[1], shape(item_frame)[0]
+        if item_frame.ndim != 1 or shape(item_face) != (M,):
+            raise ValueError("item_frame and item_face must be [M]")
+        if not (1 <= F <= 16 and 1 <= M <= 32767):   # (before the outputs are sized by them; the C entry checks again)
+            raise MiError(-1, "max_faces must be 1..16 and max_items 1..32767")   # MI_EINVAL
+        pf, faces = _render_operand(faces, mem, self.device, "float32", "faces")
+        pi, item_frame = _render_operand(item_frame, mem, self.device, "int32", "item_frame")
+        pk, item_face = _render_operand(item_face, mem, self.device, "int32", "item_face")
+        D = self.features
+        shapes = dict(embeddings=((M, D), "float32"), valid=((M,), "int32"))
+        if want_raw:
+            shapes["raw"] = ((M, D), "float32")
+        if want_chips:
+            shapes["chips"] = ((M, FE_CHIP_SIZE, FE_CHIP_SIZE, 3), "float32")
+        if mem == MI_MEM_DEVICE:
+            import torch
+            out = {k: torch.zeros(sh, dtype=getattr(torch, dt), device=frames.device) for k, (sh, dt) in shapes.items()}
+            torch.cuda.current_stream(frames.device).synchronize()   # (the zero fills above were queued on torch's stream)
+        else:
+            out = {k: np.zeros(sh, getattr(np, dt)) for k, (sh, dt) in shapes.items()}
+        opt = lambda k: _ptr(out[k])[0] if k in out else None
+        _check(self.L.mi_fe_infer_face_items(self.h, p, B, W, H, stride, pf, F, pi, pk, M, _ptr(out["embeddings"])[0], _ptr(out["valid"])[0],
+                                             opt("raw"), opt("chips"), mem, C.c_void_p(stream or 0)))
+        return out
+
+
+def face_chip_rect(detection, image_size):
+    """mi_face_chip_rect (host only, no GPU): the rectangle FaceEmbeddings crops for a detection — `detection` a Detection or 17 floats,
+    image_size = (width, height).  -> ((x, y, w, h), valid)."""
+    d = CDetection()
+    data = np.asarray(detection.data if isinstance(detection, Detection) else detection, np.float32).reshape(-1)
+    for i in range(16):
+        d.data[i] = data[i]
+    rect, valid = (C.c_int * 4)(), C.c_int()
+    _check(lib().mi_face_chip_rect(C.byref(d), int(image_size[0]), int(image_size[1]), rect, C.byref(valid)))
+    return tuple(rect), bool(valid.value)
+
+
+def l2_norm(arr):
+    """utils::l2_norm (utils.rs:30-33), bit-identical to the reference's order of operations: arr / sqrt(sum arr^2) over ALL elements of
+    `arr` (an Array2 in the reference), float32, same shape."""
+    a = np.ascontiguousarray(arr, np.float32)
+    out = np.zeros_like(a)
+    _check(lib().mi_l2_norm(C.c_void_p(a.ctypes.data), int(a.size), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def similarity_score(a, b):
+    """utils::similarity_score (utils.rs:44-50): the cosine of two vectors, all three sums float32 and sequential.  -> numpy float32."""
+    a = np.ascontiguousarray(a, np.float32).reshape(-1)
+    b = np.ascontiguousarray(b, np.float32).reshape(-1)
+    if a.size != b.size:
+        raise ValueError("a and b must have the same length")   # (the reference's zip would stop at the shorter one for the dot product only)
+    out = C.c_float()
+    _check(lib().mi_similarity_score(C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), int(a.size), C.byref(out)))
+    return np.float32(out.value)
+
+
+def similarity_matrix(a, b, device=0, stream=None):
+    """mi_similarity_matrix: out[i, j] = similarity_score(a[i], b[j]) for a [n, D] against a gallery b [m, D] on the GPU's f32 matrix cores;
+    numpy arrays (-> numpy) or CUDA tensors (-> a CUDA tensor; asynchronous with a caller stream).  D 1..4096."""
+    if _is_torch(a) and a.is_cuda:
+        import torch
+        if not (_is_torch(b) and b.is_cuda and a.dim() == 2 and b.dim() == 2 and a.is_contiguous() and b.is_contiguous()):
+            raise ValueError("a and b must be contiguous 2-d CUDA tensors")
+        _device_ready(a, device)
+        _device_ready(b, device)
+        mem = MI_MEM_DEVICE
+        out = torch.empty((int(a.shape[0]), int(b.shape[0])), dtype=torch.float32, device=a.device)
+    else:
+        a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+        if a.ndim != 2 or b.ndim != 2:
+            raise ValueError("a and b must be [n, D] and [m, D]")
+        mem = MI_MEM_HOST
+        out = np.empty((a.shape[0], b.shape[0]), np.float32)
+    if int(a.shape[1]) != int(b.shape[1]):
+        raise ValueError("a and b must have the same number of features")
+    _check(lib().mi_similarity_matrix(int(device), _ptr(a)[0], int(a.shape[0]), _ptr(b)[0], int(b.shape[0]), int(a.shape[1]), _ptr(out)[0], mem,
+                                      C.c_void_p(stream or 0)))
+    return out
 
 
 def _pipeline_submit_jpeg(self, slot, im_bytes):

@@ -21,7 +21,9 @@
 #include <cstdio>
 #include <thread>
 
+#include "embed.hpp"
 #include "engine.hpp"
+#include "face_chip.hpp"
 #include "face_items.hpp"
 #include "launch.hpp"
 #include "host_glue.hpp"
@@ -385,6 +387,13 @@ struct mi_iris {
     DeviceBuf d_in, d_roi, d_size, d_pad, d_flip, d_contour, d_iris, d_img, d_geom, d_sizes_b;
     int sizes_N = 0, sizes_w = 0, sizes_h = 0;
     OneShot one;
+};
+
+// FaceEmbeddings (face_embeddings.rs:22-26): the caller's network and the scratch of its two entries.
+struct mi_fe {
+    mi_model model;
+    int features = 0;   // D
+    DeviceBuf d_in, d_geom, d_valid, d_img, d_frames, d_faces, d_item_frame, d_item_face, d_emb, d_raw;
 };
 
 extern "C" {
@@ -2440,6 +2449,187 @@ int mi_render_face_items(int device, const uint8_t* frames, int batch, int width
                                                                    d_present, d_eyes, *style, d_skipped, s);
                        if (e != hipSuccess) throw std::runtime_error(std::string("render kernel launch failed: ") + hipGetErrorString(e));
                    });
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ FaceEmbeddings
+static void fe_finish_create(mi_fe* h) {
+    mi::Model& m = *h->model.m;
+    const auto d = m.input_dims();
+    if (!(d.size() == 4 && d[0] == 1 && d[1] == mi::kChipSize && d[2] == mi::kChipSize && d[3] == 3))
+        throw ApiError(MI_EINVAL, "incompatible model: the input must be [1,112,112,3] (image_to_tensor(crop, None, (112,112), ..), face_embeddings.rs:55)");
+    if (m.num_outputs() != 1) throw ApiError(MI_EINVAL, "incompatible model: exactly one output is expected (face_embeddings.rs:74-75), found " + std::to_string(m.num_outputs()));
+    const auto& o = m.output_dims(0);
+    const size_t D = m.output_elems(0);
+    if (o.empty() || o[0] != 1 || D < 1 || D > (1u << 24))
+        throw ApiError(MI_EINVAL, "incompatible model: the output must hold D >= 1 values per frame ([1,D] or [1,1,1,D])");
+    h->features = static_cast<int>(D);
+}
+
+int mi_fe_create_from_bytes(const uint8_t* tflite, size_t nbytes, int device, mi_fe** out) {
+    return guarded([&] {
+        require(tflite && nbytes && out, "null argument");
+        auto h = std::make_unique<mi_fe>();
+        h->model.m = std::make_unique<mi::Model>(tflite, nbytes, device);
+        fe_finish_create(h.get());
+        *out = h.release();
+    });
+}
+
+int mi_fe_create(const char* model_path, int device, mi_fe** out) {
+    return guarded([&] {
+        require(out, "null argument");
+        auto bytes = read_file(model_path ? model_path : "./models/face_embeddings.tflite");  // face_embeddings.rs:33-37
+        auto h = std::make_unique<mi_fe>();
+        h->model.m = std::make_unique<mi::Model>(bytes.data(), bytes.size(), device);
+        fe_finish_create(h.get());
+        *out = h.release();
+    });
+}
+
+void mi_fe_free(mi_fe* h) { delete h; }
+mi_model* mi_fe_model(mi_fe* h) { return h ? &h->model : nullptr; }
+
+int mi_fe_features(const mi_fe* h, int* features) {
+    return guarded([&] {
+        require(h && features, "null argument");
+        *features = h->features;
+    });
+}
+
+int mi_face_chip_rect(const mi_detection* det, int width, int height, int rect[4], int* valid) {
+    return guarded([&] {
+        require(det && rect && valid, "null argument");
+        require(width > 0 && height > 0, "bad image geometry");
+        *valid = mi::face_chip_rect_det(det->data, width, height, rect);
+    });
+}
+
+int mi_fe_infer_image(mi_fe* h, const uint8_t* rgb, int width, int height, int stride, const double bbox[4], float* embedding, int cap) {
+    return guarded([&] {
+        require(h && rgb && bbox && embedding, "null argument");
+        require(width > 0 && height > 0 && stride >= 3 * static_cast<long>(width), "bad image geometry");
+        require(cap >= h->features, "output capacity is smaller than the model's feature count");
+        int r[4];
+        if (!mi::face_chip_rect_px(bbox, width, height, r))
+            throw ApiError(MI_ERANGE, "bounding box leaves the image or is empty (reference: Mat::roi(..).unwrap() panics, face_embeddings.rs:102-107)");
+        mi::Model& m = *h->model.m;
+        mi::hip_check(hipSetDevice(m.device()), "hipSetDevice");
+        hipStream_t s = m.stream();
+        Use use(h->model, s);
+        const int D = h->features;
+        // only the crop travels: rows y .. y + h - 1 from column x on; the last row owns 3 * w bytes
+        const uint8_t* crop = rgb + static_cast<size_t>(stride) * r[1] + static_cast<size_t>(3) * r[0];
+        const size_t crop_bytes = static_cast<size_t>(stride) * (r[3] - 1) + static_cast<size_t>(3) * r[2];
+        auto* d_crop = static_cast<uint8_t*>(h->d_img.get(crop_bytes));
+        float* d_in = static_cast<float*>(h->d_in.get(m.input_elems() * sizeof(float)));
+        float* d_emb = static_cast<float*>(h->d_emb.get(sizeof(float) * D));
+        mi::hip_check(hipMemcpyAsync(d_crop, crop, crop_bytes, hipMemcpyHostToDevice, s), "H2D crop");
+        mi::chip_tensor_enqueue_one(d_crop, r[2], r[3], stride, d_in, s);
+        m.run_device(d_in, 1, s);
+        mi::launch_l2_norm(m.output_device(0), nullptr, 1, D, d_emb, nullptr, s);
+        mi::hip_check(hipMemcpyAsync(embedding, d_emb, sizeof(float) * D, hipMemcpyDeviceToHost, s), "D2H embedding");
+        mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    });
+}
+
+int mi_fe_infer_face_items(mi_fe* h, const uint8_t* frames, int batch, int width, int height, int stride, const mi_detection* faces, int max_faces,
+                           const int* item_frame, const int* item_face, int max_items, float* embeddings, int* valid, float* raw, float* chips,
+                           int mem, void* stream) {
+    return guarded([&] {
+        // (a budget the launches cannot take is refused here, before anything is queued)
+        require_face_items(batch, max_faces, max_items, mi::kFaceItemsMaxRunItems, "max_items must be 1..32767 (one grid row of a launch per item)");
+        require(h && frames && faces && item_frame && item_face && embeddings && valid, "null argument");
+        require(width > 0 && height > 0 && stride >= 3 * static_cast<long>(width), "bad frame geometry");
+        require(mem == MI_MEM_HOST || mem == MI_MEM_DEVICE, "mem must be MI_MEM_HOST or MI_MEM_DEVICE");
+        static_assert(sizeof(mi_detection) == 17 * sizeof(float), "mi_detection layout");
+        mi::Model& m = *h->model.m;
+        mi::hip_check(hipSetDevice(m.device()), "hipSetDevice");
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m.stream();
+        Use use(h->model, s);
+        const int B = batch, M = max_items, D = h->features;
+        const size_t chip_floats = m.input_elems(), emb_bytes = sizeof(float) * D * M;
+        mi::ChipItems it{};
+        it.frames = frames; it.frame_bytes = static_cast<long>(stride) * height; it.batch = B; it.width = width; it.height = height; it.stride = stride;
+        it.faces = reinterpret_cast<const float*>(faces); it.max_faces = max_faces; it.item_frame = item_frame; it.item_face = item_face; it.N = M;
+        float *d_emb = embeddings, *d_raw = raw;
+        int* d_valid = valid;
+        if (mem == MI_MEM_HOST) {
+            auto staged = [&](DeviceBuf& buf, const void* p, size_t bytes) -> const void* {
+                void* d = buf.get(bytes);
+                mi::hip_check(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, s), "H2D operands");
+                return d;
+            };
+            it.frames = static_cast<const uint8_t*>(h->d_frames.get(static_cast<size_t>(stride) * height * B));
+            mi::hip_check(hipMemcpyAsync(const_cast<uint8_t*>(it.frames), frames, frames_bytes(B, width, height, stride), hipMemcpyHostToDevice, s), "H2D frames");
+            it.faces = static_cast<const float*>(staged(h->d_faces, faces, sizeof(mi_detection) * B * max_faces));
+            it.item_frame = static_cast<const int*>(staged(h->d_item_frame, item_frame, sizeof(int) * M));
+            it.item_face = static_cast<const int*>(staged(h->d_item_face, item_face, sizeof(int) * M));
+            d_emb = static_cast<float*>(h->d_emb.get(emb_bytes));
+            d_raw = raw ? static_cast<float*>(h->d_raw.get(emb_bytes)) : nullptr;
+            d_valid = static_cast<int*>(h->d_valid.get(sizeof(int) * M));
+        }
+        // the network's input is the handle's own buffer whatever `chips` is: the engine keys its captured graphs by that address
+        auto* d_geom = static_cast<mi::ChipGeom*>(h->d_geom.get(sizeof(mi::ChipGeom) * M));
+        float* d_in = static_cast<float*>(h->d_in.get(chip_floats * sizeof(float) * M));
+        mi::launch_chip_geom(it, d_geom, d_valid, s);
+        mi::launch_chip_tensor(it, d_geom, d_in, s);
+        m.run_device(d_in, M, s);
+        mi::launch_l2_norm(m.output_device(0), d_valid, M, D, d_emb, d_raw, s);
+        if (chips) mi::hip_check(hipMemcpyAsync(chips, d_in, chip_floats * sizeof(float) * M, mem == MI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s), "chips copy");
+        if (mem == MI_MEM_HOST) {
+            mi::hip_check(hipMemcpyAsync(embeddings, d_emb, emb_bytes, hipMemcpyDeviceToHost, s), "D2H embeddings");
+            if (raw) mi::hip_check(hipMemcpyAsync(raw, d_raw, emb_bytes, hipMemcpyDeviceToHost, s), "D2H raw");
+            mi::hip_check(hipMemcpyAsync(valid, d_valid, sizeof(int) * M, hipMemcpyDeviceToHost, s), "D2H valid");
+        }
+        if (mem == MI_MEM_HOST || !stream) mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    });
+}
+
+int mi_l2_norm(const float* in, int n, float* out) {
+    return guarded([&] {
+        require(in && out, "null argument");
+        require(n >= 1, "n must be positive");
+        const float norm = mi::embed_sqrt(mi::embed_dot(in, in, n));
+        for (int k = 0; k < n; k++) out[k] = mi::embed_div(in[k], norm);
+    });
+}
+
+int mi_similarity_score(const float* a, const float* b, int n, float* out) {
+    return guarded([&] {
+        require(a && b && out, "null argument");
+        require(n >= 1, "n must be positive");
+        const float dot = mi::embed_dot(a, b, n);
+        const float norm_a = mi::embed_sqrt(mi::embed_dot(a, a, n)), norm_b = mi::embed_sqrt(mi::embed_dot(b, b, n));
+        *out = mi::embed_div(dot, mi::embed_mul(norm_a, norm_b));
+    });
+}
+
+int mi_similarity_matrix(int device, const float* a, int n, const float* b, int m, int features, float* out, int mem, void* stream) {
+    return guarded([&] {
+        require(a && b && out, "null argument");
+        require(n >= 1 && m >= 1, "n and m must be positive");
+        require(features >= 1 && features <= mi::kSimMaxFeatures, "features must be 1..4096");
+        require(mem == MI_MEM_HOST || mem == MI_MEM_DEVICE, "mem must be MI_MEM_HOST or MI_MEM_DEVICE");
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
+            throw ApiError(MI_EDEVICE, "no such HIP device (the similarity matrix runs on the GPU; no CPU fallback exists)");
+        mi::hip_check(hipSetDevice(device), "hipSetDevice");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        DeviceBuf b_a, b_b, b_out;
+        const float *d_a = a, *d_b = b;
+        float* d_out = out;
+        const size_t a_bytes = sizeof(float) * n * features, b_bytes = sizeof(float) * m * features, out_bytes = sizeof(float) * n * static_cast<size_t>(m);
+        if (mem == MI_MEM_HOST) {
+            d_a = static_cast<const float*>(b_a.get(a_bytes));
+            d_b = static_cast<const float*>(b_b.get(b_bytes));
+            d_out = static_cast<float*>(b_out.get(out_bytes));
+            mi::hip_check(hipMemcpyAsync(const_cast<float*>(d_a), a, a_bytes, hipMemcpyHostToDevice, s), "H2D a");
+            mi::hip_check(hipMemcpyAsync(const_cast<float*>(d_b), b, b_bytes, hipMemcpyHostToDevice, s), "H2D b");
+        }
+        mi::launch_similarity(d_a, n, d_b, m, features, d_out, s);
+        if (mem == MI_MEM_HOST) mi::hip_check(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s), "D2H similarity");
+        if (mem == MI_MEM_HOST || !stream) mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
     });
 }
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "face_chip.hpp"
 #include "face_items.hpp"
 #include "roi_dev.hpp"
 
@@ -406,9 +407,83 @@ __global__ __launch_bounds__(kFaceItemsThreads) void face_items_kernel(FaceItems
     if (tid == 0) { a.n_items[0] = n_items[0]; a.n_items[1] = n_items[1]; }
 }
 
+// ---------------------------------------------------------------------------------------------- face chips (face_embeddings.rs:54-55)
+// Eight lanes per item, as pre_geom_kernel: the rectangle (face_chip.hpp), then compute_geom of the crop as a picture of its own.  An item
+// that is unused, points outside the arrays or has a rectangle Mat::roi refuses reads neither its frame nor its detection; its lanes still
+// run the elimination (on a 1 x 1 picture) so that the shuffles stay convergent.
+__global__ __launch_bounds__(64) void chip_geom_kernel(ChipItems it, ChipGeom* geom, int* valid) {
+    const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 3, sub = threadIdx.x & 7;
+    if (i >= it.N) return;   // whole groups of 8 lanes
+    const int b = it.item_frame[i];
+    int rect[4] = {0, 0, 1, 1};
+    int ok = 0;
+    if (b >= 0 && b < it.batch) {
+        const int k = it.item_face[i];
+        if (k >= 0 && k < it.max_faces) ok = face_chip_rect_det(it.faces + ((long)b * it.max_faces + k) * 17, it.width, it.height, rect);
+    }
+    if (!ok) { rect[0] = rect[1] = 0; rect[2] = rect[3] = 1; }
+    ChipGeom c;
+    c.g = compute_geom(rect[2], rect[3], nullptr, kChipSize, kChipSize, false, nullptr, 1, sub);
+    if (!c.g.valid) ok = 0;
+    c.g.valid = ok;
+    c.x = rect[0]; c.y = rect[1]; c.w = rect[2]; c.h = rect[3];
+    if (sub) return;
+    geom[i] = c;
+    valid[i] = ok;
+}
+
+// flip = false, no resize stage (keep_aspect_ratio = false): the warped pixel, then `(pixel as f64 * (1 - 0) / 255.0 + 0) as f32`
+__device__ __forceinline__ void chip_px(const ChipGeom& c, const uint8_t* crop, int stride, int idx, float* __restrict__ o) {
+    if (!c.g.valid) { o[0] = o[1] = o[2] = 0.f; return; }
+    const int y = idx / kChipSize, x = idx - y * kChipSize;
+    const Px p = warp_px(c.g, crop, c.w, c.h, stride, y, x);
+    const double k = 1.0 - 0.0;
+    o[0] = (float)((double)p.r * k / 255.0 + 0.0);
+    o[1] = (float)((double)p.g * k / 255.0 + 0.0);
+    o[2] = (float)((double)p.b * k / 255.0 + 0.0);
+}
+
+__global__ __launch_bounds__(256) void chip_tensor_kernel(ChipItems it, const ChipGeom* __restrict__ geom, float* __restrict__ out) {
+    const int i = blockIdx.y;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= kChipSize * kChipSize) return;
+    const ChipGeom c = geom[i];
+    // (behind c.g.valid: the frame of an unused slot is -1)
+    const uint8_t* crop = c.g.valid ? it.frames + (long)it.item_frame[i] * it.frame_bytes + (long)c.y * it.stride + (long)c.x * 3 : nullptr;
+    chip_px(c, crop, it.stride, idx, out + ((long)i * kChipSize * kChipSize + idx) * 3);
+}
+
+__global__ __launch_bounds__(256) void chip_tensor_one_kernel(ChipGeom c, const uint8_t* __restrict__ crop, int stride, float* __restrict__ out) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= kChipSize * kChipSize) return;
+    chip_px(c, crop, stride, idx, out + (long)idx * 3);
+}
+
 size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 }  // namespace
+
+void launch_chip_geom(const ChipItems& it, ChipGeom* d_geom, int* d_valid, hipStream_t s) {
+    if (it.N <= 0) return;
+    hipLaunchKernelGGL(chip_geom_kernel, dim3((it.N + 7) / 8), dim3(64), 0, s, it, d_geom, d_valid);
+    hip_check(hipGetLastError(), "chip_geom kernel launch");
+}
+
+void launch_chip_tensor(const ChipItems& it, const ChipGeom* d_geom, float* d_out, hipStream_t s) {
+    if (it.N <= 0) return;
+    dim3 grid((kChipSize * kChipSize + 255) / 256, it.N);
+    hipLaunchKernelGGL(chip_tensor_kernel, grid, dim3(256), 0, s, it, d_geom, d_out);
+    hip_check(hipGetLastError(), "chip_tensor kernel launch");
+}
+
+void chip_tensor_enqueue_one(const uint8_t* d_crop, int w, int h, int stride, float* d_out, hipStream_t s) {
+    ChipGeom c;
+    c.g = compute_geom(w, h, nullptr, kChipSize, kChipSize, false);   // same code as the device path
+    if (!c.g.valid) throw std::runtime_error("crop is degenerate (singular perspective transform)");
+    c.x = c.y = 0; c.w = w; c.h = h;
+    hipLaunchKernelGGL(chip_tensor_one_kernel, dim3((kChipSize * kChipSize + 255) / 256), dim3(256), 0, s, c, d_crop, stride, d_out);
+    hip_check(hipGetLastError(), "chip_tensor kernel launch");
+}
 
 void launch_pre_geom(const PreItems& it, PreGeom* d_geom, double* d_padding, hipStream_t s) {
     if (it.N <= 0) return;

@@ -82,4 +82,30 @@ struct FaceItemsArgs {
 };
 void launch_face_items(const FaceItemsArgs& a, hipStream_t s);
 
+// The face chips of FaceEmbeddings::infer (face_embeddings.rs:54-55): crop_image_to_bbox, then image_to_tensor(crop, None, (112, 112), false,
+// (0, 1), false) — a warpPerspective of the WHOLE crop, so BORDER_CONSTANT 0 applies at the crop's edge and no pixel next to the box is sampled.
+// The crop is the picture the warp reads: source pointer at the crop's origin, the crop's own width and height, the frame's stride.
+struct ChipGeom {
+    PreGeom g;              // compute_geom(crop width, crop height, no ROI, 112 x 112, keep_aspect = false); g.valid = 0: the chip is zeros
+    int x, y, w, h;         // the crop (face_chip.hpp)
+};
+struct ChipItems {              // device pointers
+    const uint8_t* frames;      // [batch][height][stride] RGB u8
+    long frame_bytes;
+    int batch, width, height, stride;
+    const float* faces;         // [batch][max_faces][17]
+    int max_faces;
+    const int* item_frame;      // [N]: -1 = unused slot
+    const int* item_face;       // [N]
+    int N;
+};
+// one geometry step per item (eight lanes each): rectangle of faces[item_frame][item_face] and its homography; valid[i] = 0 for an unused
+// slot, an index outside the arrays or a rectangle Mat::roi refuses — neither the frame nor the detection of such an item is read
+void launch_chip_geom(const ChipItems& it, ChipGeom* d_geom, int* d_valid, hipStream_t s);
+// one thread per output pixel; out f32 [N][112][112][3], zeros for an invalid item
+void launch_chip_tensor(const ChipItems& it, const ChipGeom* d_geom, float* d_out, hipStream_t s);
+// The same for ONE crop whose rectangle the host has checked: the geometry (same code, on the host) travels as a kernel argument.  d_crop is
+// the crop's first pixel, rows `stride` bytes apart.
+void chip_tensor_enqueue_one(const uint8_t* d_crop, int w, int h, int stride, float* d_out, hipStream_t s);
+
 }  // namespace mi
