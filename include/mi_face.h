@@ -128,7 +128,9 @@ size_t mi_model_describe(const mi_model *m, char *buf, size_t cap);
  * convolution on f32 tensors, bit-identical results in all three: 1 = on the matrix cores with the window's picture rows kept in registers down a column
  * of 64-pixel tiles (default), 2 = on the matrix cores row-wise, every tile loading the five picture rows of its window, 0 = the packed-FMA kernel;
  * every other value is taken as 1), "stem_run" (output rows per column run of form 1, 1..32; 0 = chosen per launch so that the runs fill the chip, and
- * the row-wise form where that leaves one row per run: a handful of frames).
+ * the row-wise form where that leaves one row per run: a handful of frames), "chain_fixed" (the frame-resident chain launches, chain_kernel: 1 = a launch
+ * whose whole form is one of the detectors' — 16x16x96 between its two stride-2 blocks, or 8x8x96, ReLU in every block and a skip connection in every stride-1 block — takes the
+ * instantiation with that shape as constants (default); 0 = always the generic kernel; bit-identical results).
  * Test hook "test_poison" (0 = off, the default; 1 = 0xFF bytes, a NaN; 2 = 0x7F bytes, 3.39e38): before every run the handle fills its activation
  * arena, its small-batch scratch, its output buffers and, in mi_model_run with host input, its input stage beyond the call's frames — a kernel that
  * reads a byte it did not write first turns up in the results. Weights, programs and the single-launch plan's workspace are never touched.

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "kernels.hpp"
 #include "launch.hpp"
@@ -24,6 +25,7 @@
 namespace mi {
 
 typedef float f32x16c __attribute__((ext_vector_type(16)));
+typedef float f32x2c __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -45,17 +47,92 @@ unsigned long long* g_chain_stamps = nullptr;
 #define MI_CHAIN_STAMP(k)
 #endif
 
+// `pre`'s staging: the fewest passes P whose input rows fit the LDS beside the constants (and `post`'s kept output) and whose 32-pixel
+// groups all find a wave of their own; 0: none.  tile = floats of the resident frame's region, which the staging area shares.
+constexpr int chain_pre_passes(int C, int H, int W, int Cin, int post_Co, int MT, bool split, long tile) {
+    const int pre_RS = (2 * W + 1) * (Cin + 4);
+    for (int P = 1; P <= 4; P++) {
+        const int RP = (H + P - 1) / P, GP = (RP * W + 31) / 32;
+        const long stage = (long)(2 * RP + 1) * pre_RS;
+        const long rest = 9 * C + C + 8 * 32 + 64 + (post_Co ? (long)(H >> 1) * (W >> 1) * (post_Co + 4) : 0);
+        if ((P - 1) * RP < H && P * GP * (split ? MT : 1) <= 8 && ((stage > tile ? stage : tile) + rest) * 4 <= 160 * 1024 - 256) return P;
+    }
+    return 0;
+}
+
+// Geometry policies of chain_kernel.  GeomRun: every size and stride is read from the arguments (any chain make_chain_geom accepts).
+struct GeomRun {
+    [[maybe_unused]] static constexpr bool fixed = false;
+    static constexpr bool all_res = false;  // a stride-1 block's skip connection is looked up per block
+    const ChainArgs& a;
+    const ChainGeom& g;
+    __device__ GeomRun(const ChainArgs& a_, const ChainGeom& g_) : a(a_), g(g_) {}
+    __device__ int C() const { return a.C; }
+    __device__ int H() const { return a.H; }
+    __device__ int W() const { return a.W; }
+    __device__ int pre_on() const { return a.pre.on; }
+    __device__ int pre_Cin() const { return a.pre.Cin; }
+    __device__ int post_on() const { return a.post.on; }
+    __device__ int post_Co() const { return a.post.Co; }
+#define MI_GEOM_FIELD(f) __device__ int f() const { return g.f; }
+    MI_GEOM_FIELD(Cp) MI_GEOM_FIELD(Ch) MI_GEOM_FIELD(C4) MI_GEOM_FIELD(PS) MI_GEOM_FIELD(RS)
+    MI_GEOM_FIELD(off_wdw) MI_GEOM_FIELD(off_bdw) MI_GEOM_FIELD(off_bias) MI_GEOM_FIELD(off_alpha)
+    MI_GEOM_FIELD(pre_P) MI_GEOM_FIELD(pre_RP) MI_GEOM_FIELD(pre_GP) MI_GEOM_FIELD(pre_PS) MI_GEOM_FIELD(pre_RS)
+#undef MI_GEOM_FIELD
+};
+// GeomFixed: one shape as constants (CIN / CO = 0: no `pre` / `post`), every stride-1 block with its skip connection (the skip of `pre` and of
+// `post` stays a run-time flag: BackCamera's `post` has none, Front's has one).  Strides and LDS offsets are
+// immediates: a depthwise tap is one base register plus an offset, the staging loops have constant trip counts, pixel coordinates come
+// from shifts.  The formulas are make_chain_geom's; launch_chain takes this form only where every field equals what that computed.
+template <int C_, int H_, int W_, int CIN, int CO>
+struct GeomFixed {
+    static constexpr bool fixed = true;
+    static constexpr bool all_res = true;
+    struct K {
+        static constexpr int C = C_, H = H_, W = W_, Cp = C, Ch = C / 2, C4 = C / 4, PS = C + 4, RS = (W + 2) * PS, MT = (C + 31) / 32;
+        static constexpr bool split = MT > 1 && ((H * W + 31) / 32) * MT <= 8;
+        static constexpr int pre_on = CIN != 0, pre_Cin = CIN, post_on = CO != 0, post_Co = CO;
+        static constexpr int tile = (H + 2) * RS;
+        static constexpr int pre_PS = CIN + 4, pre_RS = (2 * W + 1) * pre_PS;
+        static constexpr int pre_P = CIN ? chain_pre_passes(C, H, W, CIN, CO, MT, split, tile) : 0;
+        static constexpr int pre_RP = CIN ? (H + pre_P - 1) / pre_P : 0, pre_GP = (pre_RP * W + 31) / 32;
+        static constexpr int stage = CIN ? (2 * pre_RP + 1) * pre_RS : 0;
+        static constexpr int off_wdw = stage > tile ? stage : tile, off_bdw = off_wdw + 9 * Cp, off_bias = (off_bdw + Cp + 3) & ~3;
+        static constexpr int off_alpha = off_bias + MT * 32;
+    };
+    static_assert(!CIN || K::pre_P > 0, "no staging plan for `pre`");
+    __device__ GeomFixed(const ChainArgs&, const ChainGeom&) {}
+#define MI_GEOM_FIELD(f) static constexpr __device__ int f() { return K::f; }
+    MI_GEOM_FIELD(C) MI_GEOM_FIELD(H) MI_GEOM_FIELD(W) MI_GEOM_FIELD(pre_on) MI_GEOM_FIELD(pre_Cin) MI_GEOM_FIELD(post_on) MI_GEOM_FIELD(post_Co)
+    MI_GEOM_FIELD(Cp) MI_GEOM_FIELD(Ch) MI_GEOM_FIELD(C4) MI_GEOM_FIELD(PS) MI_GEOM_FIELD(RS)
+    MI_GEOM_FIELD(off_wdw) MI_GEOM_FIELD(off_bdw) MI_GEOM_FIELD(off_bias) MI_GEOM_FIELD(off_alpha)
+    MI_GEOM_FIELD(pre_P) MI_GEOM_FIELD(pre_RP) MI_GEOM_FIELD(pre_GP) MI_GEOM_FIELD(pre_PS) MI_GEOM_FIELD(pre_RS)
+#undef MI_GEOM_FIELD
+    static bool matches(const ChainArgs& a, const ChainGeom& g) {
+        bool ok = a.C == K::C && a.H == K::H && a.W == K::W && g.Cp == K::Cp && g.Ch == K::Ch && g.C4 == K::C4 && g.PS == K::PS && g.RS == K::RS &&
+                  g.MT == K::MT && (g.split != 0) == K::split && g.off_wdw == K::off_wdw && g.off_bdw == K::off_bdw && g.off_bias == K::off_bias &&
+                  g.off_alpha == K::off_alpha && (a.pre.on != 0) == (CIN != 0) && (a.post.on != 0) == (CO != 0);
+        if (ok && CIN) ok = a.pre.Cin == CIN && g.pre_P == K::pre_P && g.pre_RP == K::pre_RP && g.pre_GP == K::pre_GP && g.pre_PS == K::pre_PS && g.pre_RS == K::pre_RS;
+        if (ok && CO) ok = a.post.Co == CO;
+        for (int k = 0; ok && k < a.nblocks; k++) ok = a.blocks[k].has_res != 0;
+        return ok;
+    }
+};
+constexpr int kActRun = -1;  // chain_kernel's ACT: each block's activation is looked up per block
+
 // SPLIT: frames of so few 32-pixel groups that every stage runs as (group, output tile) units, one per wave (g.split)
-template <int MT, bool SPLIT>
+// GP: geometry policy (above).  ACT: kActRun, or the one activation of every block, `pre` and `post` included (ACT_RELU: a lean epilogue).
+template <int MT, bool SPLIT, class GP = GeomRun, int ACT = kActRun>
 __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    const GP geo(a, g);
     float* tile = lds;  // [(H+2)][(W+2)][PS], zero border
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int pl = lane & 31, h = lane >> 5;
     const int b = blockIdx.x;
     const float* in = a.in + (long)b * a.in_fs;
-    const int rowf4 = a.W * g.C4;
-    const int nch = g.Ch >> 2;
+    const int rowf4 = geo.W() * geo.C4();
+    const int nch = geo.Ch() >> 2;
 
     // small per-block constants -> LDS (depthwise taps [9][Cs] zero-padded to Cp, depthwise bias, pointwise bias, negative slopes).
     // fetch_consts issues the global loads of a stage's constants into registers BEFORE the previous stage computes; commit_consts
@@ -64,39 +141,58 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
     auto fetch_consts = [&](const ChainBlock& cb, int Cs, int Cos, ConstRegs& r) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const int i = tid + 512 * k, c = i % g.Cp;
-            r.w[k] = (i < 9 * g.Cp && c < Cs) ? cb.w_dw[(i / g.Cp) * Cs + c] : 0.f;
+            const int i = tid + 512 * k, c = i % geo.Cp();
+            r.w[k] = (i < 9 * geo.Cp() && c < Cs) ? cb.w_dw[(i / geo.Cp()) * Cs + c] : 0.f;
         }
         r.bdw = (tid < Cs && cb.b_dw) ? cb.b_dw[tid] : 0.f;
         r.bias = (tid < Cos && cb.bias) ? cb.bias[tid] : 0.f;
-        r.alpha = (tid < Cos && cb.act == ACT_PRELU) ? cb.alpha[tid] : (cb.act == ACT_NONE ? 1.f : 0.f);
+        if constexpr (ACT == kActRun) r.alpha = (tid < Cos && cb.act == ACT_PRELU) ? cb.alpha[tid] : (cb.act == ACT_NONE ? 1.f : 0.f);
     };
     auto commit_consts = [&](const ConstRegs& r) {
 #pragma unroll
         for (int k = 0; k < 3; k++)
-            if (tid + 512 * k < 9 * g.Cp) lds[g.off_wdw + tid + 512 * k] = r.w[k];
-        if (tid < g.Cp) lds[g.off_bdw + tid] = r.bdw;
-        if (tid < MT * 32) { lds[g.off_bias + tid] = r.bias; lds[g.off_alpha + tid] = r.alpha; }
+            if (tid + 512 * k < 9 * geo.Cp()) lds[geo.off_wdw() + tid + 512 * k] = r.w[k];
+        if (tid < geo.Cp()) lds[geo.off_bdw() + tid] = r.bdw;
+        if (tid < MT * 32) {
+            lds[geo.off_bias() + tid] = r.bias;
+            if constexpr (ACT == kActRun) lds[geo.off_alpha() + tid] = r.alpha;
+        }
     };
     // pointwise weights, packed [tile][chunk][lane][4] in global memory (L2)
+    unsigned aoff[MT];  // fixed shapes: this lane's offset into chunk 0 of tile m (floats), kept as registers of their own
+#pragma unroll
+    for (int m = 0; m < MT; m++) {
+        aoff[m] = (unsigned)((m * nch * 64 + lane) * 4);
+        if constexpr (GP::fixed) asm volatile("" : "+v"(aoff[m]));
+    }
     auto a_frag = [&](const ChainBlock& cb, int nchk, int j, float4 (&av)[MT]) {
 #ifdef MI_ABL_CHAIN_NOA  // timing ablation (development only): no weight loads inside the contraction
 #pragma unroll
         for (int m = 0; m < MT; m++) { av[m] = make_float4(1.f, 2.f, 3.f, 4.f); asm volatile("" : "+v"(av[m].x), "+v"(av[m].y), "+v"(av[m].z), "+v"(av[m].w)); }
 #else
+        if constexpr (GP::fixed) {  // a wave-uniform address stepped on the scalar unit plus this lane's loop-invariant 32-bit offsets
+            if (nchk == nch) {
+#pragma unroll
+                for (int m = 0; m < MT; m++) av[m] = cld4(cb.w_pw + (long)j * 256 + (size_t)aoff[m]);
+                return;
+            }
+        }
 #pragma unroll
         for (int m = 0; m < MT; m++) av[m] = cld4(cb.w_pw + (((long)m * nchk + j) * 64 + lane) * 4);
 #endif
     };
-    auto mfma_chunk = [&](const float4 (&av)[MT], const float4& bf, auto& D) {
+    // first: the contraction's first chunk, whose first MFMA takes a zero C operand (the accumulators are never cleared by moves)
+    const f32x16c zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    auto mfma_chunk = [&](const float4 (&av)[MT], const float4& bf, auto& D, auto first) {
 #ifdef MI_ABL_CHAIN_NOMFMA  // timing ablation: one VALU op per chunk and tile instead of the four MFMAs
 #pragma unroll
-        for (int m = 0; m < MT; m++) D[m][0] += av[m].x * bf.x + av[m].y * bf.y + av[m].z * bf.z + av[m].w * bf.w;
+        for (int m = 0; m < MT; m++) D[m][0] = (decltype(first)::value ? 0.f : D[m][0]) + (av[m].x * bf.x + av[m].y * bf.y + av[m].z * bf.z + av[m].w * bf.w);
         return;
 #endif
 #pragma unroll
         for (int m = 0; m < MT; m++) {
-            D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].x, bf.x, D[m], 0, 0, 0);
+            if constexpr (decltype(first)::value) D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].x, bf.x, zero16, 0, 0, 0);
+            else D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].x, bf.x, D[m], 0, 0, 0);
             D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].y, bf.y, D[m], 0, 0, 0);
             D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].z, bf.z, D[m], 0, 0, 0);
             D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].w, bf.w, D[m], 0, 0, 0);
@@ -105,16 +201,21 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
     // One 32-pixel group on this wave: depthwise chunk j (4 channels of this lane's k-half) by `dw`, the MFMAs of chunk j
     // interleaved with the depthwise math of chunk j + 1, pointwise weights streamed from L2 one chunk ahead.
     auto contract = [&](const ChainBlock& cb, int nchk, auto&& dw, auto& D) {
+        // the accumulators start from a zero C operand of the first chunk's MFMAs where that chunk is peeled off the loop (the fixed
+        // shapes: nchk is a constant > 1); the generic kernel clears them, which costs it no second copy of the loop body
+        constexpr bool kPeel = GP::fixed;
+        if constexpr (!kPeel) {
 #pragma unroll
-        for (int m = 0; m < MT; m++)
+            for (int m = 0; m < MT; m++)
 #pragma unroll
-            for (int e = 0; e < 16; e++) D[m][e] = 0.f;
+                for (int e = 0; e < 16; e++) D[m][e] = 0.f;
+        }
         float4 bf, av[MT];
         dw(0, bf);
         a_frag(cb, nchk, 0, av);
-        for (int j = 0; j + 1 < nchk; j++) {
+        auto step = [&](int j, auto first) {
             float4 bn, an[MT];
-            mfma_chunk(av, bf, D);
+            mfma_chunk(av, bf, D, first);
             a_frag(cb, nchk, j + 1, an);
             dw(j + 1, bn);
             bf = bn;
@@ -127,8 +228,10 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                 __builtin_amdgcn_sched_group_barrier(0x100, (19 + NM - 1) / NM, 0);  // DS read
                 __builtin_amdgcn_sched_group_barrier(0x002, (20 + NM - 1) / NM, 0);  // VALU
             }
-        }
-        mfma_chunk(av, bf, D);
+        };
+        if constexpr (kPeel) step(0, std::true_type{});
+        for (int j = kPeel ? 1 : 0; j + 1 < nchk; j++) step(j, std::false_type{});
+        mfma_chunk(av, bf, D, std::false_type{});
     };
     // ONE output tile (mt) of a 32-pixel group: the unit of work when a stage has so few pixels that whole groups would leave
     // waves idle (the 8x8 / 6x6 frames, the stride-2 block behind the chain, the output heads).  A unit is only 4 nchk dependent
@@ -140,8 +243,10 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
 #pragma unroll
         for (int j = 0; j < NJ; j++)
             if (j < nchk) aw[j] = cld4(wa + 256 * j);
+        if constexpr (!GP::fixed) {
 #pragma unroll
-        for (int e = 0; e < 16; e++) D1[e] = 0.f;
+            for (int e = 0; e < 16; e++) D1[e] = 0.f;
+        }
         float4 bf;
         dw(0, bf);
 #pragma unroll
@@ -153,7 +258,8 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                 int jn = j + 1;
                 asm volatile("" : "+s"(jn));
                 if (j + 1 < nchk) dw(jn, bn);
-                D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].x, bf.x, D1, 0, 0, 0);
+                if (GP::fixed && j == 0) D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].x, bf.x, zero16, 0, 0, 0);  // (chunk 0 always runs: nchk >= 1)
+                else D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].x, bf.x, D1, 0, 0, 0);
                 D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].y, bf.y, D1, 0, 0, 0);
                 D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].z, bf.z, D1, 0, 0, 0);
                 D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].w, bf.w, D1, 0, 0, 0);
@@ -163,7 +269,19 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
     };
     // bias (+ skip) + activation of the 4 channels ch .. ch + 3 (register quad gq) of this lane, in place
     auto finish1 = [&](f32x16c& D1, int ch, int gq, const float4& skip, float hi) {
-        const float4 bb = cld4(lds + g.off_bias + ch), al = cld4(lds + g.off_alpha + ch);
+        if constexpr (ACT == ACT_RELU) {
+            // the same two adds in the same order, packed, then one max: for finite values the bits of the general form with a slope
+            // of 0 and no upper bound (where v < 0 that one gives 0 + (-0) = +0)
+            const f32x2c* bb = reinterpret_cast<const f32x2c*>(lds + geo.off_bias() + ch);
+            const f32x2c v0 = (f32x2c{D1[4 * gq], D1[4 * gq + 1]} + bb[0]) + f32x2c{skip.x, skip.y};
+            const f32x2c v1 = (f32x2c{D1[4 * gq + 2], D1[4 * gq + 3]} + bb[1]) + f32x2c{skip.z, skip.w};
+            D1[4 * gq] = fmaxf(v0.x, 0.f);
+            D1[4 * gq + 1] = fmaxf(v0.y, 0.f);
+            D1[4 * gq + 2] = fmaxf(v1.x, 0.f);
+            D1[4 * gq + 3] = fmaxf(v1.y, 0.f);
+            return;
+        }
+        const float4 bb = cld4(lds + geo.off_bias() + ch), al = cld4(lds + geo.off_alpha() + ch);
         const float4 v = make_float4(D1[4 * gq] + bb.x + skip.x, D1[4 * gq + 1] + bb.y + skip.y, D1[4 * gq + 2] + bb.z + skip.z, D1[4 * gq + 3] + bb.w + skip.w);
         D1[4 * gq] = fminf(fmaxf(v.x, 0.f) + al.x * fminf(v.x, 0.f), hi);
         D1[4 * gq + 1] = fminf(fmaxf(v.y, 0.f) + al.y * fminf(v.y, 0.f), hi);
@@ -173,39 +291,39 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 
     // this wave's pixel group in the stride-1 blocks; g.split: frames of so few groups that (group, output tile) units fit the 8 waves
-    const int ngrp = (a.H * a.W + 31) >> 5;
+    const int ngrp = (geo.H() * geo.W() + 31) >> 5;
     const int grp_w = SPLIT ? wave % ngrp : wave, mt_w = SPLIT ? wave / ngrp : 0;
     const int q = grp_w * 32 + pl;
-    const bool valid = q < a.H * a.W;
-    const int oy = valid ? q / a.W : 0, ox = valid ? q - (q / a.W) * a.W : 0;
-    const bool wave_active = SPLIT ? wave < ngrp * MT : wave * 32 < a.H * a.W;
-    const int base0 = oy * g.RS + ox * g.PS + h * g.Ch;  // tap (ky, kx) = base0 + ky*RS + kx*PS (input row oy-1+ky at slot oy+ky)
-    float* centre = tile + (oy + 1) * g.RS + (ox + 1) * g.PS;
+    const bool valid = q < geo.H() * geo.W();
+    const int oy = valid ? q / geo.W() : 0, ox = valid ? q - (q / geo.W()) * geo.W() : 0;
+    const bool wave_active = SPLIT ? wave < ngrp * MT : wave * 32 < geo.H() * geo.W();
+    const int base0 = oy * geo.RS() + ox * geo.PS() + h * geo.Ch();  // tap (ky, kx) = base0 + ky*RS + kx*PS (input row oy-1+ky at slot oy+ky)
+    float* centre = tile + (oy + 1) * geo.RS() + (ox + 1) * geo.PS();
 
     MI_CHAIN_STAMP(0)
     ConstRegs cr;
-    if (a.pre.on) {
+    if (geo.pre_on()) {
         // ---- the stride-2 block in front of the chain: its (2H x 2W x Cin) input is staged through the (still empty) tile region in
-        // g.pre_P passes of g.pre_RP output rows — coalesced loads, every byte read once — and its 3x3 stride-2 taps and 2x2 max-pool
+        // geo.pre_P() passes of geo.pre_RP() output rows — coalesced loads, every byte read once — and its 3x3 stride-2 taps and 2x2 max-pool
         // skip are gathered from LDS.  (Gathering them from global memory, 16 bytes per lane and tap, cost one cache-line lookup per
         // lane: 60 us of a 110 us launch.)  Pass p runs on waves [p GP, (p + 1) GP): a wave computes in at most one pass and keeps its
         // result in registers until the staged input is dead; then the tile is cleared and the results become the resident frame.
         const ChainBlock& cb = a.pre.blk;
-        const int Cin = a.pre.Cin, Chp = Cin >> 1, Hi = 2 * a.H, Wi = 2 * a.W, C4i = Cin >> 2;
-        const int PSi = g.pre_PS, RSi = g.pre_RS, rowf4i = Wi * C4i;
+        const int Cin = geo.pre_Cin(), Chp = Cin >> 1, Hi = 2 * geo.H(), Wi = 2 * geo.W(), C4i = Cin >> 2;
+        const int PSi = geo.pre_PS(), RSi = geo.pre_RS(), rowf4i = Wi * C4i;
         const float* src = a.pre.in + (long)b * a.pre.in_fs;
-        fetch_consts(cb, Cin, a.C, cr);
+        fetch_consts(cb, Cin, geo.C(), cr);
         commit_consts(cr);
-        fetch_consts(a.blocks[0], a.C, a.C, cr);  // block 0's constants travel while this stage runs
-        const float* wdw = lds + g.off_wdw;
-        const float* bdw = lds + g.off_bdw;
+        fetch_consts(a.blocks[0], geo.C(), geo.C(), cr);  // block 0's constants travel while this stage runs
+        const float* wdw = lds + geo.off_wdw();
+        const float* bdw = lds + geo.off_bdw();
         f32x16c D[SPLIT ? 1 : MT];
         bool mine = false;
         float* my_centre = tile;
         int my_mt = 0;
-        const int UP = SPLIT ? g.pre_GP * MT : g.pre_GP;  // units (SPLIT) or whole groups per pass
-        for (int p = 0; p < g.pre_P; p++) {
-            const int r0 = p * g.pre_RP, r1 = min(r0 + g.pre_RP, a.H);
+        const int UP = SPLIT ? geo.pre_GP() * MT : geo.pre_GP();  // units (SPLIT) or whole groups per pass
+        for (int p = 0; p < geo.pre_P(); p++) {
+            const int r0 = p * geo.pre_RP(), r1 = min(r0 + geo.pre_RP(), geo.H());
             const int nrows = 2 * (r1 - r0) + 1;  // input rows 2 r0 .. 2 r1 (row Hi and column Wi are the SAME padding: zero)
             if (p) __syncthreads();               // the previous pass has read its rows
             for (int i = tid; i < nrows * rowf4i; i += 512) {
@@ -220,10 +338,10 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
             MI_CHAIN_STAMP(16 + p)
             const int u = wave - p * UP;
             if (u >= 0 && u < UP) {  // wave-uniform
-                const int ugrp = SPLIT ? u % g.pre_GP : u, umt = SPLIT ? u / g.pre_GP : 0;
+                const int ugrp = SPLIT ? u % geo.pre_GP() : u, umt = SPLIT ? u / geo.pre_GP() : 0;
                 const int qp = ugrp * 32 + pl;
-                const bool vp = qp < (r1 - r0) * a.W;
-                const int oyl = vp ? qp / a.W : 0, oxp = vp ? qp - (qp / a.W) * a.W : 0;
+                const bool vp = qp < (r1 - r0) * geo.W();
+                const int oyl = vp ? qp / geo.W() : 0, oxp = vp ? qp - (qp / geo.W()) * geo.W() : 0;
                 const float* t0 = lds + (2 * oyl) * RSi + (2 * oxp) * PSi;  // tap (ky, kx) of this lane's output pixel
                 auto dw = [&](int j, float4& bf) {
                     const int c0 = h * Chp + 4 * j;
@@ -232,7 +350,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                     for (int ky = 0; ky < 3; ky++)
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) {
-                            const float4 w = cld4(wdw + (ky * 3 + kx) * g.Cp + c0);
+                            const float4 w = cld4(wdw + (ky * 3 + kx) * geo.Cp() + c0);
                             const float4 d = cld4(t0 + ky * RSi + kx * PSi + c0);
                             bf.x = fmaf(d.x, w.x, bf.x);
                             bf.y = fmaf(d.y, w.y, bf.y);
@@ -248,7 +366,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
 #pragma unroll
                     for (int gq = 0; gq < 4; gq++) {
                         const int ch = (SPLIT ? umt : m) * 32 + 8 * gq + 4 * h;
-                        if (ch >= a.C) continue;
+                        if (ch >= geo.C()) continue;
                         float4 sk = zero4;
                         if (cb.has_res && ch < Cin) {  // 2x2 max-pool of the input, channels above Cin are the zero pad
                             const float4 s0 = cld4(t0 + ch), s1 = cld4(t0 + PSi + ch), s2 = cld4(t0 + RSi + ch), s3 = cld4(t0 + RSi + PSi + ch);
@@ -259,11 +377,11 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                     }
                 mine = vp;
                 my_mt = umt;
-                my_centre = tile + (r0 + oyl + 1) * g.RS + (oxp + 1) * g.PS;
+                my_centre = tile + (r0 + oyl + 1) * geo.RS() + (oxp + 1) * geo.PS();
             }
         }
         __syncthreads();  // the staged input is dead
-        for (int i = tid; i < ((a.H + 2) * g.RS) >> 2; i += 512) reinterpret_cast<float4*>(tile)[i] = zero4;
+        for (int i = tid; i < ((geo.H() + 2) * geo.RS()) >> 2; i += 512) reinterpret_cast<float4*>(tile)[i] = zero4;
         commit_consts(cr);
         __syncthreads();
         if (mine) {
@@ -272,18 +390,18 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
 #pragma unroll
                 for (int gq = 0; gq < 4; gq++) {
                     const int ch = (SPLIT ? my_mt : m) * 32 + 8 * gq + 4 * h;
-                    if (ch < a.C) *reinterpret_cast<float4*>(my_centre + ch) = make_float4(D[m][4 * gq], D[m][4 * gq + 1], D[m][4 * gq + 2], D[m][4 * gq + 3]);
+                    if (ch < geo.C()) *reinterpret_cast<float4*>(my_centre + ch) = make_float4(D[m][4 * gq], D[m][4 * gq + 1], D[m][4 * gq + 2], D[m][4 * gq + 3]);
                 }
         }
     } else {
         // ---- load the frame (coalesced)
-        fetch_consts(a.blocks[0], a.C, a.C, cr);
-        for (int i = tid; i < ((a.H + 2) * g.RS) >> 2; i += 512) reinterpret_cast<float4*>(tile)[i] = zero4;
+        fetch_consts(a.blocks[0], geo.C(), geo.C(), cr);
+        for (int i = tid; i < ((geo.H() + 2) * geo.RS()) >> 2; i += 512) reinterpret_cast<float4*>(tile)[i] = zero4;
         __syncthreads();
-        for (int i = tid; i < a.H * rowf4; i += 512) {
+        for (int i = tid; i < geo.H() * rowf4; i += 512) {
             int r = i / rowf4, e = i - r * rowf4;
-            int px = e / g.C4, c4 = e - px * g.C4;
-            *reinterpret_cast<float4*>(tile + (r + 1) * g.RS + (px + 1) * g.PS + 4 * c4) = cld4(in + 4 * (long)i);
+            int px = e / geo.C4(), c4 = e - px * geo.C4();
+            *reinterpret_cast<float4*>(tile + (r + 1) * geo.RS() + (px + 1) * geo.PS() + 4 * c4) = cld4(in + 4 * (long)i);
         }
         commit_consts(cr);
     }
@@ -294,32 +412,56 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         const ChainBlock& cb = a.blocks[blk];
         // ---- the next stage's small constants start their trip now (committed to LDS behind this block's barrier)
         const bool more = blk + 1 < a.nblocks;
-        if (more) fetch_consts(a.blocks[blk + 1], a.C, a.C, cr);
-        else if (a.post.on) fetch_consts(a.post.blk, a.C, a.post.Co, cr);
-        const float* wdw = lds + g.off_wdw;
-        const float* bdw = lds + g.off_bdw;
+        if (more) fetch_consts(a.blocks[blk + 1], geo.C(), geo.C(), cr);
+        else if (geo.post_on()) fetch_consts(a.post.blk, geo.C(), geo.post_Co(), cr);
+        const float* wdw = lds + geo.off_wdw();
+        const float* bdw = lds + geo.off_bdw();
+        // fixed shapes: this lane's tap-weight offset as ONE register that already holds the (large) constant part, so that the nine tap
+        // weights and the bias are that register plus an immediate (left to itself the compiler adds the constant again for every tap)
+        int wlane = geo.off_wdw() + h * geo.Ch();
+        if constexpr (GP::fixed) asm volatile("" : "+v"(wlane));
 
         f32x16c D[SPLIT ? 1 : MT];
         if (wave_active) {
             auto dw = [&](int j, float4& bf) {
-                const float* wj = wdw + h * g.Ch + 4 * j;
+                if constexpr (GP::fixed) {
+                    // the same FMAs in the same order, written as the packed pairs the loop is scheduled for
+                    const float* wj = lds + wlane + 4 * j;
+                    const float* tj = tile + base0 + 4 * j;
+                    f32x2c lo = {0.f, 0.f}, up = {0.f, 0.f};
+#pragma unroll
+                    for (int ky = 0; ky < 3; ky++)
+#pragma unroll
+                        for (int kx = 0; kx < 3; kx++) {
+                            const float4 w = cld4(wj + (ky * 3 + kx) * geo.Cp());
+                            const float4 d = cld4(tj + ky * geo.RS() + kx * geo.PS());
+                            lo = __builtin_elementwise_fma(f32x2c{d.x, d.y}, f32x2c{w.x, w.y}, lo);
+                            up = __builtin_elementwise_fma(f32x2c{d.z, d.w}, f32x2c{w.z, w.w}, up);
+                        }
+                    const float4 bb = cld4(wj + 9 * geo.Cp());  // the depthwise bias lies behind the nine taps
+                    lo += f32x2c{bb.x, bb.y};
+                    up += f32x2c{bb.z, bb.w};
+                    bf = make_float4(lo.x, lo.y, up.x, up.y);
+                    return;
+                }
+                const float* wj = wdw + h * geo.Ch() + 4 * j;
                 bf = zero4;
 #ifdef MI_ABL_CHAIN_NODW  // timing ablation: centre tap only
-                bf = cld4(tile + base0 + g.RS + g.PS + 4 * j);
+                bf = cld4(tile + base0 + geo.RS() + geo.PS() + 4 * j);
                 return;
 #endif
 #pragma unroll
                 for (int ky = 0; ky < 3; ky++)
 #pragma unroll
                     for (int kx = 0; kx < 3; kx++) {
-                        const float4 w = cld4(wj + (ky * 3 + kx) * g.Cp);
-                        const float4 d = cld4(tile + base0 + ky * g.RS + kx * g.PS + 4 * j);
+                        const float4 w = cld4(wj + (ky * 3 + kx) * geo.Cp());
+                        const float4 d = cld4(tile + base0 + ky * geo.RS() + kx * geo.PS() + 4 * j);
                         bf.x = fmaf(d.x, w.x, bf.x);
                         bf.y = fmaf(d.y, w.y, bf.y);
                         bf.z = fmaf(d.z, w.z, bf.z);
                         bf.w = fmaf(d.w, w.w, bf.w);
                     }
-                const float4 bb = cld4(bdw + h * g.Ch + 4 * j);
+                const float4 bb = cld4(bdw + h * geo.Ch() + 4 * j);
                 bf.x += bb.x; bf.y += bb.y; bf.z += bb.z; bf.w += bb.w;
             };
             // ---- contraction, then the epilogue into registers (reads x at the centre pixel), written back after the barrier
@@ -331,18 +473,18 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
 #pragma unroll
                 for (int gq = 0; gq < 4; gq++) {
                     const int ch = (SPLIT ? mt_w : m) * 32 + 8 * gq + 4 * h;
-                    if (ch < a.C) finish1(D[m], ch, gq, cb.has_res ? cld4(centre + ch) : zero4, hi);
+                    if (ch < geo.C()) finish1(D[m], ch, gq, (GP::all_res || cb.has_res) ? cld4(centre + ch) : zero4, hi);
                 }
         }
         __syncthreads();  // every wave has read x (and the constants) for this block
-        if (more || a.post.on) commit_consts(cr);
+        if (more || geo.post_on()) commit_consts(cr);
         if (wave_active && valid) {
 #pragma unroll
             for (int m = 0; m < (SPLIT ? 1 : MT); m++)
 #pragma unroll
                 for (int gq = 0; gq < 4; gq++) {
                     const int ch = (SPLIT ? mt_w : m) * 32 + 8 * gq + 4 * h;
-                    if (ch < a.C) *reinterpret_cast<float4*>(centre + ch) = make_float4(D[m][4 * gq], D[m][4 * gq + 1], D[m][4 * gq + 2], D[m][4 * gq + 3]);
+                    if (ch < geo.C()) *reinterpret_cast<float4*>(centre + ch) = make_float4(D[m][4 * gq], D[m][4 * gq + 1], D[m][4 * gq + 2], D[m][4 * gq + 3]);
                 }
         }
         __syncthreads();
@@ -351,20 +493,20 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
     // ---- write the frame back (coalesced 16 B per lane, consecutive addresses)
     if (a.write_out) {
         float* out = a.out + (long)b * a.out_fs;
-        for (int i = tid; i < a.H * rowf4; i += 512) {
+        for (int i = tid; i < geo.H() * rowf4; i += 512) {
             int r = i / rowf4, e = i - r * rowf4;
-            int px = e / g.C4, c4 = e - px * g.C4;
-            *reinterpret_cast<float4*>(out + 4 * (long)i) = cld4(tile + (r + 1) * g.RS + (px + 1) * g.PS + 4 * c4);
+            int px = e / geo.C4(), c4 = e - px * geo.C4();
+            *reinterpret_cast<float4*>(out + 4 * (long)i) = cld4(tile + (r + 1) * geo.RS() + (px + 1) * geo.PS() + 4 * c4);
         }
     }
     MI_CHAIN_STAMP(10)
     int post_units = 0;
-    if (a.post.on) {
+    if (geo.post_on()) {
         // ---- the stride-2 block behind the chain: taps from the resident frame, output straight to global memory
         const ChainBlock& cb = a.post.blk;
-        const int Ho = a.H >> 1, Wo = a.W >> 1, Co = a.post.Co, npo = Ho * Wo;  // constants: committed behind the last block
-        const float* wdw = lds + g.off_wdw;
-        const float* bdw = lds + g.off_bdw;
+        const int Ho = geo.H() >> 1, Wo = geo.W() >> 1, Co = geo.post_Co(), npo = Ho * Wo;  // constants: committed behind the last block
+        const float* wdw = lds + geo.off_wdw();
+        const float* bdw = lds + geo.off_bdw();
         const int ngo = (npo + 31) >> 5, MTo = (Co + 31) >> 5;
         post_units = ngo * MTo;
         for (int u = wave; u < post_units; u += 8) {  // wave-uniform; unit = (32 output pixels, 32 output channels)
@@ -373,17 +515,17 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
             const bool vo = qo < npo;
             const int py = vo ? qo / Wo : 0, px = vo ? qo - (qo / Wo) * Wo : 0;
             // SAME on an even size: taps at image rows 2py .. 2py+2 = tile slots 2py+1 .. 2py+3 (slot H+1 is the zero border)
-            const float* t0 = tile + (2 * py + 1) * g.RS + (2 * px + 1) * g.PS;
+            const float* t0 = tile + (2 * py + 1) * geo.RS() + (2 * px + 1) * geo.PS();
             f32x16c D1;
             auto dw = [&](int j, float4& bf) {
-                const int c0 = h * g.Ch + 4 * j;
+                const int c0 = h * geo.Ch() + 4 * j;
                 bf = cld4(bdw + c0);
 #pragma unroll
                 for (int ky = 0; ky < 3; ky++)
 #pragma unroll
                     for (int kx = 0; kx < 3; kx++) {
-                        const float4 w = cld4(wdw + (ky * 3 + kx) * g.Cp + c0);
-                        const float4 d = cld4(t0 + ky * g.RS + kx * g.PS + c0);
+                        const float4 w = cld4(wdw + (ky * 3 + kx) * geo.Cp() + c0);
+                        const float4 d = cld4(t0 + ky * geo.RS() + kx * geo.PS() + c0);
                         bf.x = fmaf(d.x, w.x, bf.x);
                         bf.y = fmaf(d.y, w.y, bf.y);
                         bf.z = fmaf(d.z, w.z, bf.z);
@@ -398,8 +540,8 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                 const int ch = mt * 32 + 8 * gq + 4 * h;
                 if (ch >= Co) continue;
                 float4 sk = zero4;
-                if (cb.has_res && ch < a.C) {  // 2x2 max-pool of the resident frame, zero channel pad above C
-                    const float4 s0 = cld4(t0 + ch), s1 = cld4(t0 + g.PS + ch), s2 = cld4(t0 + g.RS + ch), s3 = cld4(t0 + g.RS + g.PS + ch);
+                if (cb.has_res && ch < geo.C()) {  // 2x2 max-pool of the resident frame, zero channel pad above C
+                    const float4 s0 = cld4(t0 + ch), s1 = cld4(t0 + geo.PS() + ch), s2 = cld4(t0 + geo.RS() + ch), s3 = cld4(t0 + geo.RS() + geo.PS() + ch);
                     sk = make_float4(fmaxf(fmaxf(s0.x, s1.x), fmaxf(s2.x, s3.x)), fmaxf(fmaxf(s0.y, s1.y), fmaxf(s2.y, s3.y)),
                                      fmaxf(fmaxf(s0.z, s1.z), fmaxf(s2.z, s3.z)), fmaxf(fmaxf(s0.w, s1.w), fmaxf(s2.w, s3.w)));
                 }
@@ -420,8 +562,8 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         if (!H.on) continue;
         if (H.src == 1) { __syncthreads(); post_units = 0; }  // `post`'s LDS copy is complete; heads on the frame itself need no barrier
         const bool from_post = H.src == 1;
-        const int Wh = from_post ? a.W >> 1 : a.W, np = from_post ? (a.H >> 1) * (a.W >> 1) : a.H * a.W;
-        const int Cs = from_post ? a.post.Co : a.C, Chs = Cs >> 1, nchs = Chs >> 2;
+        const int Wh = from_post ? geo.W() >> 1 : geo.W(), np = from_post ? (geo.H() >> 1) * (geo.W() >> 1) : geo.H() * geo.W();
+        const int Cs = from_post ? geo.post_Co() : geo.C(), Chs = Cs >> 1, nchs = Chs >> 2;
         const int Cot = H.Co_a + H.Co_b, MTh = (Cot + 31) >> 5, ng = (np + 31) >> 5;
         // heads on the frame start on the waves that `post` left without a unit
         for (int u = (wave - post_units) & 7; u < ng * MTh; u += 8) {  // wave-uniform
@@ -429,7 +571,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
             const int qh = grp * 32 + pl;
             const bool vh = qh < np;
             const int qc = vh ? qh : 0;
-            const float* px = from_post ? lds + g.off_t8 + qc * (Cs + 4) : tile + (qc / Wh + 1) * g.RS + (qc % Wh + 1) * g.PS;
+            const float* px = from_post ? lds + g.off_t8 + qc * (Cs + 4) : tile + (qc / Wh + 1) * geo.RS() + (qc % Wh + 1) * geo.PS();
             float4 bq[4];
 #pragma unroll
             for (int gq = 0; gq < 4; gq++) bq[gq] = H.bias ? cld4(H.bias + mt * 32 + 8 * gq + 4 * h) : zero4;  // stacked, zero padded to the tile
@@ -469,14 +611,11 @@ bool make_chain_geom(const ChainArgs& a, ChainGeom* out) {
         if (a.pre.Cin % 8 || a.pre.Cin < 8 || a.pre.Cin > a.C) return false;
         g.pre_PS = a.pre.Cin + 4;
         g.pre_RS = (2 * a.W + 1) * g.pre_PS;
-        g.pre_P = 0;
-        for (int P = 1; P <= 4 && !g.pre_P; P++) {
-            const int RP = (a.H + P - 1) / P, GP = (RP * a.W + 31) / 32;
-            const long stage = (long)(2 * RP + 1) * g.pre_RS;
-            const long rest = 9 * g.Cp + g.Cp + 8 * 32 + 64 + (a.post.on ? (long)(a.H >> 1) * (a.W >> 1) * (a.post.Co + 4) : 0);
-            if ((P - 1) * RP < a.H && P * GP * (g.split ? g.MT : 1) <= 8 && (std::max<long>(stage, off) + rest) * 4 <= 160 * 1024 - 256) { g.pre_P = P; g.pre_RP = RP; g.pre_GP = GP; off = (int)std::max<long>(stage, off); }
-        }
+        g.pre_P = chain_pre_passes(a.C, a.H, a.W, a.pre.Cin, a.post.on ? a.post.Co : 0, g.MT, g.split != 0, off);
         if (!g.pre_P) return false;
+        g.pre_RP = (a.H + g.pre_P - 1) / g.pre_P;
+        g.pre_GP = (g.pre_RP * a.W + 31) / 32;
+        off = (int)std::max<long>((long)(2 * g.pre_RP + 1) * g.pre_RS, off);
     }
     g.off_wdw = off; off += 9 * g.Cp;
     g.off_bdw = off; off += g.Cp;
@@ -504,9 +643,18 @@ bool make_chain_geom(const ChainArgs& a, ChainGeom* out) {
     return true;
 }
 
-template <int MT, bool SPLIT>
+using Geom16 = GeomFixed<96, 16, 16, 48, 96>;  // BackCamera, Short / Front: 32x32x48 -> [s2] -> 16x16x96 blocks -> [s2] -> 8x8x96
+using Geom8 = GeomFixed<96, 8, 8, 0, 0>;       // Short / Front: the 8x8x96 blocks behind it (SPLIT)
+
+bool all_relu(const ChainArgs& a) {
+    bool ok = (!a.pre.on || a.pre.blk.act == ACT_RELU) && (!a.post.on || a.post.blk.act == ACT_RELU);
+    for (int k = 0; ok && k < a.nblocks; k++) ok = a.blocks[k].act == ACT_RELU;
+    return ok;
+}
+
+template <int MT, bool SPLIT, class GP = GeomRun, int ACT = kActRun>
 int launch_chain_inst(const ChainArgs& a, const ChainGeom& g, hipStream_t s) {
-    auto kern = chain_kernel<MT, SPLIT>;
+    auto kern = chain_kernel<MT, SPLIT, GP, ACT>;
     if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
     return (int)launch_kernel(kern, dim3((unsigned)a.B), dim3(512), (size_t)g.lds_bytes, s, a, g);
 }
@@ -518,13 +666,19 @@ bool chain_kernel_supports(const ChainArgs& a) {
     return make_chain_geom(a, &g);
 }
 
-int launch_chain(const ChainArgs& a, void* stream) {
+int launch_chain(const ChainArgs& a, void* stream, int fixed) {
     ChainGeom g;
     if (!make_chain_geom(a, &g)) return (int)hipErrorInvalidValue;
 #ifdef MI_CHAIN_STAMPS
     g.stamps = g_chain_stamps;
 #endif
     hipStream_t s = (hipStream_t)stream;
+    // the detectors' shapes as constants, where the whole launch is of that form: the shape, `pre` / `post`, ReLU in every block and a skip
+    // connection in every stride-1 block (the heads stay run-time arguments in both forms).  Same arithmetic in the same order: bit-equal to the generic kernel.
+    if (fixed && all_relu(a)) {
+        if (Geom16::matches(a, g)) return launch_chain_inst<3, false, Geom16, ACT_RELU>(a, g, s);
+        if (Geom8::matches(a, g)) return launch_chain_inst<3, true, Geom8, ACT_RELU>(a, g, s);
+    }
     switch (g.MT) {
         case 1: return launch_chain_inst<1, false>(a, g, s);
         case 2: return g.split ? launch_chain_inst<2, true>(a, g, s) : launch_chain_inst<2, false>(a, g, s);

@@ -1,6 +1,6 @@
 """Per-stage time of the frame-resident chain launch of a model (development aid; needs the stamps build of the library:
 MI_VARIANT=cstamps MI_EXTRA_FLAGS=-DMI_CHAIN_STAMPS bash rs-face-detection-tflite_amd/build.sh).
-usage: python tools/chain_stamps.py back 256"""
+usage: python tools/chain_stamps.py back 256 [option=value ...]   (chain_fixed=0: the generic kernel)"""
 import ctypes as C, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +13,8 @@ name, B = sys.argv[1], int(sys.argv[2])
 files = {"landmark": "face_landmark.tflite", "iris": "iris_landmark.tflite", "back": "face_detection_back.tflite", "front": "face_detection_front.tflite"}
 m = mi.Model(os.path.join(ROOT, "models", files[name]))
 m.set_option("graph", 0)
+for kv in sys.argv[3:]:
+    m.set_option(kv.split("=")[0], int(kv.split("=")[1]))
 print("\n".join(l[:200] for l in m.describe().splitlines() if "frame resident in LDS" in l))
 L = mi.lib()
 buf = torch.zeros(B * 24, dtype=torch.int64, device="cuda")
