@@ -130,7 +130,9 @@ size_t mi_model_describe(const mi_model *m, char *buf, size_t cap);
  * every other value is taken as 1), "stem_run" (output rows per column run of form 1, 1..32; 0 = chosen per launch so that the runs fill the chip, and
  * the row-wise form where that leaves one row per run: a handful of frames), "chain_fixed" (the frame-resident chain launches, chain_kernel: 1 = a launch
  * whose whole form is one of the detectors' — 16x16x96 between its two stride-2 blocks, or 8x8x96, ReLU in every block and a skip connection in every stride-1 block — takes the
- * instantiation with that shape as constants (default); 0 = always the generic kernel; bit-identical results).
+ * instantiation with that shape as constants (default); 0 = always the generic kernel; bit-identical results), "chain_sched" (how those fixed-shape
+ * instantiations schedule a contraction: 1 = in phases — the LDS reads of the next channel chunk requested first, then the chunk's depthwise FMAs as one
+ * block, then its MFMAs as one block (default); 0 = the MFMAs of a chunk interleaved with the next chunk's depthwise taps; bit-identical results).
  * Test hook "test_poison" (0 = off, the default; 1 = 0xFF bytes, a NaN; 2 = 0x7F bytes, 3.39e38): before every run the handle fills its activation
  * arena, its small-batch scratch, its output buffers and, in mi_model_run with host input, its input stage beyond the call's frames — a kernel that
  * reads a byte it did not write first turns up in the results. Weights, programs and the single-launch plan's workspace are never touched.

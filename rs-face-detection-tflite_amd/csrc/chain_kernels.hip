@@ -12,6 +12,8 @@
 //   * per block: depthwise 3x3 on the VALU in the MFMA B-operand layout (lane = pixel x k-half, see block_kernels.hip),
 //     v_mfma_f32_32x32x2_f32 over all output-channel tiles, the MFMAs of channel chunk j interleaved with the depthwise
 //     math of chunk j+1; pointwise weights stream from L2 in A-fragment order, one chunk ahead;
+//     (the fixed-shape instantiations run the same arithmetic in phases instead — reads of chunk j+1 requested, the MFMAs of chunk j as one
+//     block, one wait, the depthwise FMAs of chunk j+1 as one block: SCHED, contract_ph below);
 //   * epilogue values stay in registers across a workgroup barrier (all reads of x done), then overwrite x in place.
 #include <hip/hip_runtime.h>
 
@@ -26,6 +28,7 @@ namespace mi {
 
 typedef float f32x16c __attribute__((ext_vector_type(16)));
 typedef float f32x2c __attribute__((ext_vector_type(2)));
+typedef float f32x4c __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -120,9 +123,51 @@ struct GeomFixed {
 };
 constexpr int kActRun = -1;  // chain_kernel's ACT: each block's activation is looked up per block
 
+// ---- the phased contraction of the fixed shapes (chain_kernel's SCHED = 1).  One channel chunk's depthwise operands: the nine window quads, their
+// nine weight quads and the bias quad.  They are requested by explicit ds_read (left to the compiler, every read is waited for and consumed where
+// it lands, between the MFMAs: a wait for every second read), a whole block of MFMAs ahead of their use; then ONE wait, and the values pass
+// through an empty asm statement behind it, so that their consumers depend on something ordered behind the wait (to the compiler the ds_read
+// "returned" its value at once).  Every wait is lgkmcnt(0): scalar loads share the counter and return out of order.
+struct DwTaps { f32x4c w[9], d[9], b; };
+// byte strides in LDS: from tap to tap of the weights (the bias lies behind the ninth), from row to row and pixel to pixel of the window;
+// BIAS_FIRST: the FMA chain starts from the bias (`pre`, `post`), or from zero with the bias added last (the stride-1 blocks) — the generic kernel's orders
+template <int WS_, int RSB_, int PSB_, bool BIAS_FIRST_>
+struct DwForm { static constexpr int WS = WS_, RSB = RSB_, PSB = PSB_; static constexpr bool bias_first = BIAS_FIRST_; };
+template <int OFF>
+__device__ __forceinline__ void lds_request(unsigned addr, f32x4c& v) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF)); }
+template <class F, int... K>
+__device__ __forceinline__ void dw_request(unsigned wa, unsigned ta, DwTaps& t, std::integer_sequence<int, K...>) {
+    static_assert(9 * F::WS + 16 * 16 < 65536 && 2 * F::RSB + 2 * F::PSB + 16 * 16 < 65536, "ds_read offsets are 16 bits");
+    ((lds_request<K * F::WS>(wa, t.w[K]), lds_request<(K / 3) * F::RSB + (K % 3) * F::PSB>(ta, t.d[K])), ...);
+    lds_request<9 * F::WS>(wa, t.b);
+}
+template <class F>
+__device__ __forceinline__ void dw_request(unsigned wa, unsigned ta, DwTaps& t) { dw_request<F>(wa, ta, t, std::make_integer_sequence<int, 9>{}); }
+__device__ __forceinline__ void dw_landed(DwTaps& t) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < 9; k++) asm volatile("" : "+v"(t.w[k]), "+v"(t.d[k]));
+    asm volatile("" : "+v"(t.b));
+}
+// the chunk's 36 FMAs and 4 adds as 18 + 2 packed instructions over channel pairs, every chain in the generic kernel's order
+template <bool BIAS_FIRST>
+__device__ __forceinline__ void dw_fma(const DwTaps& t, float4& bf) {
+    f32x2c lo = {0.f, 0.f}, up = {0.f, 0.f};
+    if constexpr (BIAS_FIRST) { lo = f32x2c{t.b.x, t.b.y}; up = f32x2c{t.b.z, t.b.w}; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        lo = __builtin_elementwise_fma(f32x2c{t.d[k].x, t.d[k].y}, f32x2c{t.w[k].x, t.w[k].y}, lo);
+        up = __builtin_elementwise_fma(f32x2c{t.d[k].z, t.d[k].w}, f32x2c{t.w[k].z, t.w[k].w}, up);
+    }
+    if constexpr (!BIAS_FIRST) { lo += f32x2c{t.b.x, t.b.y}; up += f32x2c{t.b.z, t.b.w}; }
+    asm volatile("" : "+v"(lo), "+v"(up));  // the chunk's arithmetic ends here, in front of the fence that opens the MFMA block
+    bf = make_float4(lo.x, lo.y, up.x, up.y);
+}
+
 // SPLIT: frames of so few 32-pixel groups that every stage runs as (group, output tile) units, one per wave (g.split)
 // GP: geometry policy (above).  ACT: kActRun, or the one activation of every block, `pre` and `post` included (ACT_RELU: a lean epilogue).
-template <int MT, bool SPLIT, class GP = GeomRun, int ACT = kActRun>
+// SCHED (fixed shapes): 1 = the contractions of `pre`, the blocks and `post` run in phases (contract_ph / contract1_ph), 0 = interleaved (contract / contract1).
+template <int MT, bool SPLIT, class GP = GeomRun, int ACT = kActRun, int SCHED = 0>
 __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const GP geo(a, g);
@@ -267,6 +312,83 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                 __builtin_amdgcn_sched_barrier(0);  // keeps the scheduler from hoisting every chunk's LDS reads to the top (spills)
             }
     };
+    // ---- SCHED = 1: the same contractions in phases.  Chunk j: request chunk j + 1's depthwise operands (LDS) and weight fragments (L2) | the 4 MT
+    // MFMAs of chunk j as one block, which covers those reads | one wait | chunk j + 1's depthwise FMAs as one block of packed instructions.  The
+    // operands of chunk j are dead when those of chunk j + 1 are requested, so one register set serves; the two waves of a SIMD cover each other's
+    // phases.  Switching between FMAs and MFMAs costs issue cycles, and packed FMAs the compiler places behind an MFMA are split in two.
+    // Every FMA chain and every accumulator's k order are those of contract / contract1: bit-identical.
+    [[maybe_unused]] auto lds_addr = [](const float* p) { return (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)const_cast<float*>(p); };
+    // wa / ta: LDS byte addresses of chunk 0's first weight quad and first window quad of this lane; a chunk is 16 bytes further in both
+    [[maybe_unused]] auto contract_ph = [&](auto form, auto nchk_c, const ChainBlock& cb, unsigned wa, unsigned ta, auto& D) {
+        using F = decltype(form);
+        constexpr int NCH = decltype(nchk_c)::value;
+        static_assert(NCH >= 4 && NCH % 2 == 0, "chunks are taken in pairs: the weight fragments alternate between two register sets");
+        DwTaps t;
+        float4 bf, av[2][MT];
+        a_frag(cb, NCH, 0, av[0]);
+        dw_request<F>(wa, ta, t);
+        dw_landed(t);
+        dw_fma<F::bias_first>(t, bf);
+        auto step = [&](int j, const float4 (&ac)[MT], float4 (&an)[MT], auto first, auto last) {
+            if constexpr (!decltype(last)::value) {
+                a_frag(cb, NCH, j + 1, an);
+                dw_request<F>(wa + 16u * (unsigned)(j + 1), ta + 16u * (unsigned)(j + 1), t);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_chunk(ac, bf, D, first);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!decltype(last)::value) {
+                // (the accumulators pass through an empty asm statement: the compiler splits every packed f32 instruction it finds within an
+                // MFMA's latency behind that MFMA in two, unless something in between depends on the MFMA's result)
+#pragma unroll
+                for (int m = 0; m < MT; m++) asm volatile("" : "+v"(D[m]));
+                dw_landed(t);
+                dw_fma<F::bias_first>(t, bf);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        step(0, av[0], av[1], std::true_type{}, std::false_type{});
+        for (int j = 1; j + 2 < NCH; j += 2) {
+            step(j, av[1], av[0], std::false_type{}, std::false_type{});
+            step(j + 1, av[0], av[1], std::false_type{}, std::false_type{});
+        }
+        step(NCH - 1, av[1], av[1], std::false_type{}, std::true_type{});
+    };
+    // one output tile of a group (contract1's unit): every weight fragment in flight up front, the chunks unrolled
+    [[maybe_unused]] auto contract1_ph = [&](auto form, auto nchk_c, const float* w_pw, int mt, unsigned wa, unsigned ta, f32x16c& D1) {
+        using F = decltype(form);
+        constexpr int NCH = decltype(nchk_c)::value;
+        const float* wag = w_pw + ((long)mt * NCH * 64 + lane) * 4;
+        float4 aw[NCH];
+#pragma unroll
+        for (int j = 0; j < NCH; j++) aw[j] = cld4(wag + 256 * j);
+        DwTaps t;
+        float4 bf;
+        dw_request<F>(wa, ta, t);
+        dw_landed(t);
+        dw_fma<F::bias_first>(t, bf);
+#pragma unroll
+        for (int j = 0; j < NCH; j++) {
+            if (j + 1 < NCH) {
+                unsigned jn = 16u * (unsigned)(j + 1);  // opaque, as in contract1: a literal makes every chunk's address a register of its own
+                asm volatile("" : "+s"(jn));
+                dw_request<F>(wa + jn, ta + jn, t);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (j == 0) D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].x, bf.x, zero16, 0, 0, 0);
+            else D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].x, bf.x, D1, 0, 0, 0);
+            D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].y, bf.y, D1, 0, 0, 0);
+            D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].z, bf.z, D1, 0, 0, 0);
+            D1 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[j].w, bf.w, D1, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (j + 1 < NCH) {
+                asm volatile("" : "+v"(D1));  // (as in contract_ph: keeps the packed FMAs behind the MFMAs packed)
+                dw_landed(t);
+                dw_fma<F::bias_first>(t, bf);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
     // bias (+ skip) + activation of the 4 channels ch .. ch + 3 (register quad gq) of this lane, in place
     auto finish1 = [&](f32x16c& D1, int ch, int gq, const float4& skip, float hi) {
         if constexpr (ACT == ACT_RELU) {
@@ -358,7 +480,11 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                             bf.w = fmaf(d.w, w.w, bf.w);
                         }
                 };
-                if constexpr (SPLIT) contract1(cb.w_pw, Chp >> 2, umt, dw, D[0]);
+                if constexpr (SCHED == 1 && !SPLIT) {
+                    using K = typename GP::K;
+                    contract_ph(DwForm<K::Cp * 4, K::pre_RS * 4, K::pre_PS * 4, true>{}, std::integral_constant<int, K::pre_Cin / 8>{}, cb,
+                                lds_addr(wdw + h * Chp), lds_addr(t0 + h * Chp), D);
+                } else if constexpr (SPLIT) contract1(cb.w_pw, Chp >> 2, umt, dw, D[0]);
                 else contract(cb, Chp >> 2, dw, D);
                 const float hi = cb.act == ACT_RELU6 ? 6.f : INFINITY;
 #pragma unroll
@@ -466,7 +592,13 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
             };
             // ---- contraction, then the epilogue into registers (reads x at the centre pixel), written back after the barrier
             const float hi = cb.act == ACT_RELU6 ? 6.f : INFINITY;
-            if constexpr (SPLIT) contract1(cb.w_pw, nch, mt_w, dw, D[0]);
+            if constexpr (SCHED == 1) {
+                using K = typename GP::K;
+                using F = DwForm<K::Cp * 4, K::RS * 4, K::PS * 4, false>;
+                using N = std::integral_constant<int, K::Ch / 4>;
+                if constexpr (SPLIT) contract1_ph(F{}, N{}, cb.w_pw, mt_w, lds_addr(lds + wlane), lds_addr(tile + base0), D[0]);
+                else contract_ph(F{}, N{}, cb, lds_addr(lds + wlane), lds_addr(tile + base0), D);
+            } else if constexpr (SPLIT) contract1(cb.w_pw, nch, mt_w, dw, D[0]);
             else contract(cb, nch, dw, D);
 #pragma unroll
             for (int m = 0; m < (SPLIT ? 1 : MT); m++)
@@ -532,7 +664,11 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                         bf.w = fmaf(d.w, w.w, bf.w);
                     }
             };
-            contract1(cb.w_pw, nch, mt, dw, D1);
+            if constexpr (SCHED == 1) {
+                using K = typename GP::K;
+                contract1_ph(DwForm<K::Cp * 4, K::RS * 4, K::PS * 4, true>{}, std::integral_constant<int, K::Ch / 4>{}, cb.w_pw, mt,
+                             lds_addr(wdw + h * geo.Ch()), lds_addr(t0 + h * geo.Ch()), D1);
+            } else contract1(cb.w_pw, nch, mt, dw, D1);
             const float hi = cb.act == ACT_RELU6 ? 6.f : INFINITY;
             float* dst = a.post.out + (long)b * a.post.out_fs + (long)qo * Co;
 #pragma unroll
@@ -652,9 +788,9 @@ bool all_relu(const ChainArgs& a) {
     return ok;
 }
 
-template <int MT, bool SPLIT, class GP = GeomRun, int ACT = kActRun>
+template <int MT, bool SPLIT, class GP = GeomRun, int ACT = kActRun, int SCHED = 0>
 int launch_chain_inst(const ChainArgs& a, const ChainGeom& g, hipStream_t s) {
-    auto kern = chain_kernel<MT, SPLIT, GP, ACT>;
+    auto kern = chain_kernel<MT, SPLIT, GP, ACT, SCHED>;
     if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
     return (int)launch_kernel(kern, dim3((unsigned)a.B), dim3(512), (size_t)g.lds_bytes, s, a, g);
 }
@@ -666,7 +802,7 @@ bool chain_kernel_supports(const ChainArgs& a) {
     return make_chain_geom(a, &g);
 }
 
-int launch_chain(const ChainArgs& a, void* stream, int fixed) {
+int launch_chain(const ChainArgs& a, void* stream, int fixed, int sched) {
     ChainGeom g;
     if (!make_chain_geom(a, &g)) return (int)hipErrorInvalidValue;
 #ifdef MI_CHAIN_STAMPS
@@ -676,8 +812,9 @@ int launch_chain(const ChainArgs& a, void* stream, int fixed) {
     // the detectors' shapes as constants, where the whole launch is of that form: the shape, `pre` / `post`, ReLU in every block and a skip
     // connection in every stride-1 block (the heads stay run-time arguments in both forms).  Same arithmetic in the same order: bit-equal to the generic kernel.
     if (fixed && all_relu(a)) {
-        if (Geom16::matches(a, g)) return launch_chain_inst<3, false, Geom16, ACT_RELU>(a, g, s);
-        if (Geom8::matches(a, g)) return launch_chain_inst<3, true, Geom8, ACT_RELU>(a, g, s);
+        // sched: the contraction in phases, or interleaved (option "chain_sched"; the same FMA chains and MFMA order in both)
+        if (Geom16::matches(a, g)) return sched ? launch_chain_inst<3, false, Geom16, ACT_RELU, 1>(a, g, s) : launch_chain_inst<3, false, Geom16, ACT_RELU, 0>(a, g, s);
+        if (Geom8::matches(a, g)) return sched ? launch_chain_inst<3, true, Geom8, ACT_RELU, 1>(a, g, s) : launch_chain_inst<3, true, Geom8, ACT_RELU, 0>(a, g, s);
     }
     switch (g.MT) {
         case 1: return launch_chain_inst<1, false>(a, g, s);

@@ -103,6 +103,7 @@ const Model::Option* Model::find_option(const std::string& key) {
         {"pair_fuse", &Model::pair_fuse_, 0, 1, 0},  // 0: two plain blocks in a row keep a launch each (the face mesh's 48x48x32 blocks: mwalk_kernel), no mdblock_kernel<pair>
         {"mdb_band", &Model::mdb_band_, 0, 4096, 0},  // rows per band of the mdblock_kernel launches (0: chosen per launch)
         {"chain_fixed", &Model::chain_fixed_, 0, 1, 0},  // 0: the frame-resident chain launches always take the generic kernel (bit-identical), never a fixed-shape instantiation
+        {"chain_sched", &Model::chain_sched_, 0, 1, 0},  // fixed-shape chain launches: 1 = contraction in phases (LDS reads a chunk ahead, FMAs as a block, MFMAs as a block), 0 = MFMAs interleaved with the next chunk's taps (bit-identical)
         {"mchain", &Model::mchain_, 0, 1, 0},  // 0: the 32x32x48 blocks run one launch each (mstrip_kernel) instead of one launch per run
         {"tail", &Model::tail_, 0, 1, O::kReplan},  // 0: no stage program runs on tail_kernels.hip
         {"tail_pre", &Model::tail_pre_, 0, 2, 0},  // tail programs: 0 = chosen per launch, 1 = constants a stage ahead (one workgroup per CU), 2 = 128 registers (two per CU)
@@ -355,7 +356,7 @@ LaunchCtx Model::launch_ctx(const float* in, int chunk_start, int frames) const 
 }
 
 namespace {
-int issue(const Launch& l, hipStream_t s, int chain_fixed) {
+int issue(const Launch& l, hipStream_t s, int chain_fixed, int chain_sched) {
     auto many = [&](int (*f)(const BlockArgs*, int, void*)) { return f(l.blocks.data(), static_cast<int>(l.blocks.size()), s); };
     switch (l.to) {
         case Launcher::Conv: return launch_conv(std::get<ConvArgs>(l.args), s);
@@ -368,7 +369,7 @@ int issue(const Launch& l, hipStream_t s, int chain_fixed) {
         case Launcher::Bneck: return launch_bneck(std::get<BneckArgs>(l.args), s);
         case Launcher::Tail: return launch_tail(std::get<TailLaunch>(l.args), s);
         case Launcher::Resident: return launch_resident(std::get<ResLaunch>(l.args), s);
-        case Launcher::Chain: return launch_chain(std::get<ChainArgs>(l.args), s, chain_fixed);
+        case Launcher::Chain: return launch_chain(std::get<ChainArgs>(l.args), s, chain_fixed, chain_sched);
         case Launcher::StripPipe: return many(launch_strip_pipe);
         case Launcher::MstripChain: return many(launch_mstrip_chain);
         case Launcher::SmallChain: {
@@ -436,7 +437,7 @@ void Model::enqueue_chunk(const float* in, int chunk_start, int F, hipStream_t t
         // profiling: the launch is repeated between its two marks (a launch never reads what it writes), so that the event bubble
         // between marks is shared by profile_inner_ executions and the per-launch figure approaches rocprofv3's kernel duration
         int rc = 0;
-        for (int rep = 0; rep < (marks ? profile_inner_ : 1) && rc == 0; rep++) rc = issue(l, s, chain_fixed_);
+        for (int rep = 0; rep < (marks ? profile_inner_ : 1) && rc == 0; rep++) rc = issue(l, s, chain_fixed_, chain_sched_);
         if (rc != 0) throw std::runtime_error(std::string("kernel launch failed: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
         if (l.record) hip_check(record_event(event(k), s), "hipEventRecord");
         mark();

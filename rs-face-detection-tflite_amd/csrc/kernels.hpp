@@ -345,7 +345,8 @@ void strip_pack_consts_s2(int C, int Co, const float* w_dw, const float* b_dw, c
 int launch_strip_pipe(const BlockArgs* blocks, int n, void* stream);
 const char* strip_pipe_label(const BlockArgs* blocks, int n, char* buf, size_t cap);
 int strip_pipe_rows_per_step(int H, int hint = 0);
-int launch_chain(const ChainArgs& a, void* stream, int fixed = 1);  // fixed = 0: always the generic kernel (option "chain_fixed")
+// fixed = 0: always the generic kernel (option "chain_fixed"); sched = 0: the fixed-shape kernels with the interleaved contraction (option "chain_sched")
+int launch_chain(const ChainArgs& a, void* stream, int fixed = 1, int sched = 1);
 
 // ---- bottleneck blocks with the wide tensor in registers (bneck_kernels.hip):
 //   r = act1(W1 . x + b1) (C -> Cm);  y = act2(W2 . (DW3x3(r) + b_dw) + b2 + x) (Cm -> C)
