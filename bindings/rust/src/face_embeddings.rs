@@ -137,3 +137,102 @@ pub fn face_chip_rect(detection: &Detection, image_size: (i32, i32)) -> Result<(
     check(unsafe { ffi::mi_face_chip_rect(&det, image_size.0, image_size.1, rect.as_mut_ptr(), &mut valid) })?;
     Ok(((rect[0], rect[1], rect[2], rect[3]), valid != 0))
 }
+
+/// What `topk_select` and `Gallery::topk` return, `k` slots per query row: slots beyond the eligible rows hold -1 / -inf / -1.
+pub struct TopK {
+    pub k: usize,
+    /// `[n][k]` gallery rows, best first
+    pub index: Vec<i32>,
+    /// `[n][k]` their scores: bit for bit what `similarity_matrix` gives at `[i][index]`
+    pub score: Vec<f32>,
+    /// `[n][k]` their labels (`Gallery::topk` only)
+    pub label: Vec<i32>,
+}
+
+/// The selection rule of `Gallery::topk` applied to a score matrix `[n][m]` (`mi_topk_select`: host only, no GPU).  Row `j` is eligible
+/// iff `scores[i][j] > -inf` (NaN and -inf never are); eligible rows by score descending under the plain f32 `>`, ties to the lower `j`.
+pub fn topk_select(scores: &[f32], n: usize, m: usize, k: usize) -> Result<TopK, Error> {
+    if n == 0 || m == 0 || n.checked_mul(m) != Some(scores.len()) || k == 0 || k > 16 {
+        return Err(Error::msg("scores must be [n][m] with n, m >= 1, and k 1..16"));
+    }
+    let mut out = TopK { k, index: vec![0i32; n * k], score: vec![0f32; n * k], label: Vec::new() };
+    check(unsafe { ffi::mi_topk_select(scores.as_ptr(), n as i32, m as i32, k as i32, out.index.as_mut_ptr(), out.score.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// Enrolled embeddings `[m][features]`, copied once into device memory the handle owns, with an `i32` label per row (`None`: the label is
+/// the row index).  `topk` answers "who is this": the `k` best rows of every query by cosine score, on the device, without the `[n][m]`
+/// score matrix ever reaching memory (`mi_gallery_topk`).
+pub struct Gallery {
+    handle: *mut ffi::mi_gallery,
+    rows: usize,
+    features: usize,
+}
+
+unsafe impl Send for Gallery {}
+unsafe impl Sync for Gallery {}
+
+impl Gallery {
+    pub fn new(rows: &[f32], features: usize, labels: Option<&[i32]>) -> Result<Gallery, Error> {
+        Self::new_on_device(rows, features, labels, 0)
+    }
+
+    pub fn new_on_device(rows: &[f32], features: usize, labels: Option<&[i32]>, device: i32) -> Result<Gallery, Error> {
+        if features == 0 || features > 4096 || rows.is_empty() || rows.len() % features != 0 || rows.len() / features > (1 << 24) {
+            return Err(Error::msg("rows must be [m][features] with m 1..2^24 and features 1..4096"));
+        }
+        let m = rows.len() / features;
+        if labels.map_or(false, |l| l.len() != m) {
+            return Err(Error::msg("one label per row is expected"));
+        }
+        let mut handle: *mut ffi::mi_gallery = std::ptr::null_mut();
+        check(unsafe {
+            ffi::mi_gallery_create(device, rows.as_ptr(), m as i32, features as i32, labels.map_or(std::ptr::null(), |l| l.as_ptr()),
+                                   ffi::MI_MEM_HOST, &mut handle)
+        })?;
+        Ok(Gallery { handle, rows: m, features })
+    }
+
+    pub fn rows(&self) -> usize {
+        self.rows
+    }
+
+    pub fn features(&self) -> usize {
+        self.features
+    }
+
+    /// `"splits"`: the column ranges a row of query tiles is spread over (0 = automatic, the default; otherwise 1..64).  The results do
+    /// not depend on it.
+    pub fn set_option(&self, key: &str, value: i32) -> Result<(), Error> {
+        let key = CString::new(key)?;
+        check(unsafe { ffi::mi_gallery_set_option(self.handle, key.as_ptr(), value) })
+    }
+
+    pub fn get_option(&self, key: &str) -> Result<i32, Error> {
+        let key = CString::new(key)?;
+        let mut v: i32 = 0;
+        check(unsafe { ffi::mi_gallery_get_option(self.handle, key.as_ptr(), &mut v) })?;
+        Ok(v)
+    }
+
+    /// `queries` `[n][features]` -> the `k` (1..16) best rows of each.  The embeddings of `FaceEmbeddings::infer_items` are valid queries:
+    /// an invalid item (a row of zeros) matches nobody and comes out as all -1.
+    pub fn topk(&self, queries: &[f32], k: usize) -> Result<TopK, Error> {
+        if queries.is_empty() || queries.len() % self.features != 0 || k == 0 || k > 16 {
+            return Err(Error::msg("queries must be [n][features] with n >= 1, and k 1..16"));
+        }
+        let n = queries.len() / self.features;
+        let mut out = TopK { k, index: vec![0i32; n * k], score: vec![0f32; n * k], label: vec![0i32; n * k] };
+        check(unsafe {
+            ffi::mi_gallery_topk(self.handle, queries.as_ptr(), n as i32, k as i32, out.index.as_mut_ptr(), out.score.as_mut_ptr(),
+                                 out.label.as_mut_ptr(), ffi::MI_MEM_HOST, std::ptr::null_mut())
+        })?;
+        Ok(out)
+    }
+}
+
+impl Drop for Gallery {
+    fn drop(&mut self) {
+        unsafe { ffi::mi_gallery_free(self.handle) }
+    }
+}

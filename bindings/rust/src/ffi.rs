@@ -103,6 +103,7 @@ pub struct mi_render_items_style {
 #[repr(C)] pub struct mi_iris { _private: [u8; 0] }
 #[repr(C)] pub struct mi_pipeline { _private: [u8; 0] }
 #[repr(C)] pub struct mi_fe { _private: [u8; 0] }
+#[repr(C)] pub struct mi_gallery { _private: [u8; 0] }
 
 extern "C" {
     pub fn mi_last_error() -> *const c_char;
@@ -219,4 +220,13 @@ extern "C" {
     pub fn mi_similarity_score(a: *const c_float, b: *const c_float, n: c_int, out: *mut c_float) -> c_int;
     pub fn mi_similarity_matrix(device: c_int, a: *const c_float, n: c_int, b: *const c_float, m: c_int, features: c_int, out: *mut c_float,
                                 mem: c_int, stream: *mut c_void) -> c_int;
+    pub fn mi_topk_select(scores: *const c_float, n: c_int, m: c_int, k: c_int, index: *mut c_int, score: *mut c_float) -> c_int;
+    pub fn mi_gallery_create(device: c_int, rows: *const c_float, m: c_int, features: c_int, labels: *const c_int, mem: c_int,
+                             out: *mut *mut mi_gallery) -> c_int;
+    pub fn mi_gallery_free(g: *mut mi_gallery);
+    pub fn mi_gallery_dims(g: *const mi_gallery, m: *mut c_int, features: *mut c_int) -> c_int;
+    pub fn mi_gallery_set_option(g: *mut mi_gallery, key: *const c_char, value: c_int) -> c_int;
+    pub fn mi_gallery_get_option(g: *mut mi_gallery, key: *const c_char, value: *mut c_int) -> c_int;
+    pub fn mi_gallery_topk(g: *mut mi_gallery, queries: *const c_float, n: c_int, k: c_int, index: *mut c_int, score: *mut c_float,
+                           label: *mut c_int, mem: c_int, stream: *mut c_void) -> c_int;
 }

@@ -25,7 +25,7 @@ pub mod render;
 pub mod utils;
 
 pub use face_detection::{FaceDetection, FaceDetectionModel};
-pub use face_embeddings::{face_chip_rect, FaceEmbeddings, ItemEmbeddings};
+pub use face_embeddings::{face_chip_rect, topk_select, FaceEmbeddings, Gallery, ItemEmbeddings, TopK};
 pub use face_landmark::{face_detection_to_roi, FaceLandmark};
 pub use render::{
     detections_to_render_data, iris_landmarks_to_render_data, landmarks_to_render_data, render_face_items, render_to_image, Annotation,

@@ -418,6 +418,40 @@ int mi_similarity_score(const float *a, const float *b, int n, float *out);
  * caller stream the call is asynchronous. */
 int mi_similarity_matrix(int device, const float *a, int n, const float *b, int m, int features, float *out, int mem, void *stream);
 
+/* ---- Identification: the k best gallery rows of every query, on the device.
+ * The selection rule, stated once (csrc/topk.hpp; this host entry and the kernels go through the same comparator).  For query row i,
+ * gallery row j is ELIGIBLE iff S[i][j] > -INFINITY is true: NaN and -inf are never selected — a zero query or a zero gallery row gives NaN
+ * through the reference's IEEE division and so matches nobody.  Eligible rows are ordered by score descending under the plain f32 `>`
+ * (-0.0 and +0.0 tie), ties by the lower j.  The result is the first k rows of that order; slots beyond the number of eligible rows hold
+ * index -1, score -INFINITY (label -1).  The order is total, so the result is exact: no tolerance applies to it.
+ * Host only, no GPU: the rule applied to a score matrix scores [n][m]; index [n][k], score [n][k].  k 1..16, n, m >= 1. */
+int mi_topk_select(const float *scores, int n, int m, int k, int *index, float *score);
+
+/* A gallery of enrolled embeddings.  rows f32 [m][features] (follows `mem`) are copied ONCE into device memory the handle owns — a
+ * host-memory caller does not upload them again on every call; labels int [m] or NULL (the label of a row is its index), HOST memory.
+ * The handle also owns the scratch of a call (the partial lists of the kernels' first phase), which has to outlive an asynchronous call.
+ * m 1..2^24, features 1..4096 (as mi_similarity_matrix).  MI_EINVAL for a bad argument before anything else; MI_EDEVICE without such a
+ * device. */
+typedef struct mi_gallery mi_gallery;
+int mi_gallery_create(int device, const float *rows, int m, int features, const int *labels, int mem, mi_gallery **out);
+void mi_gallery_free(mi_gallery *g);
+int mi_gallery_dims(const mi_gallery *g, int *m, int *features);
+/* "splits": the column ranges a row of query tiles (128 queries) is spread over, one workgroup each: 0 = automatic (the default: the
+ * smallest count with which the launch has a workgroup for every compute unit), otherwise 1..64, clamped to the number of 128-column
+ * tiles.  The results do not depend on it.  Any other key is MI_EINVAL. */
+int mi_gallery_set_option(mi_gallery *g, const char *key, int value);
+int mi_gallery_get_option(mi_gallery *g, const char *key, int *value);
+/* queries f32 [n][features]; index / score / label [n][k] (label may be NULL); k 1..16, n >= 1; all pointers follow `mem`.
+ * score[i][r] is BIT FOR BIT the value mi_similarity_matrix writes at [i][index[i][r]] for the same operands (both kernels run one tile
+ * body), the selection is the rule of mi_topk_select, label[i][r] = labels[index[i][r]], or -1 with index -1.  The [n][m] score matrix
+ * never reaches memory: two launches (partial lists per column range, then a merge that writes every one of the n * k slots).
+ * The embeddings of mi_fe_infer_face_items ([max_items][D], zeros for invalid items) are a valid `queries` as they lie in device memory:
+ * invalid items come out as all -1.
+ * Concurrency as the other handles: calls on one gallery are serialised, a call on a different caller stream first waits on the device
+ * for the previous one, and with MI_MEM_DEVICE and a caller stream nothing synchronises with the host but the regrowth of scratch when
+ * n * splits * k grows.  Argument checks are MI_EINVAL before anything is queued. */
+int mi_gallery_topk(mi_gallery *g, const float *queries, int n, int k, int *index, float *score, int *label, int mem, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Host-side helpers the reference exports next to the three structs
  * ---------------------------------------------------------------------------------------------------------------- */

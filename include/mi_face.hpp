@@ -473,6 +473,66 @@ inline void similarity_matrix(const float* a, int n, const float* b, int m, int 
     detail::check(mi_similarity_matrix(device, a, n, b, m, features, out, mem, stream));
 }
 
+// The selection rule of Gallery::topk applied to a score matrix scores [n][m] (mi_topk_select: host only, no GPU): index [n][k], score [n][k]
+struct TopK {
+    int k = 0;
+    std::vector<int> index;     // [n][k], -1 beyond the eligible rows
+    std::vector<float> score;   // [n][k], -INFINITY there
+    std::vector<int> label;     // [n][k], -1 there (Gallery::topk only)
+};
+inline TopK topk_select(const std::vector<float>& scores, int n, int m, int k) {
+    if (n < 1 || m < 1 || scores.size() != static_cast<std::size_t>(n) * m) throw std::invalid_argument("topk_select: scores must be [n][m]");
+    TopK o;
+    o.k = k;
+    o.index.resize(static_cast<std::size_t>(n) * (k > 0 ? k : 0));
+    o.score.resize(o.index.size());
+    detail::check(mi_topk_select(scores.data(), n, m, k, o.index.data(), o.score.data()));
+    return o;
+}
+// mi_gallery: enrolled embeddings rows [m][features], copied once into device memory the handle owns, and an int label per row (empty: the
+// label is the row index).  topk answers "who is this": the k best rows of every query by cosine score — bit for bit similarity_matrix's
+// scores, the rule of topk_select — without the [n][m] matrix ever reaching memory.
+class Gallery {
+   public:
+    Gallery(const float* rows, int m, int features, const std::vector<int>& labels = {}, int mem = MI_MEM_HOST, int device = 0) {
+        if (!labels.empty() && labels.size() != static_cast<std::size_t>(m > 0 ? m : 0)) throw std::invalid_argument("Gallery: one label per row is expected");
+        detail::check(mi_gallery_create(device, rows, m, features, labels.empty() ? nullptr : labels.data(), mem, &h_));
+        detail::check(mi_gallery_dims(h_, &m_, &features_));
+    }
+    ~Gallery() { mi_gallery_free(h_); }
+    Gallery(const Gallery&) = delete;
+    Gallery& operator=(const Gallery&) = delete;
+    int rows() const { return m_; }
+    int features() const { return features_; }
+    // "splits": column ranges a row of query tiles is spread over (0 = automatic, otherwise 1..64); the results do not depend on it
+    void set_option(const char* key, int value) { detail::check(mi_gallery_set_option(h_, key, value)); }
+    int get_option(const char* key) const {
+        int v = 0;
+        detail::check(mi_gallery_get_option(h_, key, &v));
+        return v;
+    }
+    // queries [n][features] in host memory -> index / score / label [n][k]
+    TopK topk(const float* queries, int n, int k) const {
+        if (n < 1 || k < 1 || k > 16) throw std::invalid_argument("Gallery::topk: n >= 1 and k 1..16 are expected");
+        TopK o;
+        o.k = k;
+        o.index.resize(static_cast<std::size_t>(n) * k);
+        o.score.resize(o.index.size());
+        o.label.resize(o.index.size());
+        detail::check(mi_gallery_topk(h_, queries, n, k, o.index.data(), o.score.data(), o.label.data(), MI_MEM_HOST, nullptr));
+        return o;
+    }
+    // the same wherever the operands live (`mem`); label may be null; asynchronous with MI_MEM_DEVICE and a caller stream.  The embeddings
+    // of FaceEmbeddings' item entry are a valid `queries` as they lie in device memory: invalid items come out as all -1.
+    void topk(const float* queries, int n, int k, int* index, float* score, int* label, int mem, void* stream = nullptr) const {
+        detail::check(mi_gallery_topk(h_, queries, n, k, index, score, label, mem, stream));
+    }
+
+   private:
+    mi_gallery* h_ = nullptr;
+    int m_ = 0, features_ = 0;
+};
+
 // render.rs on the device (include/mi_face.h, "render.rs").  Colors::{BLACK, ...} (render.rs:28-68) as the bytes render_to_image writes.
 struct Colors {
     static constexpr mi_color BLACK = MI_COLOR_BLACK, RED = MI_COLOR_RED, GREEN = MI_COLOR_GREEN, BLUE = MI_COLOR_BLUE, PINK = MI_COLOR_PINK,

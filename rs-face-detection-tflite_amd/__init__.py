@@ -12,4 +12,5 @@ from .api import (  # noqa: F401
     ANN_FILLED_RECTS, ANN_LINES, ANN_POINTS, ANN_RECTS, Annotation, Color, Colors, RenderStyle, render_annotations, render_faces,
     RenderItemsStyle, render_face_items,
     FE_CHIP_SIZE, FaceEmbeddings, face_chip_rect, l2_norm, similarity_score, similarity_matrix,
+    TOPK_MAX_K, Gallery, topk_select,
 )

@@ -44,6 +44,7 @@ EXPORTS = [
     "mi_render_annotations", "mi_render_faces", "mi_render_face_items",
     "mi_fe_create", "mi_fe_create_from_bytes", "mi_fe_free", "mi_fe_model", "mi_fe_features", "mi_face_chip_rect", "mi_fe_infer_image",
     "mi_fe_infer_face_items", "mi_l2_norm", "mi_similarity_score", "mi_similarity_matrix",
+    "mi_topk_select", "mi_gallery_create", "mi_gallery_free", "mi_gallery_dims", "mi_gallery_set_option", "mi_gallery_get_option", "mi_gallery_topk",
 ]
 
 
@@ -338,6 +339,14 @@ def lib():
     L.mi_l2_norm.argtypes = [vp, C.c_int, vp]
     L.mi_similarity_score.argtypes = [vp, vp, C.c_int, fp]
     L.mi_similarity_matrix.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]
+    L.mi_topk_select.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.mi_gallery_create.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(vp)]
+    L.mi_gallery_free.argtypes = [vp]
+    L.mi_gallery_free.restype = None
+    L.mi_gallery_dims.argtypes = [vp, ip, ip]
+    L.mi_gallery_set_option.argtypes = [vp, C.c_char_p, C.c_int]
+    L.mi_gallery_get_option.argtypes = [vp, C.c_char_p, ip]
+    L.mi_gallery_topk.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     _lib = L
     return L
 
@@ -1309,6 +1318,102 @@ def similarity_matrix(a, b, device=0, stream=None):
     _check(lib().mi_similarity_matrix(int(device), _ptr(a)[0], int(a.shape[0]), _ptr(b)[0], int(b.shape[0]), int(a.shape[1]), _ptr(out)[0], mem,
                                       C.c_void_p(stream or 0)))
     return out
+
+
+TOPK_MAX_K = 16
+
+
+def topk_select(scores, k):
+    """mi_topk_select (host only, no GPU): the selection rule of Gallery.topk applied to a score matrix [n, m] -> (index [n, k] int32,
+    score [n, k] float32).  Row j is eligible iff scores[i, j] > -inf (NaN and -inf never are); eligible rows by score descending under the
+    plain float32 `>`, ties to the lower j; slots beyond the eligible rows hold -1 / -inf.  k 1..16."""
+    s = np.ascontiguousarray(scores, np.float32)
+    if s.ndim != 2:
+        raise ValueError("scores must be [n, m]")
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError("k must be 1..16")
+    n, m = s.shape
+    index, score = np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+    _check(lib().mi_topk_select(C.c_void_p(s.ctypes.data), n, m, k, C.c_void_p(index.ctypes.data), C.c_void_p(score.ctypes.data)))
+    return index, score
+
+
+class Gallery:
+    """mi_gallery: enrolled embeddings `rows` [m, D] (numpy, or a CUDA tensor), copied once into device memory the handle owns, with an int
+    label per row (None: the label is the row index).  topk() answers "who is this": the k best rows of every query by cosine score, on the
+    device, without the [n, m] score matrix ever reaching memory.  m 1..2^24, D 1..4096."""
+
+    def __init__(self, rows, labels=None, device=0):
+        self.L, self.device, self.h = lib(), int(device), C.c_void_p()
+        if _is_torch(rows) and rows.is_cuda:
+            if rows.dim() != 2 or not rows.is_contiguous():
+                raise ValueError("rows must be a contiguous 2-d tensor")
+            _device_ready(rows, self.device)
+        else:
+            rows = np.ascontiguousarray(rows, np.float32)
+            if rows.ndim != 2:
+                raise ValueError("rows must be [m, D]")
+        m, D = int(rows.shape[0]), int(rows.shape[1])
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, np.int32)
+            if lab.shape != (m,):
+                raise ValueError("labels must be [m]")
+        p, mem = _ptr(rows)
+        _check(self.L.mi_gallery_create(self.device, p, m, D, C.c_void_p(lab.ctypes.data) if lab is not None else None, mem, C.byref(self.h)))
+        self.m, self.features = m, D
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mi_gallery_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_option(self, key, value):
+        """"splits": the column ranges a row of query tiles is spread over (0 = automatic, the default; otherwise 1..64, clamped to the
+        number of 128-column tiles).  The results do not depend on it."""
+        _check(self.L.mi_gallery_set_option(self.h, key.encode(), int(value)))
+
+    def get_option(self, key):
+        v = C.c_int()
+        _check(self.L.mi_gallery_get_option(self.h, key.encode(), C.byref(v)))
+        return v.value
+
+    def topk(self, queries, k=1, stream=None):
+        """mi_gallery_topk: queries [n, D] -> (index [n, k] int32, score [n, k] float32, label [n, k] int32).  score[i, r] is bit for bit
+        what similarity_matrix gives at [i, index[i, r]]; the selection is topk_select's.  numpy in -> numpy out; a CUDA tensor in (for
+        instance the embeddings of FaceEmbeddings.infer_face_items as they lie there: invalid items come out all -1) -> CUDA tensors,
+        asynchronous with a caller stream."""
+        k = int(k)
+        if not 1 <= k <= TOPK_MAX_K:
+            raise ValueError("k must be 1..16")
+        if _is_torch(queries) and queries.is_cuda:
+            import torch
+            if queries.dim() != 2 or not queries.is_contiguous():
+                raise ValueError("queries must be a contiguous 2-d CUDA tensor")
+            _device_ready(queries, self.device)
+            empty = lambda dtype: torch.empty((int(queries.shape[0]), k), dtype=dtype, device=queries.device)
+            kinds = (torch.int32, torch.float32, torch.int32)
+        else:
+            queries = np.ascontiguousarray(queries, np.float32)
+            if queries.ndim != 2:
+                raise ValueError("queries must be [n, D]")
+            empty = lambda dtype: np.empty((queries.shape[0], k), dtype)
+            kinds = (np.int32, np.float32, np.int32)
+        if int(queries.shape[1]) != self.features:
+            raise ValueError("queries must have the gallery's %d features" % self.features)
+        if int(queries.shape[0]) < 1:
+            raise ValueError("queries must hold at least one row")
+        index, score, label = (empty(t) for t in kinds)
+        p, mem = _ptr(queries)
+        _check(self.L.mi_gallery_topk(self.h, p, int(queries.shape[0]), k, _ptr(index)[0], _ptr(score)[0], _ptr(label)[0], mem, C.c_void_p(stream or 0)))
+        return index, score, label
 
 
 def _pipeline_submit_jpeg(self, slot, im_bytes):

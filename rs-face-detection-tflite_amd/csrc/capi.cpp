@@ -31,6 +31,7 @@
 #include "jpeg.hpp"
 #include "preproc.hpp"
 #include "render.hpp"
+#include "topk.hpp"
 
 namespace {
 
@@ -394,6 +395,17 @@ struct mi_fe {
     mi_model model;
     int features = 0;   // D
     DeviceBuf d_in, d_geom, d_valid, d_img, d_frames, d_faces, d_item_frame, d_item_face, d_emb, d_raw;
+};
+
+// A gallery of enrolled embeddings (mi_gallery_topk): the rows and labels in device memory, uploaded once, and the scratch of a call —
+// the partial lists of phase 1 and, for host-memory callers, the staged operands — which has to outlive an asynchronous call.
+// `sync` is the other handles' contract (mutex, event of the last call); it carries no network.
+struct mi_gallery {
+    mi_model sync;
+    int device = 0, m = 0, features = 0;
+    int splits = 0;   // option "splits": 0 = automatic
+    DeviceBuf d_rows, d_labels, d_part, d_queries, d_index, d_score, d_label;
+    bool has_labels = false;
 };
 
 extern "C" {
@@ -2629,6 +2641,103 @@ int mi_similarity_matrix(int device, const float* a, int n, const float* b, int 
         }
         mi::launch_similarity(d_a, n, d_b, m, features, d_out, s);
         if (mem == MI_MEM_HOST) mi::hip_check(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s), "D2H similarity");
+        if (mem == MI_MEM_HOST || !stream) mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    });
+}
+
+int mi_topk_select(const float* scores, int n, int m, int k, int* index, float* score) {
+    return guarded([&] {
+        require(scores && index && score, "null argument");
+        require(n >= 1 && m >= 1, "n and m must be positive");
+        require(k >= 1 && k <= mi::kTopkMaxK, "k must be 1..16");
+        for (long i = 0; i < n; i++) mi::topk_select_row(scores + i * m, m, k, index + i * k, score + i * k);
+    });
+}
+
+int mi_gallery_create(int device, const float* rows, int m, int features, const int* labels, int mem, mi_gallery** out) {
+    return guarded([&] {
+        require(rows && out, "null argument");
+        require(m >= 1 && m <= mi::kGalleryMaxRows, "m must be 1..2^24");
+        require(features >= 1 && features <= mi::kSimMaxFeatures, "features must be 1..4096");
+        require(mem == MI_MEM_HOST || mem == MI_MEM_DEVICE, "mem must be MI_MEM_HOST or MI_MEM_DEVICE");
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
+            throw ApiError(MI_EDEVICE, "no such HIP device (a gallery lives on the GPU; no CPU fallback exists)");
+        mi::hip_check(hipSetDevice(device), "hipSetDevice");
+        auto g = std::make_unique<mi_gallery>();
+        g->device = device;
+        g->m = m;
+        g->features = features;
+        const size_t row_bytes = sizeof(float) * static_cast<size_t>(m) * features;
+        mi::hip_check(hipMemcpy(g->d_rows.get(row_bytes), rows, row_bytes, mem == MI_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice), "gallery rows copy");
+        if (labels) {
+            mi::hip_check(hipMemcpy(g->d_labels.get(sizeof(int) * m), labels, sizeof(int) * m, hipMemcpyHostToDevice), "H2D labels");
+            g->has_labels = true;
+        }
+        *out = g.release();
+    });
+}
+
+void mi_gallery_free(mi_gallery* g) { delete g; }
+
+int mi_gallery_dims(const mi_gallery* g, int* m, int* features) {
+    return guarded([&] {
+        require(g && m && features, "null argument");
+        *m = g->m;
+        *features = g->features;
+    });
+}
+
+int mi_gallery_set_option(mi_gallery* g, const char* key, int value) {
+    return guarded([&] {
+        require(g && key, "null argument");
+        require(std::strcmp(key, "splits") == 0, "unknown option (a gallery has: splits)");
+        require(value >= 0 && value <= mi::kGalleryMaxSplits, "splits must be 0 (automatic) or 1..64");
+        std::lock_guard<std::mutex> lock(g->sync.mu);
+        g->splits = value;
+    });
+}
+
+int mi_gallery_get_option(mi_gallery* g, const char* key, int* value) {
+    return guarded([&] {
+        require(g && key && value, "null argument");
+        require(std::strcmp(key, "splits") == 0, "unknown option (a gallery has: splits)");
+        std::lock_guard<std::mutex> lock(g->sync.mu);
+        *value = g->splits;
+    });
+}
+
+int mi_gallery_topk(mi_gallery* g, const float* queries, int n, int k, int* index, float* score, int* label, int mem, void* stream) {
+    return guarded([&] {
+        require(g && queries && index && score, "null argument");
+        require(n >= 1, "n must be positive");
+        require(k >= 1 && k <= mi::kTopkMaxK, "k must be 1..16");
+        require(mem == MI_MEM_HOST || mem == MI_MEM_DEVICE, "mem must be MI_MEM_HOST or MI_MEM_DEVICE");
+        mi::hip_check(hipSetDevice(g->device), "hipSetDevice");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        Use use(g->sync, s);
+        const int tiles_m = (g->m + 127) / 128;
+        const int splits = g->splits ? (g->splits < tiles_m ? g->splits : tiles_m) : mi::gallery_auto_splits(n, g->m, mi::device_cu_count());
+        const size_t N = static_cast<size_t>(n), out_elems = N * k, q_bytes = sizeof(float) * N * g->features;
+        // (growing frees the old block, which waits for the calls that still use it)
+        auto* d_part = static_cast<mi::TopkPair*>(g->d_part.get(sizeof(mi::TopkPair) * out_elems * splits));
+        const float* d_q = queries;
+        int *d_index = index, *d_label = label;
+        float* d_score = score;
+        if (mem == MI_MEM_HOST) {
+            d_q = static_cast<const float*>(g->d_queries.get(q_bytes));
+            d_index = static_cast<int*>(g->d_index.get(sizeof(int) * out_elems));
+            d_score = static_cast<float*>(g->d_score.get(sizeof(float) * out_elems));
+            if (label) d_label = static_cast<int*>(g->d_label.get(sizeof(int) * out_elems));
+            mi::hip_check(hipMemcpyAsync(const_cast<float*>(d_q), queries, q_bytes, hipMemcpyHostToDevice, s), "H2D queries");
+        }
+        mi::launch_gallery_topk(d_q, n, static_cast<const float*>(g->d_rows.p), g->m, g->features, k, splits,
+                                g->has_labels ? static_cast<const int*>(g->d_labels.p) : nullptr, d_part, d_index, d_score, d_label, s);
+        if (mem == MI_MEM_HOST) {
+            mi::hip_check(hipMemcpyAsync(index, d_index, sizeof(int) * out_elems, hipMemcpyDeviceToHost, s), "D2H index");
+            mi::hip_check(hipMemcpyAsync(score, d_score, sizeof(float) * out_elems, hipMemcpyDeviceToHost, s), "D2H score");
+            if (label) mi::hip_check(hipMemcpyAsync(label, d_label, sizeof(int) * out_elems, hipMemcpyDeviceToHost, s), "D2H label");
+        }
         if (mem == MI_MEM_HOST || !stream) mi::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
     });
 }
