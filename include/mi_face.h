@@ -128,7 +128,10 @@ size_t mi_model_describe(const mi_model *m, char *buf, size_t cap);
  * convolution on f32 tensors, bit-identical results in all three: 1 = on the matrix cores with the window's picture rows kept in registers down a column
  * of 64-pixel tiles (default), 2 = on the matrix cores row-wise, every tile loading the five picture rows of its window, 0 = the packed-FMA kernel;
  * every other value is taken as 1), "stem_run" (output rows per column run of form 1, 1..32; 0 = chosen per launch so that the runs fill the chip, and
- * the row-wise form where that leaves one row per run: a handful of frames), "chain_fixed" (the frame-resident chain launches, chain_kernel: 1 = a launch
+ * the row-wise form where that leaves one row per run: a handful of frames), "conv_mfma" (the dense k x k convolutions of f32 graphs with a multiple of
+ * 32 input channels, overlapping windows (not k x k stride k) and at most a plain skip — the 3x3 convolutions of a ResNet-style embedding network:
+ * 1 = conv_mfma_kernel, an implicit GEMM on the matrix cores (default); 0 = conv_generic_kernel, as before the option existed; each result within the f32
+ * bound of its sum — bit-identical in every case measured so far, which is observed and not promised), "chain_fixed" (the frame-resident chain launches, chain_kernel: 1 = a launch
  * whose whole form is one of the detectors' — 16x16x96 between its two stride-2 blocks, or 8x8x96, ReLU in every block and a skip connection in every stride-1 block — takes the
  * instantiation with that shape as constants (default); 0 = always the generic kernel; bit-identical results), "chain_sched" (how those fixed-shape
  * instantiations schedule a contraction: 1 = in phases — the LDS reads of the next channel chunk requested first, then the chunk's depthwise FMAs as one
@@ -361,7 +364,13 @@ int mi_pipeline_collect_jpeg(mi_pipeline *p, int slot, mi_detection *face, int *
  *
  * The MODEL IS THE CALLER'S: the reference does not ship face_embeddings.tflite (its README tells users to download one), so none is
  * shipped here either, the reference's own model could not be fetched, its operators are unknown and it has never been run on this
- * engine.  Any graph made of the operators the engine lowers loads; another operator is refused with the planner's message.
+ * engine.  Any graph made of the operators the engine lowers loads; another operator is refused with the planner's message.  The operators:
+ * CONV_2D, DEPTHWISE_CONV_2D, FULLY_CONNECTED (weights_format DEFAULT, constant weights and bias, over a [1,K] tensor or the RESHAPE of a
+ * [1,H,W,C] one: it runs as the whole-frame convolution), ADD of two tensors, MUL and ADD by a per-channel or scalar constant (an unfolded batch
+ * normalisation: folded into the convolution in front where nothing else reads it, else one launch with the activation behind it), PRELU, RELU,
+ * fused RELU / RELU6, MAX_POOL_2D, PAD, RESHAPE, CONCATENATION, RESIZE_BILINEAR, DEPTH_TO_SPACE, DEQUANTIZE / DENSIFY of constants.  That is the
+ * operator family of a ResNet-style (ArcFace) float graph; its dense 3x3 convolutions run on the matrix cores (option "conv_mfma").  Not lowered:
+ * SUB / DIV, MEAN / AVERAGE_POOL_2D, L2_NORMALIZATION, TRANSPOSE, MUL of two tensors, quantised graphs.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct mi_fe mi_fe;
 

@@ -394,7 +394,8 @@ class Pipeline {
 
 // FaceEmbeddings (face_embeddings.rs:22-109).  The model is the CALLER'S: the reference ships no face_embeddings.tflite, none is shipped here,
 // and the reference's own model has never been run on this engine; any graph of the operators the engine lowers that maps [1,112,112,3] to
-// one output of D values per frame loads.
+// one output of D values per frame loads.  Those include the family of a ResNet-style (ArcFace) float graph: dense 3x3 CONV_2D (on the matrix
+// cores: option "conv_mfma"), MUL / ADD by per-channel constants (unfolded batch normalisation), PRELU, FULLY_CONNECTED (the list: mi_face.h).
 struct FaceItemEmbeddings {       // mi_fe_infer_face_items, results in host memory
     int features = 0;
     std::vector<float> embeddings;   // [max_items][D], zeros where valid is 0

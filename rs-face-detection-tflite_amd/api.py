@@ -1189,7 +1189,10 @@ FE_CHIP_SIZE = 112   # IMG_SIZE, face_embeddings.rs:20
 class FaceEmbeddings:
     """Face embeddings — mirrors face_embeddings.rs:22-109.  The MODEL IS THE CALLER'S: the reference ships no face_embeddings.tflite (its
     README tells users to download one), none is shipped here, and the reference's own model has never been run on this engine.  Any graph
-    of the operators the engine lowers that maps [1,112,112,3] to one output of D values per frame loads; `features` is D."""
+    of the operators the engine lowers that maps [1,112,112,3] to one output of D values per frame loads; `features` is D.  ResNet-style
+    (ArcFace) float graphs are among them: dense 3x3 CONV_2D (conv_mfma_kernel on the matrix cores; `model.set_option("conv_mfma", 0)` sends
+    them back to the generic kernel), MUL / ADD by per-channel constants, PRELU and a FULLY_CONNECTED head.  Still refused: SUB / DIV, MEAN /
+    AVERAGE_POOL_2D, L2_NORMALIZATION, TRANSPOSE, quantised graphs."""
 
     def __init__(self, model_path=None, device=0, model_bytes=None):
         self.L = lib()

@@ -317,6 +317,11 @@ struct Packer {
         const size_t per_o = static_cast<size_t>(KH) * KW * I;  // (ky, kx, c) keeps its order, o moves inside
         for (size_t k = 0; k < per_o * O; k++) r[k % per_o * Cop + k / per_o] = src[k];
         pc.node_w[i] = put(r);
+        // the dense convolutions conv_mfma_kernel takes read the filter as it is stored, [O][KH*KW*I] (which of the two kernels runs is decided per launch)
+        // (but the k x k stride-k ones, the iris network's 2x2 stride-2 steps: those are the stage programs' gather form, and generic where they run alone)
+        const std::vector<int>&sin = shape(n.in.at(0)), &sout = shape(n.out);
+        const bool whole_frame = sin.size() == 4 && sout.size() == 4 && sin[1] == KH && sin[2] == KW && sout[1] == 1 && sout[2] == 1;   // (a head: the batch GEMM's or the generic kernel's)
+        if (conv_mfma_shape_ok(I, KH, KW, O) && !whole_frame && !(n.sh == KH && n.sw == KW) && (n.res < 0 || n.res_mode == RES_DIRECT)) pc.node_wrows[i] = put(std::vector<float>(src.begin(), src.begin() + static_cast<long>(per_o) * O));
         if (!stem_fuses(i, n)) return;
         std::vector<float> sc(static_cast<size_t>(mdblock_stem_consts_floats()));
         mdblock_pack_stem(src.data(), ptr(n.b, O), n.act == ACT_PRELU ? data(n.alpha, O).data() : nullptr, n.act, sc.data());
@@ -387,7 +392,7 @@ PlanConsts pack_plan_consts(const Plan& plan) {
     PlanConsts pc;
     Packer p{plan, plan.graph, pc};
     const size_t NN = plan.nodes.size();
-    for (std::vector<long>* v : {&pc.node_w, &pc.node_b, &pc.node_w2, &pc.node_b2, &pc.node_alpha, &pc.node_pair, &pc.node_stem, &pc.node_mwalk, &pc.node_chain_pair, &pc.node_strip, &pc.node_prog})
+    for (std::vector<long>* v : {&pc.node_w, &pc.node_b, &pc.node_w2, &pc.node_b2, &pc.node_alpha, &pc.node_pair, &pc.node_wrows, &pc.node_stem, &pc.node_mwalk, &pc.node_chain_pair, &pc.node_strip, &pc.node_prog})
         v->assign(NN, -1);
     for (std::vector<std::vector<MemberOff>>* v : {&pc.chain_off, &pc.chain_head_off}) v->assign(NN, {});
     for (std::vector<std::vector<long>>* v : {&pc.res_wblk, &pc.res_cblob, &pc.tail_wa, &pc.tail_wc}) v->assign(NN, {});
@@ -412,6 +417,7 @@ PlanConsts pack_plan_consts(const Plan& plan) {
             else if (n.kind == Node::Conv) p.conv(i, n);
             else if (n.kind == Node::Dw) pc.node_w[i] = p.put_tensor(n.w);
             else if (n.kind == Node::Block) p.block(i, n);
+            else if (n.kind == Node::Affine) { pc.node_w[i] = p.put(n.scale); pc.node_b[i] = p.put(n.shift); }
         }
     }
     p.plain_pairs();

@@ -22,6 +22,7 @@ struct PlanConsts {
     // per node: float offsets into the blob (-1 none)
     std::vector<long> node_w, node_b, node_w2, node_b2, node_alpha;
     std::vector<long> node_pair;        // pair launch this Block node and the next one share (mdblock_pack_consts, pair form)
+    std::vector<long> node_wrows;       // Conv node with a conv_mfma_kernel form (conv_mfma_shape_ok): the filter [Co][KH*KW*C] as stored; Affine node: node_w = scale, node_b = shift
     std::vector<long> node_stem;        // the first convolution inside the launch of the block pair behind it (mdblock_pack_stem)
     std::vector<long> node_mwalk;       // Block node: mwalk_pack_consts, or ms2_pack_consts for a stride-2 block (a node is one or the other)
     std::vector<long> node_chain_pair;  // Chain node of two plain blocks on a wide layer: mdblock_pack_consts, pair form

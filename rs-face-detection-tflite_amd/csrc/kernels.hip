@@ -654,9 +654,10 @@ static bool pw_few_applicable(const ConvArgs& a) {
            (reinterpret_cast<uintptr_t>(a.in) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.w) & 15) == 0;
 }
 bool conv_takes_u8(const ConvArgs& a) { return stem_applicable(a); }
-const char* conv_kernel_label(const ConvArgs& a) { return stem_applicable(a) ? (stem_mfma_applicable(a) ? "stem_mfma_kernel" : "stem_conv_kernel") : (pw_few_applicable(a) ? "pw_few_kernel" : "conv_generic_kernel"); }
+const char* conv_kernel_label(const ConvArgs& a) { return conv_mfma_supports(a) ? "conv_mfma_kernel" : stem_applicable(a) ? (stem_mfma_applicable(a) ? "stem_mfma_kernel" : "stem_conv_kernel") : (pw_few_applicable(a) ? "pw_few_kernel" : "conv_generic_kernel"); }
 
 int launch_conv(const ConvArgs& a, void* stream) {
+    if (conv_mfma_supports(a)) return launch_conv_mfma(a, stream);
     if (stem_applicable(a)) {
         hipStream_t st = (hipStream_t)stream;
         if (stem_mfma_applicable(a)) return launch_stem_mfma(a, st);
@@ -797,7 +798,7 @@ bool head_gemm_supports(int K, int N) { return K >= 16 && (K % 8) == 0 && N >= 1
 int launch_head_gemm(const HeadGemmArgs& a, void* stream) {
     if (!head_gemm_supports(a.K, a.N) || a.B < 1 || (a.in_fs & 3) || (reinterpret_cast<uintptr_t>(a.in) & 15) || (reinterpret_cast<uintptr_t>(a.w) & 15))
         return (int)hipErrorInvalidValue;
-    if (a.B <= 4) return (int)launch_kernel(head_dot_kernel, dim3((unsigned)((a.N + 3) / 4), (unsigned)a.B), dim3(256), 0, (hipStream_t)stream, a);
+    if (a.B <= 4 && !a.one_form) return (int)launch_kernel(head_dot_kernel, dim3((unsigned)((a.N + 3) / 4), (unsigned)a.B), dim3(256), 0, (hipStream_t)stream, a);
     const unsigned tiles_n = (unsigned)((a.N + 31) / 32);
     return (int)launch_kernel(head_gemm_kernel, dim3((tiles_n + 3) / 4, (unsigned)((a.B + 31) / 32)), dim3(256), 0, (hipStream_t)stream, a);
 }
@@ -819,6 +820,31 @@ __global__ void act_kernel(EltArgs a) {
     int b = (int)(idx / per);
     long e = idx % per;
     a.out[(long)b * a.out_fs + e] = apply_act(a.a[(long)b * a.a_fs + e], a.act, a.alpha, (int)(e % a.C));
+}
+// Per-channel affine, out = act(x * scale[c] + shift[c]) with b = scale, c the last dimension: a MUL and an ADD by constants (a batch normalisation nothing
+// could fold) and the activation behind them as ONE launch.  A separate multiply and add, each rounded, not an fma: the bits of TFLite's two operators.
+// V = 4: float4 accesses (C, the frame strides and the pointers allow it).
+template <int V>
+__global__ __launch_bounds__(256) void affine_kernel(EltArgs a) {
+    const long per = (long)a.H * a.W * a.C / V;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= per * a.B) return;
+    const int b = (int)(idx / per);
+    const long e = (idx % per) * V;
+    const int c = (int)(e % a.C);
+    const float* x = a.a + (long)b * a.a_fs + e;
+    float* o = a.out + (long)b * a.out_fs + e;
+    if (V == 4) {
+        const float4 xv = *reinterpret_cast<const float4*>(x), s = *reinterpret_cast<const float4*>(a.b + c), t = *reinterpret_cast<const float4*>(a.shift + c);
+        float4 r;
+        r.x = apply_act(__fadd_rn(__fmul_rn(xv.x, s.x), t.x), a.act, a.alpha, c);
+        r.y = apply_act(__fadd_rn(__fmul_rn(xv.y, s.y), t.y), a.act, a.alpha, c + 1);
+        r.z = apply_act(__fadd_rn(__fmul_rn(xv.z, s.z), t.z), a.act, a.alpha, c + 2);
+        r.w = apply_act(__fadd_rn(__fmul_rn(xv.w, s.w), t.w), a.act, a.alpha, c + 3);
+        *reinterpret_cast<float4*>(o) = r;
+    } else {
+        *o = apply_act(__fadd_rn(__fmul_rn(*x, a.b[c]), a.shift[c]), a.act, a.alpha, c);
+    }
 }
 // MAX_POOL_2D: p0 = filter_h, p1 = filter_w, p2 = stride_h, p3 = stride_w; SAME/VALID pads folded into Ho/Wo + H/W clip
 __global__ void maxpool_kernel(EltArgs a, int pt, int pl) {
@@ -904,8 +930,18 @@ int launch_add(const EltArgs& a, void* s) {
     return n > 0 ? (int)launch_kernel(add_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)s, a) : 0;
 }
 int launch_act(const EltArgs& a, void* s) {
+    if (a.shift) return launch_affine(a, s);   // a per-channel affine with its activation (Node::Affine)
     long n = (long)a.B * a.H * a.W * a.C;
     return n > 0 ? (int)launch_kernel(act_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)s, a) : 0;
+}
+int launch_affine(const EltArgs& a, void* s) {
+    const long n = (long)a.B * a.H * a.W * a.C;
+    if (n <= 0) return 0;
+    if (!a.b || !a.shift || (a.act == ACT_PRELU && !a.alpha)) return (int)hipErrorInvalidValue;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (a.C % 4 == 0 && a.a_fs % 4 == 0 && a.out_fs % 4 == 0 && al16(a.a) && al16(a.out) && al16(a.b) && al16(a.shift))
+        return (int)launch_kernel(affine_kernel<4>, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)s, a);
+    return (int)launch_kernel(affine_kernel<1>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)s, a);
 }
 int launch_maxpool(const EltArgs& a, void* s) {
     long n = (long)a.B * a.Ho * a.Wo * a.C;

@@ -44,7 +44,10 @@ struct ConvArgs {
     Epilogue ep;
     int no_mfma = 0;            // the 5 x 5 stem: 1 = stays on stem_conv_kernel (engine option "stem_mfma" = 0), 2 = the row-wise MFMA form ("stem_mfma" = 2)
     int stem_run = 0;           // output rows per column run of stem_mfma_kernel (engine option "stem_run"; 0: chosen per launch)
+    const float* w_rows = nullptr;  // the filter as TFLite stores it, [Co][KH*KW*C]: the B operand of conv_mfma_kernel (null: the shape has no such form)
+    int mfma = 0;               // 1: a dense convolution that conv_mfma_kernel takes runs there (engine option "conv_mfma")
 };
+
 
 // Convolution whose window is the whole frame (VALID, H == KH, W == KW: the 3x3-stride-3 mesh head 32 -> 1404, the 2x2 iris
 // heads 128 -> 213 / 15): per frame a matrix-vector product over K = KH*KW*C contiguous floats, so over a batch a plain
@@ -58,6 +61,7 @@ struct HeadGemmArgs {
     long in_fs = 0, out_fs = 0;
     int B = 0, K = 0, N = 0;
     int act = ACT_NONE;
+    int one_form = 0;            // 1: head_gemm_kernel at every batch size (a FULLY_CONNECTED: an item's bits must not depend on how many ran with it)
 };
 
 struct DwArgs {
@@ -148,6 +152,7 @@ struct EltArgs {  // ADD / activation / MAX_POOL / channel PAD / RESIZE / DEPTH_
     int B = 0, H = 0, W = 0, C = 0, Ho = 0, Wo = 0, Co = 0;
     int act = ACT_NONE;
     int p0 = 0, p1 = 0, p2 = 0, p3 = 0;  // op-specific ints (pool filter/stride, pad offsets, block size, flags)
+    const float* shift = nullptr;        // affine_kernel: out = act(a * b[c] + shift[c]), b the scale [C]
 };
 
 struct RectD {  // layout-compatible with mi_rect (include/mi_face.h) / Rect (types.rs:24-36)
@@ -300,6 +305,11 @@ unsigned tail_magic(int d);
 int launch_conv(const ConvArgs& a, void* stream);
 const char* conv_kernel_label(const ConvArgs& a);
 bool conv_takes_u8(const ConvArgs& a);  // the specialised stem kernel: the only convolution with a u8 input form
+// conv_mfma_kernels.hip: implicit-GEMM dense convolution on v_mfma_f32_32x32x2_f32.  conv_mfma_shape_ok: the graph's side of the rule (the constants
+// packer keeps a [Co][K] copy of the filter for such a node); conv_mfma_supports: this launch takes the kernel (launch_conv and conv_kernel_label ask it)
+bool conv_mfma_shape_ok(int C, int KH, int KW, int Co);
+bool conv_mfma_supports(const ConvArgs& a);
+int launch_conv_mfma(const ConvArgs& a, void* stream);
 int launch_dw(const DwArgs& a, void* stream);
 int launch_block(const BlockArgs& a, void* stream);
 bool block_kernel_supports(const BlockArgs& a);
@@ -448,6 +458,7 @@ bool head_gemm_supports(int K, int N);
 bool chain_kernel_supports(const ChainArgs& a);
 int launch_add(const EltArgs& a, void* stream);
 int launch_act(const EltArgs& a, void* stream);
+int launch_affine(const EltArgs& a, void* stream);
 int launch_maxpool(const EltArgs& a, void* stream);
 int launch_padc(const EltArgs& a, void* stream);
 int launch_resize2x(const EltArgs& a, void* stream);

@@ -284,6 +284,11 @@ struct Lowering {
                 if (n.kind == Node::Add) {
                     a.b = tensor_ptr(n.in[1], &a.b_fs);
                     set(l, Launcher::Add, a, lab("add_kernel"));
+                } else if (n.kind == Node::Affine) {
+                    if (si.size() != 4) { a.C = a.Co = si.back(); a.W = a.Wo = a.C > 0 ? static_cast<int>(g.tensors[n.in[0]].elems() / static_cast<size_t>(a.C)) : 0; }
+                    a.b = weights(pc.node_w[i]);
+                    a.shift = weights(pc.node_b[i]);
+                    set(l, Launcher::Act, a, lab("affine_kernel"));   // (launch_act hands EltArgs with a shift to launch_affine)
                 } else if (n.kind == Node::Act) {
                     set(l, Launcher::Act, a, lab("act_kernel"));
                 } else if (n.kind == Node::MaxPool) {
@@ -318,7 +323,8 @@ struct Lowering {
             h.w = c.weights + pc.node_w[i];
             h.bias = ep.bias; h.alpha = ep.alpha; h.act = ep.act;
             h.B = c.F; h.K = si[1] * si[2] * si[3]; h.N = so[3];
-            set(l, Launcher::HeadGemm, h, lab(c.F <= 4 ? "head_dot_kernel" : "head_gemm_kernel"));   // (launch_head_gemm: a handful of frames take the dot-product form)
+            h.one_form = n.fc ? 1 : 0;   // (a FULLY_CONNECTED: an embedding's bits must not depend on how many items ran with it)
+            set(l, Launcher::HeadGemm, h, lab(c.F <= 4 && !n.fc ? "head_dot_kernel" : "head_gemm_kernel"));   // (launch_head_gemm: a handful of frames take the dot-product form)
             return 1;
         }
         // the first convolution inside the launch of the pair of BlazeBlocks behind it (f32 pictures, from 32 frames on: mdblock_kernels.hip, MD::STEM)
@@ -344,6 +350,8 @@ struct Lowering {
         if (n.ept >= 0) { a.pt = n.ept; a.pl = n.epl; }
         a.ep = ep;
         a.no_mfma = c.stem_mfma == 0 ? 1 : c.stem_mfma == 2 ? 2 : 0;
+        a.w_rows = weights(pc.node_wrows[i]);
+        a.mfma = c.conv_mfma ? 1 : 0;
         a.stem_run = c.stem_run;
         if (c.u8_frames && plan.storage[n.in[0]].root == plan.storage[g.inputs[0]].root) {
             if (!conv_takes_u8(a)) throw std::runtime_error("plan: this graph's first convolution has no u8 input form");

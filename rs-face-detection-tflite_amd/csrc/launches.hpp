@@ -47,6 +47,7 @@ struct LaunchCtx {
     int u8_row_bytes = 0;
     // options (engine.cpp, find_option)
     int strip = 1, pair_fuse = 1, stem_fuse = 1, stem_mfma = 1, stem_run = 0, mchain = 1, small_chain = 16, lanes = 1;
+    int conv_mfma = 1;
     int pipe_rows = 0, pipe_band = 0, mdb_band = 0, tail_pre = 0, tail_g = 0;
     bool fork = true;                    // nodes of the side schedule leave the trunk (false: everything in line, no events)
     int cu_count = 256;
@@ -54,7 +55,7 @@ struct LaunchCtx {
     int band_test_absent = 0;
 };
 
-enum class Launcher {  // one per launch_* entry point (kernels.hpp); SmallChain: launch_strip / launch_block once per block of `blocks`
+enum class Launcher {  // one per launch_* entry point (kernels.hpp); SmallChain: launch_strip / launch_block once per block of `blocks`; Act with EltArgs::shift: launch_affine
     Conv, HeadGemm, Dw, Xc, Mdblock, Dblock, Mbneck, Bneck, Tail, Resident, Chain, StripPipe, SmallChain, Ms2, Mwalk, MstripChain, Strip, Mstrip, Block,
     Add, Act, Maxpool, Padc, Resize2x, DepthToSpace, Bandnet
 };

@@ -125,6 +125,136 @@ struct Rewriter {
         }
     }
 
+    int new_const(std::vector<int> shape, std::vector<float> data) {
+        TensorInfo t;
+        t.shape = std::move(shape); t.dtype = 0; t.is_const = true; t.f32 = std::move(data);
+        g.tensors.push_back(std::move(t));
+        return static_cast<int>(g.tensors.size()) - 1;
+    }
+    int new_activation(std::vector<int> shape) {
+        TensorInfo t;
+        t.shape = std::move(shape);
+        g.tensors.push_back(std::move(t));
+        return static_cast<int>(g.tensors.size()) - 1;
+    }
+
+    // Per-channel affines (MUL / ADD by constants: a batch normalisation as the converter leaves it when nothing folds it).
+    //  (a) consecutive affines merge: (x s1 + t1) s2 + t2 = x (s1 s2) + (t1 s2 + t2), the constants computed in double and rounded once;
+    //  (b) an affine behind a convolution / depthwise convolution / FULLY_CONNECTED that has no activation and no skip, and whose output
+    //      nobody else reads, folds into that node: filter row o scaled by s[o], bias b s + t, each product rounded once.  (An affine in
+    //      FRONT of a convolution stays: with SAME padding its shift would have to reach the zero border.)
+    //  (c) an activation that alone reads a remaining affine runs in its launch.
+    void fuse_affines() {
+        for (size_t i = 0; i < nodes.size(); i++) {
+            Node& a = nodes[i];
+            if (a.dead || a.kind != Node::Affine || a.act != ACT_NONE || is_graph_output(a.out)) continue;
+            std::vector<int> cons = consumers(a.out);
+            if (cons.size() != 1 || cons[0] <= static_cast<int>(i)) continue;
+            Node& b = nodes[cons[0]];
+            if (b.kind != Node::Affine || b.in[0] != a.out || b.scale.size() != a.scale.size()) continue;
+            for (size_t c = 0; c < a.scale.size(); c++) {
+                const double s = static_cast<double>(a.scale[c]) * b.scale[c], t = static_cast<double>(a.shift[c]) * b.scale[c] + b.shift[c];
+                b.scale[c] = static_cast<float>(s);
+                b.shift[c] = static_cast<float>(t);
+            }
+            b.in = a.in;
+            b.src_ops.insert(b.src_ops.begin(), a.src_ops.begin(), a.src_ops.end());
+            a.dead = true;
+        }
+        for (size_t i = 0; i < nodes.size(); i++) {
+            const Node& a = nodes[i];
+            if (a.dead || a.kind != Node::Affine) continue;
+            const int pi = producer(a.in[0]);
+            if (pi < 0 || pi >= static_cast<int>(i)) continue;
+            const Node& p = nodes[pi];
+            if (!(p.kind == Node::Conv || p.kind == Node::Dw) || p.act != ACT_NONE || p.res >= 0 || is_graph_output(p.out) || consumers(p.out).size() != 1) continue;
+            const size_t C = a.scale.size();
+            const std::vector<int> wshape = g.tensors[p.w].shape;
+            const std::vector<float>& wsrc = g.tensors[p.w].f32;
+            if (C == 0 || wshape.empty() || wsrc.empty() || wsrc.size() != g.tensors[p.w].elems() || wsrc.size() % C) continue;
+            if (static_cast<size_t>(p.kind == Node::Conv ? wshape.front() : wshape.back()) != C) continue;
+            if (p.b >= 0 && g.tensors[p.b].f32.size() != C) continue;
+            const size_t per = wsrc.size() / C;
+            std::vector<float> w(wsrc.size()), b(C);
+            for (size_t k = 0; k < w.size(); k++) w[k] = static_cast<float>(static_cast<double>(wsrc[k]) * a.scale[p.kind == Node::Conv ? k / per : k % C]);
+            for (size_t c = 0; c < C; c++) b[c] = static_cast<float>(static_cast<double>(p.b >= 0 ? g.tensors[p.b].f32[c] : 0.f) * a.scale[c] + a.shift[c]);
+            Node fused = p;
+            fused.w = new_const(wshape, std::move(w));
+            fused.b = new_const({static_cast<int>(C)}, std::move(b));
+            fused.out = a.out;
+            fused.act = a.act;
+            fused.src_ops.insert(fused.src_ops.end(), a.src_ops.begin(), a.src_ops.end());
+            nodes[pi].dead = true;
+            nodes[i] = std::move(fused);
+        }
+        for (size_t i = 0; i < nodes.size(); i++) {
+            const Node& a = nodes[i];
+            if (a.dead || a.kind != Node::Affine || a.act != ACT_NONE || is_graph_output(a.out)) continue;
+            std::vector<int> cons = consumers(a.out);
+            if (cons.size() != 1 || cons[0] <= static_cast<int>(i) || nodes[cons[0]].kind != Node::Act) continue;
+            const Node& c = nodes[cons[0]];
+            Node fused = a;
+            fused.act = c.act;
+            fused.alpha = c.alpha;
+            fused.out = c.out;
+            fused.src_ops.insert(fused.src_ops.end(), c.src_ops.begin(), c.src_ops.end());
+            nodes[i].dead = true;
+            nodes[cons[0]] = std::move(fused);
+        }
+    }
+
+    // FULLY_CONNECTED over a flattened [1,H,W,C] tensor with weights [N][H W C] is, byte for byte, the whole-frame VALID convolution KH = H,
+    // KW = W to [1,1,1,N]: the node reads the 4-D tensor behind the RESHAPE (which goes when nobody else reads it) and writes a [1,1,1,N] view
+    // of its [1,N] output.  A rank-2 input without such a producer is the [1,1,1,K] view of itself: a 1x1 convolution.
+    void lower_fully_connected() {
+        std::vector<std::pair<size_t, Node>> before, after;
+        for (size_t i = 0; i < nodes.size(); i++) {
+            if (nodes[i].dead || !nodes[i].fc) continue;
+            const int x = nodes[i].in[0];
+            const std::vector<int> xs = shape(x);
+            const int N = shape(nodes[i].w).at(0), K = shape(nodes[i].w).at(1);
+            int H = 1, W = 1, C = K;
+            std::vector<int> moved;
+            if (xs.size() == 4) {
+                H = xs[1]; W = xs[2]; C = xs[3];
+            } else {
+                const int pi = producer(x);
+                const int src = pi >= 0 && nodes[pi].kind == Node::Reshape ? nodes[pi].in[0] : -1;
+                if (src >= 0 && !g.tensors[src].is_const && shape(src).size() == 4 && shape(src)[0] == 1 && g.tensors[src].elems() == static_cast<size_t>(K)) {
+                    H = shape(src)[1]; W = shape(src)[2]; C = shape(src)[3];
+                    nodes[i].in = {src};
+                    if (consumers(x).empty() && !is_graph_output(x)) {
+                        moved = nodes[pi].src_ops;
+                        nodes[pi].dead = true;
+                    }
+                } else {
+                    Node r;
+                    r.kind = Node::Reshape; r.in = {x}; r.out = new_activation({1, 1, 1, K}); r.src_ops.clear();
+                    nodes[i].in = {r.out};
+                    before.emplace_back(i, std::move(r));
+                }
+            }
+            Node& n = nodes[i];
+            n.src_ops.insert(n.src_ops.begin(), moved.begin(), moved.end());
+            n.KH = H; n.KW = W; n.sh = n.sw = 1; n.padding = Padding::Valid;
+            n.w = new_const({N, H, W, C}, std::vector<float>(g.tensors[n.w].f32));
+            Node r;
+            r.kind = Node::Reshape; r.out = n.out; r.src_ops.clear();
+            n.out = new_activation({1, 1, 1, N});
+            r.in = {n.out};
+            after.emplace_back(i, std::move(r));
+        }
+        if (after.empty()) return;
+        std::vector<Node> re;
+        size_t kb = 0, ka = 0;
+        for (size_t i = 0; i < nodes.size(); i++) {
+            if (kb < before.size() && before[kb].first == i) re.push_back(std::move(before[kb++].second));
+            re.push_back(std::move(nodes[i]));
+            if (ka < after.size() && after[ka].first == i) re.push_back(std::move(after[ka++].second));
+        }
+        nodes = std::move(re);
+    }
+
     // Spatial PAD (zeros) in front of VALID convolutions — how the MLIR-converted full_range_sparse graph writes every
     // convolution — folds into its consumers: as SAME when the amounts are TF's SAME amounts for that consumer (3x3 stride 1 with
     // 1/1/1/1), as explicit pads before the first row / column otherwise (the kernels bound-check the far side).
@@ -1176,7 +1306,8 @@ namespace {
 // Activation tensors whose channel count is not a multiple of 4 (front / short-range: 36 -> 42 -> 48) keep their layers off every
 // fused kernel (float4 pixels everywhere).  Such a tensor — together with everything tied to it by channel-preserving operators
 // (depthwise conv, ADD, RELU / PRELU, MAX_POOL) — is widened to the next multiple of 4 with channels that are exactly zero: the
-// producing convolution gets zero filter rows and biases, depthwise stages zero taps and biases, PRELU a zero slope, consuming
+// producing convolution gets zero filter rows and biases, depthwise stages zero taps and biases, PRELU a zero slope, a per-channel MUL / ADD
+// constant the scale 1 / the shift 0 (0 * 1 + 0 is exactly zero), consuming
 // convolutions zero filter columns, and channel PADs on either side (zeros appended at the high end) append
 // or remove correspondingly fewer / more.  Every real channel computes what it computed before, bit for bit.  Classes that touch a
 // graph input / output or an operator not listed here are left alone.
@@ -1210,10 +1341,26 @@ void pad_odd_channels(Graph& g, std::vector<double>* logical_elems, std::vector<
                 al.shape.back() != g.tensors[in].shape.back()) return;
         } else if (op.op == BuiltinOp::Pad) {
             if (op.inputs.size() < 2 || op.inputs[1] < 0 || !g.tensors[op.inputs[1]].is_const) return;
-        } else if (op.op == BuiltinOp::Add) {
-            if (op.inputs.size() < 2 || op.inputs[1] < 0) return;
+        } else if (op.op == BuiltinOp::Add || op.op == BuiltinOp::Mul) {
+            if (op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0) return;
         }
     }
+    // MUL / ADD by a constant: the activation operand, and whether the constant can follow a widening (a scalar factor needs none, a [.., C] constant
+    // grows with the tensor; anything else is left to the lowering's error message and keeps its class as it is)
+    auto affine_x = [&](const OpInfo& op) {
+        const bool c0 = g.tensors[op.inputs[0]].is_const, c1 = g.tensors[op.inputs[1]].is_const;
+        return c0 == c1 ? -1 : (c0 ? op.inputs[1] : op.inputs[0]);
+    };
+    auto affine_c = [&](const OpInfo& op) { return g.tensors[op.inputs[0]].is_const ? op.inputs[0] : op.inputs[1]; };
+    auto affine_widens = [&](const OpInfo& op) {
+        const int x = affine_x(op);
+        if (x < 0 || g.tensors[x].shape.empty()) return false;
+        const TensorInfo& ct = g.tensors[affine_c(op)];
+        const int C = g.tensors[x].shape.back();
+        if (ct.f32.size() != ct.elems()) return false;
+        if (ct.elems() == 1) return op.op == BuiltinOp::Mul;   // (a scalar shift would fill the appended channels, which must stay zero)
+        return C >= 1 && ct.elems() == static_cast<size_t>(C) && !ct.shape.empty() && ct.shape.back() == C;
+    };
     for (int t = 0; t < NT; t++)
         if (!g.tensors[t].is_const && g.tensors[t].shape.empty()) return;
     std::vector<int> parent(NT);
@@ -1229,6 +1376,9 @@ void pad_odd_channels(Graph& g, std::vector<double>* logical_elems, std::vector<
             case BuiltinOp::Add:
                 unite(op.inputs.at(0), op.outputs.at(0));
                 if (act(op.inputs.at(1))) unite(op.inputs.at(1), op.outputs.at(0));
+                break;
+            case BuiltinOp::Mul:
+                if (affine_x(op) >= 0) unite(affine_x(op), op.outputs.at(0));
                 break;
             default: break;
         }
@@ -1248,8 +1398,9 @@ void pad_odd_channels(Graph& g, std::vector<double>* logical_elems, std::vector<
                 if (!g.tensors[op.inputs.at(1)].is_const) mark(op.inputs[0]);
                 break;
             case BuiltinOp::Add:
-                if (!act(op.inputs.at(1))) mark(op.inputs[0]);  // constant addend: not handled
-                if (!act(op.inputs.at(0))) { mark(op.inputs[1]); mark(op.outputs.at(0)); }  // ... on either side
+            case BuiltinOp::Mul:
+                if (act(op.inputs.at(0)) && act(op.inputs.at(1)) && op.op == BuiltinOp::Add) break;
+                if (!affine_widens(op)) { mark(op.inputs[0]); mark(op.inputs[1]); mark(op.outputs.at(0)); }  // (a constant that cannot follow, MUL of two activations)
                 break;
             case BuiltinOp::Pad: {
                 const auto& pd = g.tensors[op.inputs.at(1)].i32;
@@ -1357,6 +1508,7 @@ void pad_odd_channels(Graph& g, std::vector<double>* logical_elems, std::vector<
                 if (act(in) && newC[in] != newC[out]) return;
                 break;
             case BuiltinOp::Add:
+            case BuiltinOp::Mul:
                 if ((act(in) && newC[in] != newC[out]) || (act(op.inputs.at(1)) && newC[op.inputs[1]] != newC[out])) return;
                 break;
             default: break;
@@ -1368,11 +1520,11 @@ void pad_odd_channels(Graph& g, std::vector<double>* logical_elems, std::vector<
         logical_C->push_back((*logical_C)[t]);
         return static_cast<int>(g.tensors.size()) - 1;
     };
-    auto widen_last = [&](int t, int Cn) {  // [..., C] -> [..., Cn], zeros appended (filters [*,kh,kw,I], taps [1,kh,kw,C], bias / alpha [C])
+    auto widen_last = [&](int t, int Cn, float fill = 0.f) {  // [..., C] -> [..., Cn], zeros appended (filters [*,kh,kw,I], taps [1,kh,kw,C], bias / alpha [C]; a MUL's scale: ones)
         TensorInfo& ti = g.tensors[t];
         const int C = ti.shape.back();
         const size_t rows = ti.elems() / static_cast<size_t>(C);
-        std::vector<float> w(rows * Cn, 0.f);
+        std::vector<float> w(rows * Cn, fill);
         for (size_t r = 0; r < rows; r++)
             for (int c = 0; c < C; c++) w[r * Cn + c] = ti.f32[r * C + c];
         ti.f32 = std::move(w);
@@ -1402,6 +1554,10 @@ void pad_odd_channels(Graph& g, std::vector<double>* logical_elems, std::vector<
         } else if (op.op == BuiltinOp::Prelu && Con != Co) {
             op.inputs[1] = clone_const(op.inputs[1]);
             widen_last(op.inputs[1], Con);
+        } else if ((op.op == BuiltinOp::Add || op.op == BuiltinOp::Mul) && Con != Co && affine_x(op) >= 0 && g.tensors[affine_c(op)].elems() != 1) {
+            const int k = g.tensors[op.inputs[0]].is_const ? 0 : 1;
+            op.inputs[k] = clone_const(op.inputs[k]);
+            widen_last(op.inputs[k], Con, op.op == BuiltinOp::Mul ? 1.f : 0.f);
         } else if (op.op == BuiltinOp::Pad && (Cin != Ci || Con != Co)) {
             op.inputs[1] = clone_const(op.inputs[1]);
             g.tensors[op.inputs[1]].i32[7] = Con - Cin;
@@ -1436,8 +1592,11 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
         if (op.outputs.empty()) throw std::runtime_error("plan: operator without an output");
         for (int t : op.outputs)
             if (t < 0 || plan.graph.tensors[static_cast<size_t>(t)].shape.empty()) throw std::runtime_error("plan: operator output without a shape");
+        // (but the scalar constant of a MUL / ADD, which converters store with rank 0)
+        const bool affine_op = op.op == BuiltinOp::Mul || op.op == BuiltinOp::Add;
         for (int t : op.inputs)
-            if (t >= 0 && plan.graph.tensors[static_cast<size_t>(t)].shape.empty()) throw std::runtime_error("plan: operator input without a shape");
+            if (t >= 0 && plan.graph.tensors[static_cast<size_t>(t)].shape.empty() && !(affine_op && plan.graph.tensors[static_cast<size_t>(t)].is_const))
+                throw std::runtime_error("plan: operator input without a shape");
     }
     for (int t : plan.graph.inputs)
         if (t < 0 || plan.graph.tensors[static_cast<size_t>(t)].shape.empty()) throw std::runtime_error("plan: graph input without a shape");
@@ -1478,12 +1637,70 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
                     throw std::runtime_error("plan: convolution channel mismatch");
                 break;
             }
-            case BuiltinOp::Add:
-                n.kind = Node::Add;
-                n.in = {op.inputs.at(0), op.inputs.at(1)};
+            case BuiltinOp::FullyConnected: {
+                n.kind = Node::Conv;
+                n.fc = true;
+                if (op.inputs.size() < 2) throw std::runtime_error("plan: FULLY_CONNECTED without weights");
+                n.in = {op.inputs[0]};
+                n.w = op.inputs[1];
+                n.b = op.inputs.size() > 2 ? op.inputs[2] : -1;
+                if (n.w < 0 || !g.tensors[n.w].is_const) throw std::runtime_error("plan: FULLY_CONNECTED weights must be a constant tensor");
+                if (n.b >= 0 && !g.tensors[n.b].is_const) throw std::runtime_error("plan: FULLY_CONNECTED bias must be a constant tensor");
+                if (op.weights_format != 0)
+                    throw std::runtime_error("plan: FULLY_CONNECTED weights_format " + std::to_string(op.weights_format) + " unsupported (only DEFAULT: row-major [N][K])");
+                const TensorInfo& wt = g.tensors[n.w];
+                if (wt.shape.size() != 2 || wt.shape[0] < 1 || wt.shape[1] < 1 || wt.f32.size() != wt.elems())
+                    throw std::runtime_error("plan: FULLY_CONNECTED weights must be an f32 [N][K] constant");
+                const int N = wt.shape[0], K = wt.shape[1];
+                if (n.in[0] < 0 || g.tensors[n.in[0]].is_const) throw std::runtime_error("plan: FULLY_CONNECTED of a constant input unsupported");
+                const TensorInfo& xt = g.tensors[n.in[0]];
+                bool x_ok = (xt.shape.size() == 2 || xt.shape.size() == 4) && xt.shape[0] == 1;
+                for (int d : xt.shape) x_ok = x_ok && d >= 1 && d <= (1 << 24);
+                if (!x_ok) throw std::runtime_error("plan: FULLY_CONNECTED input must be [1,K] or [1,H,W,C]");
+                if (xt.elems() != static_cast<size_t>(K))
+                    throw std::runtime_error("plan: FULLY_CONNECTED K = " + std::to_string(K) + " does not match its input's " + std::to_string(xt.elems()) + " elements");
+                const TensorInfo& ot = g.tensors[n.out];
+                if (ot.shape.size() == 4 && op.keep_num_dims) throw std::runtime_error("plan: FULLY_CONNECTED keep_num_dims with a rank-4 output unsupported");
+                if (ot.shape.size() != 2 || ot.shape[0] != 1 || ot.shape[1] != N) throw std::runtime_error("plan: FULLY_CONNECTED output must be [1,N]");
+                if (n.b >= 0 && (g.tensors[n.b].f32.size() != static_cast<size_t>(N) || g.tensors[n.b].elems() != static_cast<size_t>(N)))
+                    throw std::runtime_error("plan: FULLY_CONNECTED bias must be an f32 [N] constant");
+                n.padding = Padding::Valid;
                 n.act = act_of(op.act);
-                if (g.tensors[n.in[0]].shape != g.tensors[n.in[1]].shape) throw std::runtime_error("plan: broadcasting ADD unsupported");
                 break;
+            }
+            case BuiltinOp::Add:
+            case BuiltinOp::Mul: {
+                const bool mul = op.op == BuiltinOp::Mul;
+                const std::string name = mul ? "MUL" : "ADD";
+                if (op.inputs.size() < 2) throw std::runtime_error("plan: " + name + " needs two operands");
+                const int a = op.inputs[0], b = op.inputs[1];
+                const bool ca = g.tensors[a].is_const, cb = g.tensors[b].is_const;
+                n.act = act_of(op.act);
+                if (!ca && !cb) {
+                    if (mul) throw std::runtime_error("plan: MUL of two activations unsupported (only MUL by a per-channel or scalar constant)");
+                    n.kind = Node::Add;
+                    n.in = {a, b};
+                    if (g.tensors[n.in[0]].shape != g.tensors[n.in[1]].shape) throw std::runtime_error("plan: broadcasting ADD unsupported");
+                    break;
+                }
+                if (ca && cb) throw std::runtime_error("plan: " + name + " of two constants unsupported");
+                // x * c / x + c, either operand order, c per channel (C elements, C its last dimension) or a scalar: an affine of x's last dimension
+                const int x = ca ? b : a, c = ca ? a : b;
+                const std::vector<int>& xs = g.tensors[x].shape;
+                const TensorInfo& ct = g.tensors[c];
+                const int C = xs.back();
+                const size_t ce = ct.elems();
+                const bool per_channel = C >= 1 && ce == static_cast<size_t>(C) && !ct.shape.empty() && ct.shape.back() == C, scalar = ce == 1;
+                if (C < 1 || C > (1 << 16) || !(per_channel || scalar) || ct.f32.size() != ce)   // (65536 channels bound what a crafted graph makes a node allocate)
+                    throw std::runtime_error("plan: " + name + " by a constant that is neither per-channel ([C]) nor a scalar unsupported");
+                if (g.tensors[n.out].shape != xs) throw std::runtime_error("plan: broadcasting " + name + " unsupported");
+                n.kind = Node::Affine;
+                n.in = {x};
+                n.scale.assign(static_cast<size_t>(C), 1.f);
+                n.shift.assign(static_cast<size_t>(C), 0.f);
+                for (int k = 0; k < C; k++) (mul ? n.scale : n.shift)[static_cast<size_t>(k)] = ct.f32[scalar ? 0 : static_cast<size_t>(k)];
+                break;
+            }
             case BuiltinOp::Relu:
                 n.kind = Node::Act; n.in = {op.inputs.at(0)}; n.act = ACT_RELU;
                 break;
@@ -1526,6 +1743,8 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
     }
 
     Rewriter rw{g, nodes};
+    if (fuse_level >= 1) rw.fuse_affines();
+    rw.lower_fully_connected();
     if (fuse_level >= 1) rw.fold_spatial_pads();
     if (fuse_level >= 1) rw.fuse_epilogues();
     if (fuse_level >= 2) rw.fuse_blocks();
@@ -1932,7 +2151,7 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
 }  // namespace
 
 std::string Plan::describe() const {
-    static const char* kinds[] = {"conv", "dw", "block", "add", "act", "maxpool", "pad", "reshape", "concat", "resize", "d2s", "chain", "resident"};
+    static const char* kinds[] = {"conv", "dw", "block", "add", "act", "maxpool", "pad", "reshape", "concat", "resize", "d2s", "chain", "resident", "affine"};
     static const char* acts[] = {"", "+relu", "+relu6", "+prelu"};
     static const char* res[] = {"", "+skip", "+skip(maxpool)", "+skip(up2x)"};
     std::ostringstream os;

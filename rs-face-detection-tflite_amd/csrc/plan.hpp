@@ -4,7 +4,8 @@
 // /root/reference/src/face_detection_lite/face_detection.rs:235).  Here the graph is rewritten once, at load:
 //   level 0  one launch per builtin op (RESHAPE = view, CONCATENATION = producers write into the joined buffer)
 //   level 1  ADD / RELU / PRELU / MAX_POOL_2D-skip / channel-PAD-skip / RESIZE_BILINEAR-skip folded into the
-//            producing convolution's epilogue
+//            producing convolution's epilogue; per-channel MUL / ADD by constants (unfolded batch normalisation) merged,
+//            folded into the filter and bias of the convolution in front where nothing else reads it, else one launch
 //   level 2  DEPTHWISE_CONV_2D -> CONV_2D 1x1 (-> skip -> activation) fused into one BlazeBlock kernel
 //   level 3  runs of same-shape stride-1 BlazeBlocks whose frame fits in LDS fused into one frame-resident chain kernel
 //   level 4  runs of narrow (C <= 24, W <= 128) stride-1 BlazeBlocks cut into row-pipelined chains of up to 4 blocks: one
@@ -24,7 +25,7 @@
 namespace mi {
 
 struct Node {
-    enum Kind { Conv, Dw, Block, Add, Act, MaxPool, Pad, Reshape, Concat, Resize, DepthToSpace, Chain, Resident } kind = Conv;
+    enum Kind { Conv, Dw, Block, Add, Act, MaxPool, Pad, Reshape, Concat, Resize, DepthToSpace, Chain, Resident, Affine } kind = Conv;
     std::vector<Node> members;  // Chain: the fused BlazeBlocks, in order; Resident: the fused nodes (chains expanded), in order
     // Resident: the stage program.  ResStage geometry / LDS placement is final; global references and weight offsets are
     // filled in by the engine from (src_t, dst_t, res_t) and the member's constants.
@@ -51,6 +52,8 @@ struct Node {
     std::vector<HeadPair> head_pairs;
     bool chain_pre = false, chain_post = false;  // frame-resident Chain: members.front() / members.back() is the stride-2 block before / after the resident blocks
     bool gemm_head = false;      // Conv whose window is the whole frame: runs as a GEMM over the batch (head_gemm_kernel)
+    bool fc = false;             // Conv lowered from FULLY_CONNECTED: the whole-frame VALID convolution over the flattened tensor's frame
+    std::vector<float> scale, shift;  // Affine: out = act(x * scale[c] + shift[c]), c the last dimension (MUL / ADD by per-channel constants)
     std::vector<int> extra_out;  // Resident: further tensors the launch writes to global memory (besides `out`)
     std::vector<int> in;   // activation inputs (tensor ids)
     int out = -1;

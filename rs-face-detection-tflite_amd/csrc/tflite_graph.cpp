@@ -333,10 +333,10 @@ Graph parse_tflite(const uint8_t* data, size_t size) {
         op.inputs = o.ints(1);
         op.outputs = o.ints(2);
         for (size_t k = 0; k < op.inputs.size(); k++) {
-            // -1 = optional input absent: only the bias slot of a convolution is optional in the operators taken here; a -1
+            // -1 = optional input absent: only the bias slot of a convolution / FULLY_CONNECTED is optional in the operators taken here; a -1
             // anywhere else (an activation, a filter, PAD's paddings ...) is a malformed model, refused before any g.tensors[t]
             int t = op.inputs[k];
-            bool optional_slot = k >= 2 && (op.op == BuiltinOp::Conv2D || op.op == BuiltinOp::DepthwiseConv2D);
+            bool optional_slot = k >= 2 && (op.op == BuiltinOp::Conv2D || op.op == BuiltinOp::DepthwiseConv2D || op.op == BuiltinOp::FullyConnected);
             if (t < (optional_slot ? -1 : 0) || t >= static_cast<int>(g.tensors.size())) throw std::runtime_error("tflite: tensor index out of range");
         }
         for (int t : op.outputs)
@@ -371,6 +371,12 @@ Graph parse_tflite(const uint8_t* data, size_t size) {
                     op.act = static_cast<FusedAct>(opt.scalar<int8_t>(5, 0));
                     break;
                 case BuiltinOp::Add: op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0)); break;
+                case BuiltinOp::Mul: op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0)); break;
+                case BuiltinOp::FullyConnected:  // FullyConnectedOptions: 0 fused_activation_function, 1 weights_format, 2 keep_num_dims
+                    op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0));
+                    op.weights_format = opt.scalar<int8_t>(1, 0);
+                    op.keep_num_dims = opt.scalar<uint8_t>(2, 0) != 0;
+                    break;
                 case BuiltinOp::Concatenation:
                     op.axis = opt.scalar<int32_t>(0, 0);
                     op.act = static_cast<FusedAct>(opt.scalar<int8_t>(1, 0));

@@ -14,8 +14,8 @@
 namespace mi {
 
 enum class BuiltinOp : int {
-    Add = 0, Concatenation = 2, Conv2D = 3, DepthwiseConv2D = 4, DepthToSpace = 5, Dequantize = 6, MaxPool2D = 17,
-    Relu = 19, Reshape = 22, ResizeBilinear = 23, Pad = 34, Prelu = 54, Densify = 124,
+    Add = 0, Concatenation = 2, Conv2D = 3, DepthwiseConv2D = 4, DepthToSpace = 5, Dequantize = 6, FullyConnected = 9, MaxPool2D = 17,
+    Mul = 18, Relu = 19, Reshape = 22, ResizeBilinear = 23, Pad = 34, Prelu = 54, Densify = 124,
 };
 
 enum class Padding : int { Same = 0, Valid = 1 };
@@ -43,6 +43,8 @@ struct OpInfo {
     int stride_w = 1, stride_h = 1, filter_w = 1, filter_h = 1, depth_multiplier = 1, axis = 0, block_size = 1;
     FusedAct act = FusedAct::None;
     bool align_corners = false, half_pixel_centers = false;
+    int weights_format = 0;        // FULLY_CONNECTED: 0 = DEFAULT ([N][K] row major), anything else is refused by the lowering
+    bool keep_num_dims = false;    // FULLY_CONNECTED
 };
 
 struct Graph {
