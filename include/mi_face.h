@@ -369,8 +369,14 @@ int mi_pipeline_collect_jpeg(mi_pipeline *p, int slot, mi_detection *face, int *
  * [1,H,W,C] one: it runs as the whole-frame convolution), ADD of two tensors, MUL and ADD by a per-channel or scalar constant (an unfolded batch
  * normalisation: folded into the convolution in front where nothing else reads it, else one launch with the activation behind it), PRELU, RELU,
  * fused RELU / RELU6, MAX_POOL_2D, PAD, RESHAPE, CONCATENATION, RESIZE_BILINEAR, DEPTH_TO_SPACE, DEQUANTIZE / DENSIFY of constants.  That is the
- * operator family of a ResNet-style (ArcFace) float graph; its dense 3x3 convolutions run on the matrix cores (option "conv_mfma").  Not lowered:
- * SUB / DIV, MEAN / AVERAGE_POOL_2D, L2_NORMALIZATION, TRANSPOSE, MUL of two tensors, quantised graphs.
+ * operator family of a ResNet-style (ArcFace) float graph; its dense 3x3 convolutions run on the matrix cores (option "conv_mfma").  Pooled heads
+ * load as well: AVERAGE_POOL_2D, MEAN over H and W of a [1,H,W,C] tensor (either keep_dims), L2_NORMALIZATION over the last dimension (no fused
+ * activation), SUB / DIV by a per-channel or scalar constant (x - c, c - x, x / c; a divisor that is no power of two is a true division), and
+ * TRANSPOSE of a rank-4 tensor by a constant perm that keeps the batch axis (the identity is an alias).  ONNX-exported graphs are normalised at
+ * load: behind TRANSPOSE (0,3,1,2) the channel-first element-wise operators ([1,C,1,1] / [C,1,1] constants, PAD on axes 2 and 3, MEAN over {2,3},
+ * the C,H,W flatten in front of FULLY_CONNECTED) move onto NHWC tensors and the transposes around the convolutions disappear; any other reader
+ * gets one transpose launch.  Not lowered: c / x, SUB / DIV / MUL of two tensors, MEAN over other axes, CONCATENATION on the channel axis
+ * (Inception-style FaceNet), LOGISTIC and the other activations, quantised graphs.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct mi_fe mi_fe;
 

@@ -1191,8 +1191,11 @@ class FaceEmbeddings:
     README tells users to download one), none is shipped here, and the reference's own model has never been run on this engine.  Any graph
     of the operators the engine lowers that maps [1,112,112,3] to one output of D values per frame loads; `features` is D.  ResNet-style
     (ArcFace) float graphs are among them: dense 3x3 CONV_2D (conv_mfma_kernel on the matrix cores; `model.set_option("conv_mfma", 0)` sends
-    them back to the generic kernel), MUL / ADD by per-channel constants, PRELU and a FULLY_CONNECTED head.  Still refused: SUB / DIV, MEAN /
-    AVERAGE_POOL_2D, L2_NORMALIZATION, TRANSPOSE, quantised graphs."""
+    them back to the generic kernel), MUL / ADD by per-channel constants, PRELU and a FULLY_CONNECTED head.  Pooled heads load too
+    (AVERAGE_POOL_2D, MEAN over H and W, L2_NORMALIZATION, SUB / DIV by a per-channel or scalar constant), and so do ONNX-exported graphs:
+    TRANSPOSE by a constant perm that keeps the batch axis, with the channel-first element-wise operators moved onto NHWC tensors at load so
+    that the transposes around the convolutions disappear.  Still refused: MUL / SUB / DIV of two tensors, c / x, MEAN over other axes,
+    CONCATENATION on the channel axis, LOGISTIC and the other activations, quantised graphs."""
 
     def __init__(self, model_path=None, device=0, model_bytes=None):
         self.L = lib()

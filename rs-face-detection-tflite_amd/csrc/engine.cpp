@@ -390,6 +390,9 @@ int issue(const Launch& l, hipStream_t s, int chain_fixed, int chain_sched) {
         case Launcher::Resize2x: return launch_resize2x(std::get<EltArgs>(l.args), s);
         case Launcher::DepthToSpace: return launch_depth_to_space(std::get<EltArgs>(l.args), s);
         case Launcher::Bandnet: return launch_bandnet(std::get<BandLaunch>(l.args), s);
+        case Launcher::Avgpool: return launch_avgpool(std::get<EltArgs>(l.args), s);
+        case Launcher::L2norm: return launch_l2norm_rows(std::get<EltArgs>(l.args), s);
+        case Launcher::Transpose: return launch_transpose(std::get<EltArgs>(l.args), s);
     }
     return 0;
 }

@@ -824,7 +824,8 @@ __global__ void act_kernel(EltArgs a) {
 // Per-channel affine, out = act(x * scale[c] + shift[c]) with b = scale, c the last dimension: a MUL and an ADD by constants (a batch normalisation nothing
 // could fold) and the activation behind them as ONE launch.  A separate multiply and add, each rounded, not an fma: the bits of TFLite's two operators.
 // V = 4: float4 accesses (C, the frame strides and the pointers allow it).
-template <int V>
+// DIV: the divisor form, out = act(x / d[c] + shift[c]) with b = d — a DIV by constants that are not powers of two is a true, correctly rounded division.
+template <int V, bool DIV = false>
 __global__ __launch_bounds__(256) void affine_kernel(EltArgs a) {
     const long per = (long)a.H * a.W * a.C / V;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -837,13 +838,13 @@ __global__ __launch_bounds__(256) void affine_kernel(EltArgs a) {
     if (V == 4) {
         const float4 xv = *reinterpret_cast<const float4*>(x), s = *reinterpret_cast<const float4*>(a.b + c), t = *reinterpret_cast<const float4*>(a.shift + c);
         float4 r;
-        r.x = apply_act(__fadd_rn(__fmul_rn(xv.x, s.x), t.x), a.act, a.alpha, c);
-        r.y = apply_act(__fadd_rn(__fmul_rn(xv.y, s.y), t.y), a.act, a.alpha, c + 1);
-        r.z = apply_act(__fadd_rn(__fmul_rn(xv.z, s.z), t.z), a.act, a.alpha, c + 2);
-        r.w = apply_act(__fadd_rn(__fmul_rn(xv.w, s.w), t.w), a.act, a.alpha, c + 3);
+        r.x = apply_act(__fadd_rn(DIV ? __fdiv_rn(xv.x, s.x) : __fmul_rn(xv.x, s.x), t.x), a.act, a.alpha, c);
+        r.y = apply_act(__fadd_rn(DIV ? __fdiv_rn(xv.y, s.y) : __fmul_rn(xv.y, s.y), t.y), a.act, a.alpha, c + 1);
+        r.z = apply_act(__fadd_rn(DIV ? __fdiv_rn(xv.z, s.z) : __fmul_rn(xv.z, s.z), t.z), a.act, a.alpha, c + 2);
+        r.w = apply_act(__fadd_rn(DIV ? __fdiv_rn(xv.w, s.w) : __fmul_rn(xv.w, s.w), t.w), a.act, a.alpha, c + 3);
         *reinterpret_cast<float4*>(o) = r;
     } else {
-        *o = apply_act(__fadd_rn(__fmul_rn(*x, a.b[c]), a.shift[c]), a.act, a.alpha, c);
+        *o = apply_act(__fadd_rn(DIV ? __fdiv_rn(*x, a.b[c]) : __fmul_rn(*x, a.b[c]), a.shift[c]), a.act, a.alpha, c);
     }
 }
 // MAX_POOL_2D: p0 = filter_h, p1 = filter_w, p2 = stride_h, p3 = stride_w; SAME/VALID pads folded into Ho/Wo + H/W clip
@@ -939,8 +940,12 @@ int launch_affine(const EltArgs& a, void* s) {
     if (n <= 0) return 0;
     if (!a.b || !a.shift || (a.act == ACT_PRELU && !a.alpha)) return (int)hipErrorInvalidValue;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (a.C % 4 == 0 && a.a_fs % 4 == 0 && a.out_fs % 4 == 0 && al16(a.a) && al16(a.out) && al16(a.b) && al16(a.shift))
-        return (int)launch_kernel(affine_kernel<4>, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)s, a);
+    const bool v4 = a.C % 4 == 0 && a.a_fs % 4 == 0 && a.out_fs % 4 == 0 && al16(a.a) && al16(a.out) && al16(a.b) && al16(a.shift);
+    if (a.div) {
+        if (v4) return (int)launch_kernel(affine_kernel<4, true>, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)s, a);
+        return (int)launch_kernel(affine_kernel<1, true>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)s, a);
+    }
+    if (v4) return (int)launch_kernel(affine_kernel<4>, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)s, a);
     return (int)launch_kernel(affine_kernel<1>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)s, a);
 }
 int launch_maxpool(const EltArgs& a, void* s) {

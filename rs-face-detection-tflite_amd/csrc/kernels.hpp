@@ -153,6 +153,7 @@ struct EltArgs {  // ADD / activation / MAX_POOL / channel PAD / RESIZE / DEPTH_
     int act = ACT_NONE;
     int p0 = 0, p1 = 0, p2 = 0, p3 = 0;  // op-specific ints (pool filter/stride, pad offsets, block size, flags)
     const float* shift = nullptr;        // affine_kernel: out = act(a * b[c] + shift[c]), b the scale [C]
+    int div = 0;                         // affine_kernel, divisor form: out = act(a / b[c] + shift[c]), b the divisor [C] (a DIV by constants that are not powers of two)
 };
 
 struct RectD {  // layout-compatible with mi_rect (include/mi_face.h) / Rect (types.rs:24-36)
@@ -460,6 +461,18 @@ int launch_add(const EltArgs& a, void* stream);
 int launch_act(const EltArgs& a, void* stream);
 int launch_affine(const EltArgs& a, void* stream);
 int launch_maxpool(const EltArgs& a, void* stream);
+// embed_ops_kernels.hip — the operators of pooled-head and ONNX-exported embedding graphs, each one k-ordered f32 chain per output element
+int launch_avgpool(const EltArgs& a, void* stream);      // AVERAGE_POOL_2D / MEAN over H and W: p0 = filter_h, p1 = filter_w, p2 = stride_h, p3 = stride_w (pads as launch_maxpool)
+int launch_l2norm_rows(const EltArgs& a, void* stream);  // L2_NORMALIZATION over C of the H * W rows of a frame
+int launch_transpose(const EltArgs& a, void* stream);    // TRANSPOSE of [H][W][C] frames: out dimension d (1..3) is in dimension p<d>
+// The two perms that are one matrix transpose per frame take the tiled form: (0,3,1,2) is [H*W][C] -> [C][H*W], (0,2,3,1) is [H][W*C] -> [W*C][H].
+// (32-bit offsets inside a frame, frames on blockIdx.y: a frame of 2^31 elements or more, or more than 65535 frames, takes the general form)
+inline bool transpose_takes_tiled(const EltArgs& a) {
+    const bool to_nchw = a.p1 == 3 && a.p2 == 1 && a.p3 == 2, to_nhwc = a.p1 == 2 && a.p2 == 3 && a.p3 == 1;
+    return (to_nchw || to_nhwc) && static_cast<long>(a.H) * a.W * a.C < (1L << 31) && a.B <= 65535;
+}
+// thread-per-row form of l2norm_rows_kernel from this many rows on (below: a wave per row, lane 0 sums, every lane divides)
+constexpr long kL2NormLaneRows = 2048;
 int launch_padc(const EltArgs& a, void* stream);
 int launch_resize2x(const EltArgs& a, void* stream);
 int launch_depth_to_space(const EltArgs& a, void* stream);

@@ -288,12 +288,27 @@ struct Lowering {
                     if (si.size() != 4) { a.C = a.Co = si.back(); a.W = a.Wo = a.C > 0 ? static_cast<int>(g.tensors[n.in[0]].elems() / static_cast<size_t>(a.C)) : 0; }
                     a.b = weights(pc.node_w[i]);
                     a.shift = weights(pc.node_b[i]);
+                    a.div = n.divide ? 1 : 0;
                     set(l, Launcher::Act, a, lab("affine_kernel"));   // (launch_act hands EltArgs with a shift to launch_affine)
                 } else if (n.kind == Node::Act) {
                     set(l, Launcher::Act, a, lab("act_kernel"));
                 } else if (n.kind == Node::MaxPool) {
                     a.p0 = n.filter_h; a.p1 = n.filter_w; a.p2 = n.sh; a.p3 = n.sw;
                     set(l, Launcher::Maxpool, a, lab("maxpool_kernel"));
+                } else if (n.kind == Node::Pool) {
+                    if (si.size() != 4 || so.size() != 4) throw std::runtime_error("internal: pool on a tensor that is not rank 4");
+                    a.p0 = n.filter_h; a.p1 = n.filter_w; a.p2 = n.sh; a.p3 = n.sw;
+                    set(l, Launcher::Avgpool, a, lab("avgpool_kernel"));
+                } else if (n.kind == Node::L2Norm) {
+                    // rows of D = the last dimension: [1,D] is one row a frame, [1,H,W,D] H * W of them
+                    a.C = a.Co = si.back();
+                    a.H = a.Ho = 1;
+                    a.W = a.Wo = a.C > 0 ? static_cast<int>(g.tensors[n.in[0]].elems() / static_cast<size_t>(a.C)) : 0;
+                    set(l, Launcher::L2norm, a, lab(static_cast<long>(c.F) * a.W < kL2NormLaneRows ? "l2norm_rows_kernel<wave per row>" : "l2norm_rows_kernel<thread per row>"));
+                } else if (n.kind == Node::Transpose) {
+                    if (si.size() != 4 || so.size() != 4 || n.perm.size() != 4) throw std::runtime_error("internal: transpose on a tensor that is not rank 4");
+                    a.p1 = n.perm[1]; a.p2 = n.perm[2]; a.p3 = n.perm[3];
+                    set(l, Launcher::Transpose, a, lab(transpose_takes_tiled(a) ? "transpose_tiled_kernel" : "transpose_kernel"));
                 } else if (n.kind == Node::Pad) {
                     const auto& pv = g.tensors[n.pads].i32;
                     if (pv[0] != 0 || pv[1] != 0) throw std::runtime_error("PAD on the batch axis unsupported");

@@ -57,7 +57,7 @@ struct LaunchCtx {
 
 enum class Launcher {  // one per launch_* entry point (kernels.hpp); SmallChain: launch_strip / launch_block once per block of `blocks`; Act with EltArgs::shift: launch_affine
     Conv, HeadGemm, Dw, Xc, Mdblock, Dblock, Mbneck, Bneck, Tail, Resident, Chain, StripPipe, SmallChain, Ms2, Mwalk, MstripChain, Strip, Mstrip, Block,
-    Add, Act, Maxpool, Padc, Resize2x, DepthToSpace, Bandnet
+    Add, Act, Maxpool, Padc, Resize2x, DepthToSpace, Bandnet, Avgpool, L2norm, Transpose
 };
 
 struct Launch {

@@ -1,7 +1,9 @@
 // plan.cpp — graph rewriting + activation-arena planning (see plan.hpp).
 #include "plan.hpp"
+#include "layout.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <map>
 #include <sstream>
@@ -152,6 +154,7 @@ struct Rewriter {
             if (cons.size() != 1 || cons[0] <= static_cast<int>(i)) continue;
             Node& b = nodes[cons[0]];
             if (b.kind != Node::Affine || b.in[0] != a.out || b.scale.size() != a.scale.size()) continue;
+            if (a.divide || b.divide) continue;   // a true division merges with nothing: x * (1 / c) is a different number
             for (size_t c = 0; c < a.scale.size(); c++) {
                 const double s = static_cast<double>(a.scale[c]) * b.scale[c], t = static_cast<double>(a.shift[c]) * b.scale[c] + b.shift[c];
                 b.scale[c] = static_cast<float>(s);
@@ -163,7 +166,7 @@ struct Rewriter {
         }
         for (size_t i = 0; i < nodes.size(); i++) {
             const Node& a = nodes[i];
-            if (a.dead || a.kind != Node::Affine) continue;
+            if (a.dead || a.kind != Node::Affine || a.divide) continue;
             const int pi = producer(a.in[0]);
             if (pi < 0 || pi >= static_cast<int>(i)) continue;
             const Node& p = nodes[pi];
@@ -1593,15 +1596,21 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
         for (int t : op.outputs)
             if (t < 0 || plan.graph.tensors[static_cast<size_t>(t)].shape.empty()) throw std::runtime_error("plan: operator output without a shape");
         // (but the scalar constant of a MUL / ADD, which converters store with rank 0)
-        const bool affine_op = op.op == BuiltinOp::Mul || op.op == BuiltinOp::Add;
+        const bool affine_op = op.op == BuiltinOp::Mul || op.op == BuiltinOp::Add || op.op == BuiltinOp::Sub || op.op == BuiltinOp::Div;
         for (int t : op.inputs)
             if (t >= 0 && plan.graph.tensors[static_cast<size_t>(t)].shape.empty() && !(affine_op && plan.graph.tensors[static_cast<size_t>(t)].is_const))
                 throw std::runtime_error("plan: operator input without a shape");
     }
+    // (the reader checks the operators' tensor indices; a crafted subgraph's own input / output lists reach this point unchecked — a mutated output index
+    // read behind the tensor table, found under AddressSanitizer)
+    const size_t n_tensors = plan.graph.tensors.size();
     for (int t : plan.graph.inputs)
-        if (t < 0 || plan.graph.tensors[static_cast<size_t>(t)].shape.empty()) throw std::runtime_error("plan: graph input without a shape");
+        if (t < 0 || static_cast<size_t>(t) >= n_tensors || plan.graph.tensors[static_cast<size_t>(t)].shape.empty()) throw std::runtime_error("plan: graph input without a shape");
     for (int t : plan.graph.outputs)
-        if (t < 0 || plan.graph.tensors[static_cast<size_t>(t)].shape.empty()) throw std::runtime_error("plan: graph output without a shape");
+        if (t < 0 || static_cast<size_t>(t) >= n_tensors || plan.graph.tensors[static_cast<size_t>(t)].shape.empty()) throw std::runtime_error("plan: graph output without a shape");
+    // ONNX-exported graphs: channel-first element-wise operators move onto NHWC tensors and the transposes around the convolutions go (layout.hpp);
+    // a graph without TRANSPOSE (0,3,1,2) passes through untouched
+    layout_detail::normalise_layout(plan.graph);
     // algorithmic sizes (traffic / MAC figures of the plan) are those of the graph as stored, whatever padding the lowering adds
     std::vector<double> logical_elems;
     std::vector<int> logical_C;
@@ -1669,15 +1678,18 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
                 break;
             }
             case BuiltinOp::Add:
-            case BuiltinOp::Mul: {
-                const bool mul = op.op == BuiltinOp::Mul;
-                const std::string name = mul ? "MUL" : "ADD";
+            case BuiltinOp::Mul:
+            case BuiltinOp::Sub:
+            case BuiltinOp::Div: {
+                const bool mul = op.op == BuiltinOp::Mul, sub = op.op == BuiltinOp::Sub, div = op.op == BuiltinOp::Div;
+                const std::string name = mul ? "MUL" : sub ? "SUB" : div ? "DIV" : "ADD";
                 if (op.inputs.size() < 2) throw std::runtime_error("plan: " + name + " needs two operands");
                 const int a = op.inputs[0], b = op.inputs[1];
                 const bool ca = g.tensors[a].is_const, cb = g.tensors[b].is_const;
                 n.act = act_of(op.act);
                 if (!ca && !cb) {
                     if (mul) throw std::runtime_error("plan: MUL of two activations unsupported (only MUL by a per-channel or scalar constant)");
+                    if (sub || div) throw std::runtime_error("plan: " + name + " of two activations unsupported (only " + name + " by a per-channel or scalar constant)");
                     n.kind = Node::Add;
                     n.in = {a, b};
                     if (g.tensors[n.in[0]].shape != g.tensors[n.in[1]].shape) throw std::runtime_error("plan: broadcasting ADD unsupported");
@@ -1698,7 +1710,27 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
                 n.in = {x};
                 n.scale.assign(static_cast<size_t>(C), 1.f);
                 n.shift.assign(static_cast<size_t>(C), 0.f);
-                for (int k = 0; k < C; k++) (mul ? n.scale : n.shift)[static_cast<size_t>(k)] = ct.f32[scalar ? 0 : static_cast<size_t>(k)];
+                if (div && ca) throw std::runtime_error("plan: DIV of a constant by an activation (c / x) unsupported");
+                // DIV: a divisor that is a power of two has an exact reciprocal, and x * (1 / c) is x / c bit for bit; any other divisor keeps a true
+                // division (the node's divisor form), because x * (1 / c) is a different number
+                bool pow2 = div;
+                for (size_t k = 0; div && k < ce; k++) {
+                    const float v = ct.f32[k];
+                    if (!std::isfinite(v) || v == 0.f) throw std::runtime_error("plan: DIV by a zero or non-finite constant unsupported");
+                    int e = 0;
+                    pow2 = pow2 && std::fabs(std::frexp(v, &e)) == 0.5f && std::isnormal(v) && std::isnormal(1.f / v);
+                }
+                n.divide = div && !pow2;
+                for (int k = 0; k < C; k++) {
+                    const float v = ct.f32[scalar ? 0 : static_cast<size_t>(k)];
+                    float& s = n.scale[static_cast<size_t>(k)];
+                    float& t = n.shift[static_cast<size_t>(k)];
+                    if (mul) s = v;
+                    else if (div) s = pow2 ? 1.f / v : v;
+                    else if (sub && ca) { s = -1.f; t = v; }   // c - x = (-x) + c
+                    else if (sub) t = -v;                      // x - c = x + (-c)
+                    else t = v;
+                }
                 break;
             }
             case BuiltinOp::Relu:
@@ -1715,6 +1747,85 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
                 n.filter_h = op.filter_h; n.filter_w = op.filter_w; n.sh = op.stride_h; n.sw = op.stride_w;
                 n.padding = op.padding; n.act = act_of(op.act);
                 break;
+            case BuiltinOp::AveragePool2D: {
+                n.kind = Node::Pool; n.in = {op.inputs.at(0)};
+                n.filter_h = op.filter_h; n.filter_w = op.filter_w; n.sh = op.stride_h; n.sw = op.stride_w;
+                n.padding = op.padding; n.act = act_of(op.act);
+                const std::vector<int>&si = g.tensors[n.in[0]].shape, &so = g.tensors[n.out].shape;
+                bool ok = si.size() == 4 && so.size() == 4 && si[0] == 1 && n.filter_h >= 1 && n.filter_w >= 1 && n.sh >= 1 && n.sw >= 1 &&
+                          (n.padding == Padding::Same || n.padding == Padding::Valid);
+                for (size_t d = 0; ok && d < 4; d++) ok = si[d] >= 1 && si[d] <= (1 << 24);
+                if (!ok) throw std::runtime_error("plan: AVERAGE_POOL_2D needs a [1,H,W,C] input, a window and strides of at least 1");
+                // (every output element has at least one in-frame tap: SAME's first tap of the last window is in the frame, VALID's windows are whole)
+                const bool same = n.padding == Padding::Same;
+                if (!same && (si[1] < n.filter_h || si[2] < n.filter_w)) throw std::runtime_error("plan: AVERAGE_POOL_2D VALID window larger than the frame");
+                const int ho = same ? (si[1] + n.sh - 1) / n.sh : (si[1] - n.filter_h) / n.sh + 1, wo = same ? (si[2] + n.sw - 1) / n.sw : (si[2] - n.filter_w) / n.sw + 1;
+                if (so != std::vector<int>{1, ho, wo, si[3]}) throw std::runtime_error("plan: AVERAGE_POOL_2D output shape does not match its window");
+                break;
+            }
+            case BuiltinOp::Mean: {
+                // MEAN over H and W of a [1,H,W,C] tensor is the whole-frame average pool; without keep_dims its [1,C] output is a view of the [1,1,1,C] result
+                if (op.inputs.size() < 2) throw std::runtime_error("plan: MEAN needs its axes");
+                n.kind = Node::Pool; n.in = {op.inputs[0]};
+                const TensorInfo& at = g.tensors[op.inputs[1]];
+                if (!at.is_const || at.dtype != 2 || at.i32.empty() || at.i32.size() > 8) throw std::runtime_error("plan: MEAN axes must be a constant int32 tensor");
+                const std::vector<int> si = g.tensors[n.in[0]].shape, so = g.tensors[n.out].shape;
+                bool ok = si.size() == 4 && si[0] == 1;
+                for (size_t d = 0; ok && d < 4; d++) ok = si[d] >= 1 && si[d] <= (1 << 24);
+                if (!ok) throw std::runtime_error("plan: MEAN of a tensor that is not [1,H,W,C] unsupported");
+                std::set<int> axes;
+                for (int32_t a : at.i32) {
+                    if (a < -4 || a >= 4) throw std::runtime_error("plan: MEAN axis outside the input's rank");
+                    axes.insert(a < 0 ? a + 4 : a);
+                }
+                if (axes != std::set<int>{1, 2}) throw std::runtime_error("plan: MEAN over axes other than H and W (1, 2) unsupported");
+                if (so != (op.keep_dims ? std::vector<int>{1, 1, 1, si[3]} : std::vector<int>{1, si[3]})) throw std::runtime_error("plan: MEAN output shape does not match its axes and keep_dims");
+                n.filter_h = si[1]; n.filter_w = si[2]; n.sh = n.sw = 1; n.padding = Padding::Valid;
+                if (!op.keep_dims) {
+                    Node r;
+                    r.kind = Node::Reshape; r.out = n.out; r.src_ops.clear();
+                    TensorInfo t4;
+                    t4.shape = {1, 1, 1, si[3]};
+                    g.tensors.push_back(std::move(t4));
+                    n.out = static_cast<int>(g.tensors.size()) - 1;
+                    r.in = {n.out};
+                    if (g.tensors[n.in[0]].is_const) throw std::runtime_error("plan: constant activation inputs unsupported");
+                    nodes.push_back(std::move(n));
+                    nodes.push_back(std::move(r));
+                    continue;
+                }
+                break;
+            }
+            case BuiltinOp::L2Normalization: {
+                n.kind = Node::L2Norm; n.in = {op.inputs.at(0)};
+                if (op.act != FusedAct::None) throw std::runtime_error("plan: L2_NORMALIZATION with a fused activation unsupported");
+                const std::vector<int>&si = g.tensors[n.in[0]].shape, &so = g.tensors[n.out].shape;
+                bool ok = si.size() >= 2 && si.size() <= 4 && si[0] == 1 && so == si;
+                for (size_t d = 0; ok && d < si.size(); d++) ok = si[d] >= 1 && si[d] <= (1 << 24);
+                if (!ok) throw std::runtime_error("plan: L2_NORMALIZATION needs a [1,..,D] tensor of rank 2 to 4 and an output of the same shape");
+                break;
+            }
+            case BuiltinOp::Transpose: {
+                if (op.inputs.size() < 2) throw std::runtime_error("plan: TRANSPOSE needs its perm");
+                n.kind = Node::Transpose; n.in = {op.inputs[0]};
+                const TensorInfo& pt = g.tensors[op.inputs[1]];
+                if (!pt.is_const || pt.dtype != 2 || pt.i32.empty()) throw std::runtime_error("plan: TRANSPOSE perm must be a constant int32 tensor");
+                const std::vector<int>&si = g.tensors[n.in[0]].shape, &so = g.tensors[n.out].shape;
+                bool ok = si.size() == 4 && so.size() == 4 && pt.i32.size() == 4;
+                for (size_t d = 0; ok && d < 4; d++) ok = si[d] >= 1 && si[d] <= (1 << 24);
+                if (!ok) throw std::runtime_error("plan: TRANSPOSE of a tensor that is not rank 4 unsupported");
+                int seen = 0;
+                for (int32_t p : pt.i32) {
+                    if (p < 0 || p > 3 || (seen >> p & 1)) throw std::runtime_error("plan: TRANSPOSE perm is not a permutation of 0..3");
+                    seen |= 1 << p;
+                }
+                if (pt.i32[0] != 0 || si[0] != 1) throw std::runtime_error("plan: TRANSPOSE that moves the batch axis unsupported");
+                for (size_t d = 0; d < 4; d++)
+                    if (so[d] != si[static_cast<size_t>(pt.i32[d])]) throw std::runtime_error("plan: TRANSPOSE output shape does not match its perm");
+                n.perm.assign(pt.i32.begin(), pt.i32.end());
+                if (n.perm == std::vector<int>{0, 1, 2, 3}) { n.kind = Node::Reshape; n.perm.clear(); }   // the identity: an alias of its input
+                break;
+            }
             case BuiltinOp::Pad:
                 n.kind = Node::Pad; n.in = {op.inputs.at(0)}; n.pads = op.inputs.at(1);
                 need_const(n.pads, "PAD paddings");
@@ -2151,7 +2262,7 @@ Plan build_plan_impl(Graph graph, int fuse_level, int pipe_max_opt, int res_budg
 }  // namespace
 
 std::string Plan::describe() const {
-    static const char* kinds[] = {"conv", "dw", "block", "add", "act", "maxpool", "pad", "reshape", "concat", "resize", "d2s", "chain", "resident", "affine"};
+    static const char* kinds[] = {"conv", "dw", "block", "add", "act", "maxpool", "pad", "reshape", "concat", "resize", "d2s", "chain", "resident", "affine", "pool", "l2norm", "transpose"};
     static const char* acts[] = {"", "+relu", "+relu6", "+prelu"};
     static const char* res[] = {"", "+skip", "+skip(maxpool)", "+skip(up2x)"};
     std::ostringstream os;
@@ -2166,6 +2277,9 @@ std::string Plan::describe() const {
         for (size_t d = 1; d < so.size(); d++) os << (d > 1 ? "x" : "") << so[d];
         os << "]";
         if (n.kind == Node::Conv || n.kind == Node::Dw || (n.kind == Node::Block && n.w >= 0)) os << " k" << n.KH << "x" << n.KW << " s" << n.sh;
+        if (n.kind == Node::Pool) os << " k" << n.filter_h << "x" << n.filter_w << " s" << n.sh << (n.padding == Padding::Same ? " same" : " valid");
+        if (n.kind == Node::Affine && n.divide) os << " divisor form";
+        if (n.kind == Node::Transpose) os << " perm " << n.perm[0] << n.perm[1] << n.perm[2] << n.perm[3];
         if (n.kind == Node::Conv && n.gemm_head) os << " whole-frame window: GEMM over the batch";
         if (n.ept >= 0) os << " pad" << n.ept << "/" << n.epl;
         if (n.kind == Node::Block && n.w < 0) os << " pointwise";

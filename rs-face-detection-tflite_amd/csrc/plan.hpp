@@ -25,7 +25,7 @@
 namespace mi {
 
 struct Node {
-    enum Kind { Conv, Dw, Block, Add, Act, MaxPool, Pad, Reshape, Concat, Resize, DepthToSpace, Chain, Resident, Affine } kind = Conv;
+    enum Kind { Conv, Dw, Block, Add, Act, MaxPool, Pad, Reshape, Concat, Resize, DepthToSpace, Chain, Resident, Affine, Pool, L2Norm, Transpose } kind = Conv;
     std::vector<Node> members;  // Chain: the fused BlazeBlocks, in order; Resident: the fused nodes (chains expanded), in order
     // Resident: the stage program.  ResStage geometry / LDS placement is final; global references and weight offsets are
     // filled in by the engine from (src_t, dst_t, res_t) and the member's constants.
@@ -54,6 +54,8 @@ struct Node {
     bool gemm_head = false;      // Conv whose window is the whole frame: runs as a GEMM over the batch (head_gemm_kernel)
     bool fc = false;             // Conv lowered from FULLY_CONNECTED: the whole-frame VALID convolution over the flattened tensor's frame
     std::vector<float> scale, shift;  // Affine: out = act(x * scale[c] + shift[c]), c the last dimension (MUL / ADD by per-channel constants)
+    bool divide = false;         // Affine, divisor form: out = act(x / scale[c] + shift[c]) (DIV by constants that are not all powers of two: a true division)
+    std::vector<int> perm;       // Transpose: out dimension d is in dimension perm[d] (rank 4, perm[0] == 0)
     std::vector<int> extra_out;  // Resident: further tensors the launch writes to global memory (besides `out`)
     std::vector<int> in;   // activation inputs (tensor ids)
     int out = -1;

@@ -363,6 +363,7 @@ Graph parse_tflite(const uint8_t* data, size_t size) {
                         throw std::runtime_error("tflite: dilated convolution unsupported");
                     break;
                 case BuiltinOp::MaxPool2D:
+                case BuiltinOp::AveragePool2D:   // Pool2DOptions, both
                     op.padding = static_cast<Padding>(opt.scalar<int8_t>(0, 0));
                     op.stride_w = opt.scalar<int32_t>(1, 1);
                     op.stride_h = opt.scalar<int32_t>(2, 1);
@@ -372,6 +373,10 @@ Graph parse_tflite(const uint8_t* data, size_t size) {
                     break;
                 case BuiltinOp::Add: op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0)); break;
                 case BuiltinOp::Mul: op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0)); break;
+                case BuiltinOp::Sub: op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0)); break;
+                case BuiltinOp::Div: op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0)); break;
+                case BuiltinOp::L2Normalization: op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0)); break;   // L2NormOptions
+                case BuiltinOp::Mean: op.keep_dims = opt.scalar<uint8_t>(0, 0) != 0; break;                          // ReducerOptions
                 case BuiltinOp::FullyConnected:  // FullyConnectedOptions: 0 fused_activation_function, 1 weights_format, 2 keep_num_dims
                     op.act = static_cast<FusedAct>(opt.scalar<int8_t>(0, 0));
                     op.weights_format = opt.scalar<int8_t>(1, 0);

@@ -14,8 +14,9 @@
 namespace mi {
 
 enum class BuiltinOp : int {
-    Add = 0, Concatenation = 2, Conv2D = 3, DepthwiseConv2D = 4, DepthToSpace = 5, Dequantize = 6, FullyConnected = 9, MaxPool2D = 17,
-    Mul = 18, Relu = 19, Reshape = 22, ResizeBilinear = 23, Pad = 34, Prelu = 54, Densify = 124,
+    Add = 0, AveragePool2D = 1, Concatenation = 2, Conv2D = 3, DepthwiseConv2D = 4, DepthToSpace = 5, Dequantize = 6, FullyConnected = 9,
+    L2Normalization = 11, MaxPool2D = 17, Mul = 18, Relu = 19, Reshape = 22, ResizeBilinear = 23, Pad = 34, Transpose = 39, Mean = 40, Sub = 41,
+    Div = 42, Prelu = 54, Densify = 124,
 };
 
 enum class Padding : int { Same = 0, Valid = 1 };
@@ -45,6 +46,7 @@ struct OpInfo {
     bool align_corners = false, half_pixel_centers = false;
     int weights_format = 0;        // FULLY_CONNECTED: 0 = DEFAULT ([N][K] row major), anything else is refused by the lowering
     bool keep_num_dims = false;    // FULLY_CONNECTED
+    bool keep_dims = false;        // MEAN (ReducerOptions)
 };
 
 struct Graph {
