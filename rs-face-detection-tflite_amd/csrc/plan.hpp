@@ -1,7 +1,8 @@
 // plan.hpp — lowering of a parsed .tflite graph to a list of fused kernel launches (host side).
 //
 // The reference executes these graphs op by op inside TensorFlow-Lite (`interpreter.invoke()`,
-// /root/reference/src/face_detection_lite/face_detection.rs:235).  Here the graph is rewritten once, at load:
+// /root/reference/src/face_detection_lite/face_detection.rs:235).  Here the graph is rewritten once, at load (plan.cpp runs the passes;
+// plan_internal.hpp lists them with their plan_*.cpp files):
 //   level 0  one launch per builtin op (RESHAPE = view, CONCATENATION = producers write into the joined buffer)
 //   level 1  ADD / RELU / PRELU / MAX_POOL_2D-skip / channel-PAD-skip / RESIZE_BILINEAR-skip folded into the
 //            producing convolution's epilogue; per-channel MUL / ADD by constants (unfolded batch normalisation) merged,

@@ -302,7 +302,7 @@ def back_like(seed, size, c0=24, n1=3, n2=3, coarse_first=False):
 def front_like(seed, size, act="relu", stem_act="relu"):
     """The front / short-range detector's habit of growing by channel PADs on the skip, with widths that are not multiples of 4:
     24 -> 30 -> 42 at size/2, stride 2 to 54 (max-pool + PAD skip), 54 -> 58 -> 58, 1x1 head.  The lowering widens the 30 / 42 /
-    54 / 58-channel tensors to 32 / 44 / 56 / 60 with zero channels (plan.cpp pad_odd_channels) so the fused kernels take them."""
+    54 / 58-channel tensors to 32 / 44 / 56 / 60 with zero channels (plan_widen.cpp pad_odd_channels) so the fused kernels take them."""
     g = GraphBuilder(seed, [1, size, size, 3])
     x = g.conv(g.input, 24, 5, 2)
     x = g.relu(x) if stem_act == "relu" else (g.prelu(x) if stem_act == "prelu" else x)

@@ -216,7 +216,7 @@ def test_absent_operand_is_refused_not_dereferenced(mi):
 
 
 def test_pad_with_constant_input_and_shrinking_output_terminates(tmp_path):
-    """the widening pass (plan.cpp pad_odd_channels) checks its channel PADs to a fixpoint; a PAD whose DATA input is a
+    """the widening pass (plan_widen.cpp pad_odd_channels) checks its channel PADs to a fixpoint; a PAD whose DATA input is a
     constant tensor can never be marked (constants are no activation classes), and when its output is narrower than its input the
     loop used to report a change on every pass — a crafted model hung mi_*_create_from_bytes.  The lowering runs in a child process
     under a timeout: it must come back (accepting or refusing the graph), with or without an odd-width neighbour that makes the pass

@@ -242,18 +242,23 @@ def test_the_new_kernels_do_not_spill(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------- AddressSanitizer
+# the host modules built with AddressSanitizer (the lowering is plan.cpp and its plan_*.cpp passes); their plain objects are not linked.
+# tests/test_lowering_asan.py takes the list from here
+HOST = ("plan", "plan_ops", "plan_widen", "plan_rewrite", "plan_chain", "plan_resident", "plan_layout", "consts", "bandplan", "launches", "tflite_graph")
+
+
 def test_lowering_of_mutated_embedding_graphs_under_address_sanitizer(tmp_path):
     """The host lowering built as tests/test_lowering_asan.py builds it (same sources, same flags, tests/asan_lowering.cpp unchanged) over 150
     mutations each of the pooled-head graph, the ONNX-style network and a graph of TRANSPOSE / MEAN / PAD operators: mutated perms, axes, paddings
     and shapes must be refused, never read out of bounds."""
     build = os.path.join(ROOT, "rs-face-detection-tflite_amd", "build")
-    objs = sorted(f for f in (os.path.join(build, n) for n in os.listdir(build)) if f.endswith(".o") and os.path.basename(f) not in ("plan.o", "consts.o", "bandplan.o", "launches.o", "tflite_graph.o"))
+    objs = sorted(f for f in (os.path.join(build, n) for n in os.listdir(build)) if f.endswith(".o") and os.path.basename(f) not in [m + ".o" for m in HOST])
     assert len(objs) >= 15, "build the product first (__graft_entry__.build())"
     flags = ["-O1", "-g", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
              "-fsanitize=address", "-fno-gpu-sanitize", "-fno-omit-frame-pointer"]
     hipcc = "/opt/rocm/bin/hipcc"
     mine = []
-    for src in (os.path.join(CSRC, "plan.cpp"), os.path.join(CSRC, "consts.cpp"), os.path.join(CSRC, "bandplan.cpp"), os.path.join(CSRC, "launches.cpp"), os.path.join(CSRC, "tflite_graph.cpp"), os.path.join(ROOT, "tests", "asan_lowering.cpp")):
+    for src in [os.path.join(CSRC, m + ".cpp") for m in HOST] + [os.path.join(ROOT, "tests", "asan_lowering.cpp")]:
         o = str(tmp_path / (os.path.basename(src) + ".o"))
         subprocess.check_call([hipcc] + flags + ["-x", "hip", "-c", src, "-o", o], stderr=subprocess.DEVNULL)
         mine.append(o)

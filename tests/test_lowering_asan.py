@@ -1,5 +1,5 @@
-"""The host-side lowering (plan.cpp), constant packing (consts.cpp), single-launch planner (bandplan.cpp) and launch lists (launches.cpp) under AddressSanitizer, over mutated graphs.  CPU only: it builds the
-HOST side of plan.cpp / consts.cpp / bandplan.cpp / launches.cpp / tflite_graph.cpp with hipcc's AddressSanitizer and links the product's other objects; every hipcc line that names -fsanitize= also
+"""The host-side lowering (plan.cpp and its plan_*.cpp passes), constant packing (consts.cpp), single-launch planner (bandplan.cpp) and launch lists (launches.cpp) under AddressSanitizer, over mutated graphs.  CPU only: it builds the
+HOST side of plan.cpp / plan_*.cpp / consts.cpp / bandplan.cpp / launches.cpp / tflite_graph.cpp with hipcc's AddressSanitizer and links the product's other objects; every hipcc line that names -fsanitize= also
 carries -fno-gpu-sanitize, so no device code is instrumented, and none is run."""
 import os
 import subprocess
@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 
 from conftest import MODELS, ROOT
+from test_embed_ops_cpu import HOST   # the host modules instrumented here; their plain objects are not linked
 
 CSRC = os.path.join(ROOT, "rs-face-detection-tflite_amd", "csrc")
 
@@ -17,13 +18,13 @@ def test_lowering_of_mutated_models_under_address_sanitizer(tmp_path):
     its output's shape that way — a four-byte read behind a vector, which crashed the plain build once in twenty runs — and a PRELU on a
     tensor of rank 0."""
     build = os.path.join(ROOT, "rs-face-detection-tflite_amd", "build")
-    objs = sorted(f for f in (os.path.join(build, n) for n in os.listdir(build)) if f.endswith(".o") and os.path.basename(f) not in ("plan.o", "consts.o", "bandplan.o", "launches.o", "tflite_graph.o"))
+    objs = sorted(f for f in (os.path.join(build, n) for n in os.listdir(build)) if f.endswith(".o") and os.path.basename(f) not in [m + ".o" for m in HOST])
     assert len(objs) >= 15, "build the product first (__graft_entry__.build())"
     flags = ["-O1", "-g", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
              "-fsanitize=address", "-fno-gpu-sanitize", "-fno-omit-frame-pointer"]
     hipcc = "/opt/rocm/bin/hipcc"
     mine = []
-    for src in (os.path.join(CSRC, "plan.cpp"), os.path.join(CSRC, "consts.cpp"), os.path.join(CSRC, "bandplan.cpp"), os.path.join(CSRC, "launches.cpp"), os.path.join(CSRC, "tflite_graph.cpp"), os.path.join(ROOT, "tests", "asan_lowering.cpp")):
+    for src in [os.path.join(CSRC, m + ".cpp") for m in HOST] + [os.path.join(ROOT, "tests", "asan_lowering.cpp")]:
         o = str(tmp_path / (os.path.basename(src) + ".o"))
         subprocess.check_call([hipcc] + flags + ["-x", "hip", "-c", src, "-o", o], stderr=subprocess.DEVNULL)
         mine.append(o)
