@@ -59,6 +59,30 @@ impl FaceEmbeddings {
         self.features
     }
 
+    /// Operand precision of the network's dense k x k convolutions (engine option "conv_bf16" on the handle's model): "f32" (default),
+    /// "bf16" (operands rounded to bf16) or "bf16x3" (operands split into two bf16 values: about f32 accuracy).  Anything else is an `Err`.
+    pub fn set_precision(&self, precision: &str) -> Result<(), Error> {
+        let value = match precision {
+            "f32" => 0,
+            "bf16" => 1,
+            "bf16x3" => 2,
+            other => return Err(anyhow::anyhow!("precision must be \"f32\", \"bf16\" or \"bf16x3\", not {:?}", other)),
+        };
+        let key = CString::new("conv_bf16")?;
+        check(unsafe { ffi::mi_model_set_option(ffi::mi_fe_model(self.handle), key.as_ptr(), value) })
+    }
+
+    pub fn precision(&self) -> Result<&'static str, Error> {
+        let key = CString::new("conv_bf16")?;
+        let mut value: i32 = 0;
+        check(unsafe { ffi::mi_model_get_option(ffi::mi_fe_model(self.handle), key.as_ptr(), &mut value) })?;
+        Ok(match value {
+            1 => "bf16",
+            2 => "bf16x3",
+            _ => "f32",
+        })
+    }
+
     /// `infer(&self, image, bbox) -> Result<Array2<f32>>` — face_embeddings.rs:46-89, the `[1, D]` array as its row: `bbox` in absolute
     /// pixels (`faces[0].bbox().scale(size)`, :128), `crop_image_to_bbox`, `image_to_tensor(crop, None, (112, 112), false, (0, 1), false)`,
     /// the network, `l2_norm`.  Where the reference panics (`Mat::roi(..).unwrap()`, :107: a box that leaves the image) this is an `Err`.

@@ -104,6 +104,7 @@ pub struct mi_render_items_style {
 #[repr(C)] pub struct mi_pipeline { _private: [u8; 0] }
 #[repr(C)] pub struct mi_fe { _private: [u8; 0] }
 #[repr(C)] pub struct mi_gallery { _private: [u8; 0] }
+#[repr(C)] pub struct mi_model { _private: [u8; 0] }
 
 extern "C" {
     pub fn mi_last_error() -> *const c_char;
@@ -209,6 +210,9 @@ extern "C" {
     pub fn mi_fe_create_from_bytes(tflite: *const u8, nbytes: usize, device: c_int, out: *mut *mut mi_fe) -> c_int;
     pub fn mi_fe_free(h: *mut mi_fe);
     pub fn mi_fe_features(h: *const mi_fe, features: *mut c_int) -> c_int;
+    pub fn mi_fe_model(h: *mut mi_fe) -> *mut mi_model;
+    pub fn mi_model_set_option(m: *mut mi_model, key: *const c_char, value: c_int) -> c_int;
+    pub fn mi_model_get_option(m: *mut mi_model, key: *const c_char, value: *mut c_int) -> c_int;
     pub fn mi_face_chip_rect(det: *const mi_detection, width: c_int, height: c_int, rect: *mut c_int, valid: *mut c_int) -> c_int;
     pub fn mi_fe_infer_image(h: *mut mi_fe, rgb: *const u8, width: c_int, height: c_int, stride: c_int, bbox: *const c_double,
                              embedding: *mut c_float, cap: c_int) -> c_int;

@@ -131,7 +131,12 @@ size_t mi_model_describe(const mi_model *m, char *buf, size_t cap);
  * the row-wise form where that leaves one row per run: a handful of frames), "conv_mfma" (the dense k x k convolutions of f32 graphs with a multiple of
  * 32 input channels, overlapping windows (not k x k stride k) and at most a plain skip — the 3x3 convolutions of a ResNet-style embedding network:
  * 1 = conv_mfma_kernel, an implicit GEMM on the matrix cores (default); 0 = conv_generic_kernel, as before the option existed; each result within the f32
- * bound of its sum — bit-identical in every case measured so far, which is observed and not promised), "chain_fixed" (the frame-resident chain launches, chain_kernel: 1 = a launch
+ * bound of its sum — bit-identical in every case measured so far, which is observed and not promised), "conv_bf16" (the same convolutions, whatever
+ * "conv_mfma" says, on the bf16 matrix cores, conv_bf16_kernel; tensors stay f32 in memory: 0 = off (default: every bit as without the option); 1 = "bf16":
+ * activations and filter values rounded to bf16, round to nearest even, products accumulated in f32 — each result within (K + 4) 2^-24 sum |x w| of the
+ * exact convolution of the ROUNDED operands, which are up to 2^-9 relative from the f32 ones; 2 = "bf16x3": every operand split into two bf16 values
+ * hi + lo, three products for one (lo w_hi, hi w_lo, hi w_hi) — each result within (3 2^-18 + (3 K + 4) 2^-24) sum |x w| of the exact convolution; an
+ * infinite activation gives NaN in this form; values outside 0..2 are clamped; the constants are packed again when it changes), "chain_fixed" (the frame-resident chain launches, chain_kernel: 1 = a launch
  * whose whole form is one of the detectors' — 16x16x96 between its two stride-2 blocks, or 8x8x96, ReLU in every block and a skip connection in every stride-1 block — takes the
  * instantiation with that shape as constants (default); 0 = always the generic kernel; bit-identical results), "chain_sched" (how those fixed-shape
  * instantiations schedule a contraction: 1 = in phases — the LDS reads of the next channel chunk requested first, then the chunk's depthwise FMAs as one

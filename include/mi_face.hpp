@@ -414,6 +414,18 @@ class FaceEmbeddings {
     FaceEmbeddings(const FaceEmbeddings&) = delete;
     FaceEmbeddings& operator=(const FaceEmbeddings&) = delete;
     int features() const { return features_; }
+    // operand precision of the network's dense k x k convolutions (mi_model option "conv_bf16" on mi_fe_model): "f32" (default), "bf16"
+    // (operands rounded to bf16) or "bf16x3" (operands split into two bf16 values: about f32 accuracy); anything else throws std::invalid_argument
+    void set_precision(const std::string& precision) {
+        const int v = precision == "f32" ? 0 : precision == "bf16" ? 1 : precision == "bf16x3" ? 2 : -1;
+        if (v < 0) throw std::invalid_argument("precision must be \"f32\", \"bf16\" or \"bf16x3\"");
+        detail::check(mi_model_set_option(mi_fe_model(h_), "conv_bf16", v));
+    }
+    std::string precision() const {
+        int v = 0;
+        detail::check(mi_model_get_option(mi_fe_model(h_), "conv_bf16", &v));
+        return v == 1 ? "bf16" : v == 2 ? "bf16x3" : "f32";
+    }
 
     // FaceEmbeddings::infer(&Mat, BBox) -> Array2<f32> [1, D], l2-normalised; bbox in absolute pixels (face_embeddings.rs:46-89).  Throws
     // Error (MI_ERANGE) where the reference panics: a box that leaves the image.

@@ -1195,9 +1195,17 @@ class FaceEmbeddings:
     (AVERAGE_POOL_2D, MEAN over H and W, L2_NORMALIZATION, SUB / DIV by a per-channel or scalar constant), and so do ONNX-exported graphs:
     TRANSPOSE by a constant perm that keeps the batch axis, with the channel-first element-wise operators moved onto NHWC tensors at load so
     that the transposes around the convolutions disappear.  Still refused: MUL / SUB / DIV of two tensors, c / x, MEAN over other axes,
-    CONCATENATION on the channel axis, LOGISTIC and the other activations, quantised graphs."""
+    CONCATENATION on the channel axis, LOGISTIC and the other activations, quantised graphs.
 
-    def __init__(self, model_path=None, device=0, model_bytes=None):
+    `precision` is the operand precision of those dense k x k convolutions (engine option "conv_bf16"; tensors stay f32 in memory): "f32"
+    (default: every bit as without the argument), "bf16" (activations and filter values rounded to bf16, products accumulated in f32 on
+    v_mfma_f32_32x32x16_bf16) or "bf16x3" (every operand split into two bf16 values, three products for one: about f32 accuracy)."""
+
+    PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2}
+
+    def __init__(self, model_path=None, device=0, model_bytes=None, precision="f32"):
+        if precision not in self.PRECISIONS:   # (before a handle is made)
+            raise ValueError("precision must be one of %s, not %r" % (sorted(self.PRECISIONS), precision))
         self.L = lib()
         self.h = C.c_void_p()
         if model_bytes is not None:
@@ -1210,6 +1218,14 @@ class FaceEmbeddings:
         n = C.c_int()
         _check(self.L.mi_fe_features(self.h, C.byref(n)))
         self.features = n.value
+        if self.PRECISIONS[precision]:
+            self.model.set_option("conv_bf16", self.PRECISIONS[precision])
+
+    @property
+    def precision(self):
+        """the operand precision the handle runs at, read back from the engine"""
+        value = self.model.get_option("conv_bf16")
+        return next(name for name, v in self.PRECISIONS.items() if v == value)
 
     def close(self):
         if getattr(self, "h", None):

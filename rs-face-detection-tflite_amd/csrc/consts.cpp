@@ -3,6 +3,7 @@
 #include "consts.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <stdexcept>
 
 namespace mi {
@@ -16,6 +17,19 @@ const std::vector<float>& const_data(const Graph& g, int t, long need) {
     if (t < 0 || static_cast<size_t>(t) >= g.tensors.size()) throw std::runtime_error("consts: a layer names a constant tensor that does not exist");
     const std::vector<float>& v = g.tensors[static_cast<size_t>(t)].f32;
     if (need < 0 || v.size() < static_cast<size_t>(need)) throw std::runtime_error("consts: a constant tensor is shorter than the layer that reads it");
+    return v;
+}
+
+uint16_t bf16_rne(float v) {
+    uint32_t u;
+    std::memcpy(&u, &v, 4);
+    return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+float bf16_to_float(uint16_t h) {
+    const uint32_t u = static_cast<uint32_t>(h) << 16;
+    float v;
+    std::memcpy(&v, &u, 4);
     return v;
 }
 
@@ -327,6 +341,25 @@ struct Packer {
         mdblock_pack_stem(src.data(), ptr(n.b, O), n.act == ACT_PRELU ? data(n.alpha, O).data() : nullptr, n.act, sc.data());
         pc.node_stem[i] = put(sc);
     }
+    // conv_bf16_kernel's B operand of a convolution that has node_wrows: the filter rows rounded to bf16 (`hi`), and with `split` what the
+    // rounding dropped, rounded again (`lo` = bf16(w - hi)); two values a float slot
+    void conv_bf16_planes(size_t i, const Node& n, bool split) {
+        const std::vector<int>& ws = shape(n.w);
+        const size_t count = static_cast<size_t>(ws.at(0)) * ws.at(1) * ws.at(2) * ws.at(3);   // (even: C % 32 == 0)
+        const std::vector<float>& src = data(n.w, static_cast<long>(count));
+        std::vector<uint16_t> hi(count), lo(count);
+        for (size_t k = 0; k < count; k++) {
+            hi[k] = bf16_rne(src[k]);
+            lo[k] = bf16_rne(src[k] - bf16_to_float(hi[k]));
+        }
+        auto plane = [&](const std::vector<uint16_t>& h) {
+            std::vector<float> v(count / 2);
+            std::memcpy(v.data(), h.data(), v.size() * sizeof(float));
+            return put(v);
+        };
+        pc.node_wbf16_hi[i] = plane(hi);
+        if (split) pc.node_wbf16_lo[i] = plane(lo);
+    }
     // BlazeBlock with a launch of its own: the block kernel's constants, and those of every specialised form its shape has
     void block(size_t i, const Node& n) {
         if (n.w >= 0) pc.node_w[i] = put_tensor(n.w);
@@ -388,11 +421,11 @@ struct Packer {
 
 }  // namespace
 
-PlanConsts pack_plan_consts(const Plan& plan) {
+PlanConsts pack_plan_consts(const Plan& plan, int conv_bf16) {
     PlanConsts pc;
     Packer p{plan, plan.graph, pc};
     const size_t NN = plan.nodes.size();
-    for (std::vector<long>* v : {&pc.node_w, &pc.node_b, &pc.node_w2, &pc.node_b2, &pc.node_alpha, &pc.node_pair, &pc.node_wrows, &pc.node_stem, &pc.node_mwalk, &pc.node_chain_pair, &pc.node_strip, &pc.node_prog})
+    for (std::vector<long>* v : {&pc.node_w, &pc.node_b, &pc.node_w2, &pc.node_b2, &pc.node_alpha, &pc.node_pair, &pc.node_wrows, &pc.node_wbf16_hi, &pc.node_wbf16_lo, &pc.node_stem, &pc.node_mwalk, &pc.node_chain_pair, &pc.node_strip, &pc.node_prog})
         v->assign(NN, -1);
     for (std::vector<std::vector<MemberOff>>* v : {&pc.chain_off, &pc.chain_head_off}) v->assign(NN, {});
     for (std::vector<std::vector<long>>* v : {&pc.res_wblk, &pc.res_cblob, &pc.tail_wa, &pc.tail_wc}) v->assign(NN, {});
@@ -421,6 +454,9 @@ PlanConsts pack_plan_consts(const Plan& plan) {
         }
     }
     p.plain_pairs();
+    if (conv_bf16 != 0)   // behind everything else: no other offset moves
+        for (size_t i = 0; i < NN; i++)
+            if (plan.nodes[i].kind == Node::Conv && pc.node_wrows[i] >= 0) p.conv_bf16_planes(i, plan.nodes[i], conv_bf16 == 2);
     pc.blob.resize(pc.blob.size() + 4096, 0.f);  // slack: the stage programs' A-fragment prefetch walks up to 8 KiB past a tile's last chunk
     return pc;
 }

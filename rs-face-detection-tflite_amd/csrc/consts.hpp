@@ -3,6 +3,7 @@
 // (tests/consts_dump.cpp, tests/asan_lowering.cpp).  The engine uploads `blob` and the two programs as they are.
 #pragma once
 
+#include <cstdint>
 #include <vector>
 
 #include "plan.hpp"
@@ -23,6 +24,9 @@ struct PlanConsts {
     std::vector<long> node_w, node_b, node_w2, node_b2, node_alpha;
     std::vector<long> node_pair;        // pair launch this Block node and the next one share (mdblock_pack_consts, pair form)
     std::vector<long> node_wrows;       // Conv node with a conv_mfma_kernel form (conv_mfma_shape_ok): the filter [Co][KH*KW*C] as stored; Affine node: node_w = scale, node_b = shift
+    // Conv node with node_wrows, packed with conv_bf16 != 0 (-1 otherwise): that filter rounded to bf16, two values a float slot (element 2 j in the
+    // low half of slot j), Co * K / 2 floats a plane: `hi` = rne_bf16(w), and with conv_bf16 == 2 `lo` = rne_bf16(w - hi) (conv_bf16_kernel's B operand)
+    std::vector<long> node_wbf16_hi, node_wbf16_lo;
     std::vector<long> node_stem;        // the first convolution inside the launch of the block pair behind it (mdblock_pack_stem)
     std::vector<long> node_mwalk;       // Block node: mwalk_pack_consts, or ms2_pack_consts for a stride-2 block (a node is one or the other)
     std::vector<long> node_chain_pair;  // Chain node of two plain blocks on a wide layer: mdblock_pack_consts, pair form
@@ -38,8 +42,13 @@ struct PlanConsts {
     std::vector<long> node_prog;        // per node: its first stage in progs / tail_progs (-1 none)
 };
 
-// plan.root_offset is final when this is called (the stage programs carry arena offsets)
-PlanConsts pack_plan_consts(const Plan& plan);
+// plan.root_offset is final when this is called (the stage programs carry arena offsets).  conv_bf16: engine option "conv_bf16"; 0 packs no
+// bf16 plane, and 1 / 2 append theirs behind everything else: every other offset, and the blob up to there, is the same at all three values
+PlanConsts pack_plan_consts(const Plan& plan, int conv_bf16 = 0);
+
+// f32 -> bf16, round to nearest even, as the device's v_cvt_pk_bf16_f32 rounds a finite value: (u + 0x7fff + ((u >> 16) & 1)) >> 16 on the bit pattern u
+uint16_t bf16_rne(float v);
+float bf16_to_float(uint16_t h);
 
 // constant tensor t, of which the caller reads the first `need` floats: the only way the packers (consts.cpp, bandplan.cpp) read a constant.
 // A tensor that does not exist or is shorter than that (the model is untrusted) throws std::runtime_error

@@ -100,6 +100,9 @@ const Model::Option* Model::find_option(const std::string& key) {
         // 2 = the row-wise MFMA form (every tile loads its five rows); 0 = stem_conv_kernel (packed VALU FMAs) at every batch size
         {"stem_mfma", &Model::stem_mfma_, 0, 2, O::kForms},
         {"conv_mfma", &Model::conv_mfma_, 0, 1, 0},  // 0: the dense k x k convolutions with C % 32 == 0 stay on conv_generic_kernel instead of conv_mfma_kernel (the matrix cores)
+        // the same convolutions (whatever "conv_mfma" says) on the bf16 matrix cores, conv_bf16_kernel: 1 = activations and filter values rounded to bf16 (nearest even),
+        // products accumulated in f32; 2 = every operand split into two bf16 values, three products for one (about f32 accuracy); 0 = as without the option, bit for bit
+        {"conv_bf16", &Model::conv_bf16_, 0, 2, O::kReplan},
         {"stem_run", &Model::stem_run_, 0, 32, 0},  // output rows per column run of stem_mfma_kernel (0: chosen per launch, the row-wise form where a run would be one row)
         {"pair_fuse", &Model::pair_fuse_, 0, 1, 0},  // 0: two plain blocks in a row keep a launch each (the face mesh's 48x48x32 blocks: mwalk_kernel), no mdblock_kernel<pair>
         {"mdb_band", &Model::mdb_band_, 0, 4096, 0},  // rows per band of the mdblock_kernel launches (0: chosen per launch)
@@ -163,7 +166,7 @@ void Model::rebuild() {
             if (plan_.root_offset[t] >= 0) { plan_.root_offset[t] = off; off += plan_.root_elems[t]; }
         plan_.arena_floats_per_frame = off;
     }
-    consts_ = pack_plan_consts(plan_);  // every constant the launches need and the stage programs (consts.cpp)
+    consts_ = pack_plan_consts(plan_, conv_bf16_);  // every constant the launches need and the stage programs (consts.cpp)
     upload(d_weights_, consts_.blob, "hipMalloc weights", "upload weights");  // (never empty: the blob ends in its slack)
     upload(d_tail_programs_, consts_.tail_progs, "hipMalloc programs", "upload programs");
     upload(d_programs_, consts_.progs, "hipMalloc programs", "upload programs");
@@ -344,7 +347,7 @@ LaunchCtx Model::launch_ctx(const float* in, int chunk_start, int frames) const 
     c.band_prog = d_band_prog_; c.band_consts = d_band_consts_; c.band_ws = d_band_ws_; c.band_sync = d_band_sync_; c.band_fail = d_band_fail_;
     c.chunk_cap = chunk_cap_; c.chunk_start = chunk_start; c.F = frames;
     c.u8_frames = u8_.frames; c.u8_lut = u8_.lut; c.u8_frame_bytes = u8_.frame_bytes; c.u8_row_bytes = u8_.row_bytes;
-    c.strip = strip_; c.pair_fuse = pair_fuse_; c.stem_fuse = stem_fuse_; c.stem_mfma = stem_mfma_; c.stem_run = stem_run_; c.mchain = mchain_; c.conv_mfma = conv_mfma_;
+    c.strip = strip_; c.pair_fuse = pair_fuse_; c.stem_fuse = stem_fuse_; c.stem_mfma = stem_mfma_; c.stem_run = stem_run_; c.mchain = mchain_; c.conv_mfma = conv_mfma_; c.conv_bf16 = conv_bf16_;
     c.small_chain = small_chain_; c.lanes = lanes_;
     c.pipe_rows = pipe_rows_; c.pipe_band = pipe_band_; c.mdb_band = mdb_band_; c.tail_pre = tail_pre_; c.tail_g = tail_g_;
     // (with several lanes the chunks already overlap; the head streams and node events are one set per model, and sharing

@@ -93,6 +93,7 @@ class Model {
     int chunk_ = 0, lanes_ = 1, use_graph_ = 1;                    // "chunk", "lanes", "graph"
     int fork_ = 1, head_streams_opt_ = 1;                          // "fork", "heads"
     int conv_mfma_ = 1;   // "conv_mfma"
+    int conv_bf16_ = 0;   // "conv_bf16"
     int strip_ = 1, stem_fuse_ = 1, stem_mfma_ = 1, stem_run_ = 0, pair_fuse_ = 1, mchain_ = 1, chain_fixed_ = 1, chain_sched_ = 1;   // "strip", "stem_fuse", "stem_mfma", "stem_run", "pair_fuse", "mchain", "chain_fixed", "chain_sched"
     int pipe_rows_ = 0, pipe_band_ = 0, mdb_band_ = 0;             // "pipe_rows", "pipe_band", "mdb_band"
     int tail_pre_ = 0, tail_g_ = 0;                                // "tail_pre", "tail_g"

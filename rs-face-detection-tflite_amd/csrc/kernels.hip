@@ -654,9 +654,10 @@ static bool pw_few_applicable(const ConvArgs& a) {
            (reinterpret_cast<uintptr_t>(a.in) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.w) & 15) == 0;
 }
 bool conv_takes_u8(const ConvArgs& a) { return stem_applicable(a); }
-const char* conv_kernel_label(const ConvArgs& a) { return conv_mfma_supports(a) ? "conv_mfma_kernel" : stem_applicable(a) ? (stem_mfma_applicable(a) ? "stem_mfma_kernel" : "stem_conv_kernel") : (pw_few_applicable(a) ? "pw_few_kernel" : "conv_generic_kernel"); }
+const char* conv_kernel_label(const ConvArgs& a) { return conv_bf16_supports(a) ? "conv_bf16_kernel" : conv_mfma_supports(a) ? "conv_mfma_kernel" : stem_applicable(a) ? (stem_mfma_applicable(a) ? "stem_mfma_kernel" : "stem_conv_kernel") : (pw_few_applicable(a) ? "pw_few_kernel" : "conv_generic_kernel"); }
 
 int launch_conv(const ConvArgs& a, void* stream) {
+    if (conv_bf16_supports(a)) return launch_conv_bf16(a, stream);
     if (conv_mfma_supports(a)) return launch_conv_mfma(a, stream);
     if (stem_applicable(a)) {
         hipStream_t st = (hipStream_t)stream;

@@ -46,6 +46,11 @@ struct ConvArgs {
     int stem_run = 0;           // output rows per column run of stem_mfma_kernel (engine option "stem_run"; 0: chosen per launch)
     const float* w_rows = nullptr;  // the filter as TFLite stores it, [Co][KH*KW*C]: the B operand of conv_mfma_kernel (null: the shape has no such form)
     int mfma = 0;               // 1: a dense convolution that conv_mfma_kernel takes runs there (engine option "conv_mfma")
+    // engine option "conv_bf16" (1: operands rounded to bf16, 2: split into hi + lo) and the filter [Co][KH*KW*C] rounded to bf16, two values
+    // a float slot: the B operand of conv_bf16_kernel, its `hi` plane and (2 only) its `lo` plane (null: the shape has no such form, or the option is 0)
+    int bf16 = 0;
+    const float* w_bf16 = nullptr;
+    const float* w_bf16_lo = nullptr;
 };
 
 
@@ -311,6 +316,11 @@ bool conv_takes_u8(const ConvArgs& a);  // the specialised stem kernel: the only
 bool conv_mfma_shape_ok(int C, int KH, int KW, int Co);
 bool conv_mfma_supports(const ConvArgs& a);
 int launch_conv_mfma(const ConvArgs& a, void* stream);
+// conv_bf16_kernels.hip: the same implicit GEMM on v_mfma_f32_32x32x16_bf16, operands rounded to bf16 or split into two bf16 values (ConvArgs::bf16).
+// conv_bf16_supports: the launch has the bf16 planes and conv_mfma_supports takes its shape (whatever ConvArgs::mfma says); launch_conv and
+// conv_kernel_label ask it first
+bool conv_bf16_supports(const ConvArgs& a);
+int launch_conv_bf16(const ConvArgs& a, void* stream);
 int launch_dw(const DwArgs& a, void* stream);
 int launch_block(const BlockArgs& a, void* stream);
 bool block_kernel_supports(const BlockArgs& a);

@@ -367,6 +367,11 @@ struct Lowering {
         a.no_mfma = c.stem_mfma == 0 ? 1 : c.stem_mfma == 2 ? 2 : 0;
         a.w_rows = weights(pc.node_wrows[i]);
         a.mfma = c.conv_mfma ? 1 : 0;
+        if (c.conv_bf16) {   // (planes that the constants were not packed with stay null, and the launch keeps its f32 kernel)
+            a.bf16 = c.conv_bf16;
+            a.w_bf16 = weights(pc.node_wbf16_hi[i]);
+            a.w_bf16_lo = weights(pc.node_wbf16_lo[i]);
+        }
         a.stem_run = c.stem_run;
         if (c.u8_frames && plan.storage[n.in[0]].root == plan.storage[g.inputs[0]].root) {
             if (!conv_takes_u8(a)) throw std::runtime_error("plan: this graph's first convolution has no u8 input form");

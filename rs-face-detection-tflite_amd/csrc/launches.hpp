@@ -48,6 +48,7 @@ struct LaunchCtx {
     // options (engine.cpp, find_option)
     int strip = 1, pair_fuse = 1, stem_fuse = 1, stem_mfma = 1, stem_run = 0, mchain = 1, small_chain = 16, lanes = 1;
     int conv_mfma = 1;
+    int conv_bf16 = 0;                   // 1 / 2: the convolutions conv_mfma_kernel has a form for take conv_bf16_kernel (the constants were packed with the same value)
     int pipe_rows = 0, pipe_band = 0, mdb_band = 0, tail_pre = 0, tail_g = 0;
     bool fork = true;                    // nodes of the side schedule leave the trunk (false: everything in line, no events)
     int cu_count = 256;
