@@ -794,6 +794,38 @@ __device__ __forceinline__ void strip_row_s2m(const float* me2, const cfloat* cs
     }
 }
 
+// What a MODE 2 call of strip_row_s2m computes for the output row it finishes when its even input row is the row of zeros below the
+// picture: the ky = 2 taps add zeros to the partial sums, so the started row `acc` is finished as it stands — accumulators from bias (+
+// max-pool), then the same MFMAs in the same order.  Reads no row image and no taps, starts no row.
+template <int CQ, int NH>
+__device__ __forceinline__ void strip_flush_s2m(const cfloat* cst, int hf, bool has_skip, const v2f (&acc)[CQ][2], const float4 (&mx)[CQ],
+                                                v4f (&oacc)[CQ], const float (&wa)[SK<CQ>::NA]) {
+    constexpr int C = 4 * CQ, Co = NH * C;
+    constexpr int ST2 = (32 + 2 * Co + 15) / 16 * 16, OFF_BIAS2 = (C / 2) * ST2;
+    const cfloat* bp = cst + OFF_BIAS2 + hf * C;
+    asm volatile("" : "+s"(bp));
+    if (has_skip) {
+#pragma unroll
+        for (int q = 0; q < CQ; q++) oacc[q] = v4f{mx[q].x, mx[q].y, mx[q].z, mx[q].w} + v4f{bp[4 * q], bp[4 * q + 1], bp[4 * q + 2], bp[4 * q + 3]};
+    } else {
+#pragma unroll
+        for (int q = 0; q < CQ; q++) oacc[q] = v4f{bp[4 * q], bp[4 * q + 1], bp[4 * q + 2], bp[4 * q + 3]};
+    }
+#pragma unroll
+    for (int st = 0; st < 2 * CQ; st++) {
+        const v2f pch = acc[st >> 1][st & 1];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const float bv = e ? pch.y : pch.x;
+#pragma unroll
+            for (int tq = 0; tq < CQ; tq++) {
+                const int nn = (2 * st + e) * CQ + tq;
+                oacc[tq] = mfma4_bcast(wa[nn >> 4], bv, oacc[tq], nn & 15);
+            }
+        }
+    }
+}
+
 template <int CQ, bool RELU>
 __global__ __launch_bounds__(256, CQ <= 6 ? 3 : 2) void strip_kernel(StripArgs a) {
     using K = SK<CQ>;
@@ -957,6 +989,9 @@ __global__ __launch_bounds__(256, CQ <= 6 ? 3 : 2) void strip_kernel(StripArgs a
 // free).  Only block 0 reads HBM (LDS-DMA) and only block KB-1 writes it: the HBM traffic of KB layers becomes that of
 // one.  Steps are separated by one s_barrier; block j lags block j-1 by two rows, so a band costs band_rows + 3 KB - 1
 // steps, and block j computes KB-1-j extra rows above and below the band (the halo of the blocks behind it).
+// (The two-row forms: block j lags by two steps, a band costs band_rows / 2 + 2 S - 1 steps for S stride-1 blocks, + 2 with a stride-2
+// tail.  strip_pipe2m_kernel on whole-frame bands leaves out the steps that see only rows outside the picture: floor(S / 2) at the top,
+// and the tail's flush step: 128 rows x 4 blocks 71 -> 69 steps, 3 blocks + tail 71 -> 69; 64 rows 39 -> 37 both.)
 constexpr int kMaxPipe = 4;
 struct PipeArgs {
     const float* in;
@@ -1751,11 +1786,23 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
     const cfloat* cst = (const cfloat*)a.consts[role];
     const bool has_res = a.has_res[role] != 0;
     const float hi = a.hi[role];
-    // the last stride-1 block produces rows [y0, hi_last): two more rows when a stride-2 tail follows (its third tap row,
-    // and one to keep the count even)
-    const int hi_last = NH2 ? y1 + 2 : y1;
+    // Whole-frame bands (one band per frame: y0 == 0 and y1 == H for every unit, so the condition is uniform over the workgroup): the halo
+    // rows above and below the band are rows outside the picture, i.e. zeros, and the steps that would only see them are left out.
+    //   Top: of the row pairs of block j, the first kskip = ceil((S - 1 - j) / 2) lie wholly above row 0.  Run on zeros they leave the
+    //   partial sums aA / aB at zero, where they start, and finish rows < 0 only, which hand_row replaces by zeros in a ring that was
+    //   cleared at kernel start; `onext` is first used for row c0 - 1 < 0 of the first executed pair.  Every block starts at its pair
+    //   kskip, and the whole schedule D = kskip of block 0 steps earlier: block j's pair m runs in step m - D + 2j (its predecessor finished
+    //   that pair's rows in the step before, as in the interior schedule).
+    //   Bottom (stride-2 tail): the last stride-1 block stops at row H, and the tail wave finishes its last output row in the step that
+    //   consumes the pair (H - 2, H - 1) instead of in a flush step whose ky = 2 taps read the zero row H (strip_flush_s2m).
+    const bool whole = a.bands == 1;
+    // the last stride-1 block produces rows [y0, hi_last): two more rows when a stride-2 tail follows in an interior band (its third tap
+    // row, and one to keep the count even)
+    const int hi_last = NH2 && !whole ? y1 + 2 : y1;
     const int lo_j = y0 - (S - 1 - role), hi_j = hi_last + (S - 1 - role);  // this (stride-1) block produces rows [lo_j, hi_j)
     const int P = (hi_j - lo_j + 2) >> 1;                                   // row pairs it consumes: (lo_j - 1 + 2m, lo_j + 2m)
+    const int D = whole ? S >> 1 : 0;                                       // steps the schedule starts early = pairs block 0 skips
+    const int kskip = whole && !tail ? (S - role) >> 1 : 0;                 // pairs this block skips
     const int img_p = a.strips == 2 ? 64 * PXS * p : 66 * PXS * p;
 
     for (int i = threadIdx.x; i < RING_F / 4; i += NT) reinterpret_cast<float4*>(lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1835,12 +1882,13 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         for (int i = 0; i < K::NA; i++) wa[i] = a.consts[S][OFF_A2 + (hf * K::NA + i) * 64 + lane];
     }
     prefetch_consts();
-    if (role == 0 && active) {
-        issue_row(lo_j - 1, 0);
-        issue_row(lo_j, 1);
-        if (P > 1) {
-            issue_row(lo_j + 1, 2);
-            issue_row(lo_j + 2, 3);
+    if (role == 0 && active) {  // the first two pairs block 0 executes (pairs D, D + 1: it runs pair t + D in step t, on buffer pair t & 1)
+        const int r0 = lo_j - 1 + 2 * D;
+        issue_row(r0, 0);
+        issue_row(r0 + 1, 1);
+        if (P - D > 1) {
+            issue_row(r0 + 2, 2);
+            issue_row(r0 + 3, 3);
         }
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -1901,7 +1949,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
     // ---- stride-2 tail: consumes the pair (even row, odd row) the last stride-1 block handed over in the previous step
     auto tail_step = [&](int t, v2f (&tacc)[CQ][2], float4 (&tmx)[CQ]) {
         if constexpr (NH2 > 0) {
-            const int mt = t - 2 * S;
+            const int mt = t + D - 2 * S;
             if (mt < 0 || 2 * mt > a.band_rows) return;
             const int k = 2 * mt;  // band-relative index of the even row
             constexpr int Co = NH2 * C;
@@ -1911,10 +1959,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
             const int tu = a.strips == 2 ? 0 : lane >> 5, tox = a.strips == 2 ? lane : lane & 31;
             const float* me2 = img + tu * 66 * PXS + (2 * tox + 1) * PXS;
             const bool skip = hf == 0 && a.has_res[S] != 0;
-            if (mt == 0) {
-                strip_row_s2m<CQ, NH2, 1, PXS>(me2, cst2, hf, skip, tacc, tmx, toacc, wa);
-            } else {
-                strip_row_s2m<CQ, NH2, 2, PXS>(me2, cst2, hf, skip, tacc, tmx, toacc, wa);
+            auto store_out = [&](int ke) {  // the output row that band-relative even row ke finishes: activation, transposition, store
                 float4 o[CQ];
                 strip_act<CQ, RELU>(toacc, cst2 + OFF_SLOPE2 + hf * C, a.hi[S], o);
                 float* obuf = scratch;
@@ -1930,33 +1975,44 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
                     const int ub = un % a.bands, bb = min(un / a.bands, a.B - 1);
                     const int uy0 = ub * a.band_rows, uy1 = min(uy0 + a.band_rows, a.H);
                     const float4 v = sld4(obuf + 4 * f);
-                    if (un < a.units && uy0 + k <= uy1 && ox < Wo) {
-                        const int oy = (uy0 + k - 2) >> 1;
+                    if (un < a.units && uy0 + ke <= uy1 && ox < Wo) {
+                        const int oy = (uy0 + ke - 2) >> 1;
                         sst4(a.out + (long)bb * a.out_fs + ((long)oy * Wo + ox) * Co + hf * C + 4 * qd, v);
                     }
                 }
                 wave_sync();
+            };
+            if (mt == 0) {
+                strip_row_s2m<CQ, NH2, 1, PXS>(me2, cst2, hf, skip, tacc, tmx, toacc, wa);
+            } else {
+                strip_row_s2m<CQ, NH2, 2, PXS>(me2, cst2, hf, skip, tacc, tmx, toacc, wa);
+                store_out(k);
             }
             if (k + 1 < a.band_rows) strip_row_s2m<CQ, NH2, 0, PXS>(me2 + IMG, cst2, hf, skip, tacc, tmx, toacc, wa);
+            if (whole && k + 2 == a.band_rows) {  // the pair (H - 2, H - 1): the last output row is finished here, row H being zeros
+                strip_flush_s2m<CQ, NH2>(cst2, hf, skip, tacc, tmx, toacc, wa);
+                store_out(k + 2);
+            }
         }
     };
     auto step = [&](int t) {
         v2f (&tacc)[CQ][2] = aA;
         float4 (&tmx)[CQ] = onext;
-        const int m = t - 2 * role;  // pair index of this block in this step
+        const int m = t + D - 2 * role;  // pair index of this block in this step
         const int c0 = lo_j - 1 + 2 * m;
+        const int bp = (t & 1) * 2;      // block 0 (m = t + D): DMA buffer pair of this step, counted from its first executed pair
         bool hand_over = false;
         float4 o0[CQ], o1[CQ];
-        if (!tail && active && m >= 0 && m < P) {
+        if (!tail && active && m >= kskip && m < P) {
             const float *me0, *me1;
             int ps;
             if (role == 0) {
                 if (m + 1 < P) wait_vm<2 * NL>();
                 else wait_vm<0>();
-                fix_row(c0, (m & 1) * 2);
-                fix_row(c0 + 1, (m & 1) * 2 + 1);
+                fix_row(c0, bp);
+                fix_row(c0 + 1, bp + 1);
                 wave_sync();
-                me0 = scratch + ((m & 1) * 2) * BUF_F + lane * C;
+                me0 = scratch + bp * BUF_F + lane * C;
                 me1 = me0 + BUF_F;
                 ps = C;
             } else {
@@ -1979,8 +2035,8 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
             }
             if (role == 0 && m + 2 < P) {
                 wave_sync();
-                issue_row(c0 + 4, (m & 1) * 2);
-                issue_row(c0 + 5, (m & 1) * 2 + 1);
+                issue_row(c0 + 4, bp);
+                issue_row(c0 + 5, bp + 1);
             }
         }
         if constexpr (NH2 > 0) {
@@ -2012,7 +2068,8 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         asm volatile("" ::: "memory");
         MI_PSTAMP(3)
     };
-    const int T = NH2 ? 2 * S + a.band_rows / 2 + 1 : 2 * S - 1 + a.band_rows / 2;
+    // interior bands: 2 S - 1 fill steps + band_rows / 2 (+ 2 with a tail: its own lag and its flush step); whole frames: D fewer, and no flush
+    const int T = (NH2 ? 2 * S + a.band_rows / 2 + (whole ? 0 : 1) : 2 * S - 1 + a.band_rows / 2) - D;
     for (int t = 0; t < T; t++) step(t);
 #ifdef MI_PIPE_STAMPS
     if (a.stamps && lane == 0) {
