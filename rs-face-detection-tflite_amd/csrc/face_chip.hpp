@@ -1,6 +1,6 @@
 // face_chip.hpp — the rectangle FaceEmbeddings::infer crops before it resizes to 112 x 112 (reference:
 // /root/reference/src/face_detection_lite/face_embeddings.rs:54,101-109 with types.rs:162-165,219-225).  The arithmetic below is the only
-// statement of the rule; the host entries (mi_face_chip_rect, mi_fe_infer_image in capi.cpp) and chip_geom_kernel (preproc.hip) both go
+// statement of the rule; the host entries (mi_face_chip_rect, mi_fe_infer_image in capi_embed.cpp) and chip_geom_kernel (preproc.hip) both go
 // through it.
 //
 //   bbox = detection.bbox().scale((width, height)): each of xmin, ymin, xmax, ymax is the detection's f32 widened to f64, times the picture

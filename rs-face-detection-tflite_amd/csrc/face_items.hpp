@@ -1,5 +1,5 @@
 // face_items.hpp — the item list of mi_pipeline_run_faces: which (frame, face) pairs get a mesh / iris slot.  The per-slot arithmetic below is
-// the only statement of the rule; the host entry mi_face_items_layout (capi.cpp) and face_items_kernel (preproc.hip) both go through it.
+// the only statement of the rule; the host entry mi_face_items_layout (capi_pipeline.cpp) and face_items_kernel (preproc.hip) both go through it.
 //
 //   frame b contributes n_b = min(max(face_counts[b], 0), max_faces) faces; item j = (sum of n_b' for b' < b) + k is face k of frame b while
 //   j < max_items; n_items = {min(total, max_items), total - min(total, max_items)}; slots behind the last item hold -1 / -1.

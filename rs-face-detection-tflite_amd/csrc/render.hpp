@@ -1,5 +1,5 @@
 // render.hpp — device-side render_to_image (render.rs:361-479) over a batch: the canvas phase (RGB -> RGBA / RGB) and the draw
-// phase (one workgroup per frame, annotations in list order).  Kernels in render_kernels.hip; the C entries are in capi.cpp.
+// phase (one workgroup per frame, annotations in list order).  Kernels in render_kernels.hip; the C entries are in capi_render.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>

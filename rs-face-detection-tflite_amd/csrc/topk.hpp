@@ -1,5 +1,5 @@
 // topk.hpp — which gallery rows a query matches: the selection rule of mi_topk_select and mi_gallery_topk.  The comparator and the list
-// operations below are the only statement of the rule; the host entry mi_topk_select (capi.cpp) and the kernels of topk_kernels.hip all go
+// operations below are the only statement of the rule; the host entry mi_topk_select (capi_embed.cpp) and the kernels of topk_kernels.hip all go
 // through them.
 //
 //   For query row i, gallery row j is ELIGIBLE iff S[i][j] > -INFINITY is true: NaN (a zero query or a zero gallery row, through the
