@@ -225,7 +225,7 @@ __global__ __launch_bounds__(K::NWV * 64, 2) void mdblock_kernel(MdbArgs a) {
         for (int i = threadIdx.x; i < K::STEM_F / 4; i += NWV * 64) reinterpret_cast<float4*>(wst)[i] = reinterpret_cast<const float4*>(a.sconsts)[i];
     issue_row(y0 - 1, 1);
     if constexpr (K::STEM) __syncthreads();   // (the constants: also drains the loads above)
-    else { dwait_vm<NLD>(); dwg_barrier(); }
+    else { wait_vm<NLD>(); dwg_barrier(); }
     asm volatile("" ::: "memory");
     if constexpr (K::STEM) stem_emit(y0 - 2, 0);   // x row y0 - 2: complete for everybody at step 0's barrier
     // depthwise taps of this lane's channels: tap[ks][t] = w_dw[t][4 ks + kq], resident in registers for the whole kernel
@@ -327,10 +327,10 @@ __global__ __launch_bounds__(K::NWV * 64, 2) void mdblock_kernel(MdbArgs a) {
     auto wait_row = [&](int t) {
         if constexpr (K::STEM) return;   // (no DMA: the compiler counts the loads and stores it sees)
         const bool st = t - 1 >= 4, dm = t == 0 || t + 1 <= TL;  // step 0: the prologue's second row is behind it
-        if (st && dm) dwait_vm<NST + NLD>();
-        else if (dm) dwait_vm<NLD>();
-        else if (st) dwait_vm<NST>();
-        else dwait_vm<0>();
+        if (st && dm) wait_vm<NST + NLD>();
+        else if (dm) wait_vm<NLD>();
+        else if (st) wait_vm<NST>();
+        else wait_vm<0>();
     };
     // e1 / e2: stage 1 / stage 2 finish a row in this step
     auto step = [&](auto e1c, auto e2c, int t, RowAcc<WT> (&q1PN)[CK1], RowAcc<WT> (&q1C)[CK1], RowAcc<WT> (&q2PN)[CK2], RowAcc<WT> (&q2C)[CK2], df32x4 (&P)[MT2][WT]) {
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(K::NWV * 64, 2) void mdblock_kernel(MdbArgs a) {
         }
         if constexpr (!K::PAIR) init_P(P, slot);   // output row r starts from bias + its skip, the centre pixels of x row r
         __builtin_amdgcn_sched_barrier(0);
-        dwave_sync();      // every read of x image `slot` by this wave is issued before the DMA below overwrites this wave's part of it
+        wave_sync();      // every read of x image `slot` by this wave is issued before the DMA below overwrites this wave's part of it
         __builtin_amdgcn_s_waitcnt(0xC07F);  // ... and has returned (the other waves read row r's halo pixels before the a-row barrier)
         if constexpr (K::STEM) {
             // x row r + 1 -> the other image: its last readers (row r - 1: stage 1 and the skips) passed the previous step's a-row barrier
@@ -481,7 +481,7 @@ __global__ __launch_bounds__(K::NF * K::NWV * 64, 2) void mbneck_kernel(MdbArgs 
     issue_row(y0 - 1, 0);
     for (int i = threadIdx.x; i < K::TOTAL / 4; i += NF * NWV * 64) reinterpret_cast<float4*>(wgc)[i] = reinterpret_cast<const float4*>(a.consts)[i];
     issue_row(y0, 1);
-    dwait_vm<NLD>();
+    wait_vm<NLD>();
     dwg_barrier();
     asm volatile("" ::: "memory");
     dv2f tap2[CK2][5];
@@ -563,17 +563,17 @@ __global__ __launch_bounds__(K::NF * K::NWV * 64, 2) void mbneck_kernel(MdbArgs 
     const int TL = (y1 - y0) + 1;
     auto wait_row = [&](int t) {
         const bool st = t - 1 >= 2, dm = t == 0 || t + 1 <= TL;
-        if (st && dm) dwait_vm<NST + NLD>();
-        else if (dm) dwait_vm<NLD>();
-        else if (st) dwait_vm<NST>();
-        else dwait_vm<0>();
+        if (st && dm) wait_vm<NST + NLD>();
+        else if (dm) wait_vm<NLD>();
+        else if (st) wait_vm<NST>();
+        else wait_vm<0>();
     };
     auto step = [&](auto e2c, int t, RowAcc<WT> (&q2PN)[CK2], RowAcc<WT> (&q2C)[CK2], df32x4 (&Pc)[MT2][WT], df32x4 (&Pi)[MT2][WT]) {
         constexpr bool E2 = decltype(e2c)::value;
         const int r = y0 - 1 + t, slot = t & 1;
         wait_row(t);
         fix_row(r, slot);
-        dwave_sync();
+        wave_sync();
         init_D1();
         mpw_row<CK1, MT1, WT, PS>(xc_lds + (unsigned)(slot * XIMG_F * 4), a1_lds, D1);
         __builtin_amdgcn_sched_barrier(0);
@@ -586,7 +586,7 @@ __global__ __launch_bounds__(K::NF * K::NWV * 64, 2) void mbneck_kernel(MdbArgs 
         __builtin_amdgcn_sched_barrier(0);
         init_P(Pi, slot);   // output row r starts from bias + its skip, the centre pixels of x row r
         __builtin_amdgcn_sched_barrier(0);
-        dwave_sync();
+        wave_sync();
         __builtin_amdgcn_s_waitcnt(0xC07F);
         if (t + 2 <= TL) issue_row(r + 2, slot);
     };

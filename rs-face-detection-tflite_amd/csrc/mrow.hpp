@@ -8,19 +8,14 @@
 #include <type_traits>
 #include <utility>
 
+#include "wave_sync.hpp"
+
 namespace mi {
 
 namespace {
 
 typedef float df32x4 __attribute__((ext_vector_type(4)));
 
-template <int N>
-__device__ __forceinline__ void dwait_vm() { __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70); }
-__device__ __forceinline__ void dwave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // workgroup barrier behind an LDS-only wait (__syncthreads() would also drain vmcnt: the next row's DMA and the output stores)
 __device__ __forceinline__ void dwg_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

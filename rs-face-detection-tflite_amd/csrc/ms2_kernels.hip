@@ -61,9 +61,9 @@ struct MS2 {
 
 __device__ __forceinline__ void ms2_wait_le(int n) {   // s_waitcnt vmcnt(n), n a multiple of 4 up to 44 (wave-uniform)
     switch (n >> 2) {
-        case 0: dwait_vm<0>(); break;  case 1: dwait_vm<4>(); break;  case 2: dwait_vm<8>(); break;   case 3: dwait_vm<12>(); break;
-        case 4: dwait_vm<16>(); break; case 5: dwait_vm<20>(); break; case 6: dwait_vm<24>(); break;  case 7: dwait_vm<28>(); break;
-        case 8: dwait_vm<32>(); break; case 9: dwait_vm<36>(); break; case 10: dwait_vm<40>(); break; default: dwait_vm<44>(); break;
+        case 0: wait_vm<0>(); break;  case 1: wait_vm<4>(); break;  case 2: wait_vm<8>(); break;   case 3: wait_vm<12>(); break;
+        case 4: wait_vm<16>(); break; case 5: wait_vm<20>(); break; case 6: wait_vm<24>(); break;  case 7: wait_vm<28>(); break;
+        case 8: wait_vm<32>(); break; case 9: wait_vm<36>(); break; case 10: wait_vm<40>(); break; default: wait_vm<44>(); break;
     }
 }
 

@@ -38,6 +38,7 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "wave_sync.hpp"
 
 namespace mi {
 
@@ -87,14 +88,6 @@ struct MK {
     static constexpr int WG_F = A_F + 2 * C + TAP_F;   // LDS floats shared by a workgroup: A operands, bias, slopes, taps (read once)
     static constexpr int NBUF = 2;
 };
-
-template <int N>
-__device__ __forceinline__ void mwait_vm() { __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70); }
-__device__ __forceinline__ void mwave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <class F, int... KS>
 __device__ __forceinline__ void mfor_each(F&& f, std::integer_sequence<int, KS...>) { (f(std::integral_constant<int, KS>{}), ...); }
@@ -178,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void mstrip_kernel(MstripArgs a) {
     // operations retire in issue order): the compiler counts only its own loads when it places vmcnt waits — always safe, since a
     // counted wait also covers everything older — but the loop's own counted waits assume that nothing else is outstanding.
     if (active) issue_row(y0, 1);
-    if (active) mwait_vm<NLD>(); else mwait_vm<0>();
+    if (active) wait_vm<NLD>(); else wait_vm<0>();
     MI_MSTAMP(6)
     // raw barrier behind an LDS-only wait: __syncthreads() would also drain vmcnt, i.e. wait for the second row
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -338,16 +331,16 @@ __global__ __launch_bounds__(256, 2) void mstrip_kernel(MstripArgs a) {
     constexpr int NST = 2 * MT;
     auto wait_row = [&](int t) {  // t = step number (row y0 - 1 + t)
         const bool st = t - 1 >= 2, dm = t == 0 || (t - 1) + 2 <= (y1 - y0 + 1);  // step 0: the prologue's second row is behind it
-        if (st && dm) mwait_vm<NST + NLD>();
-        else if (dm) mwait_vm<NLD>();
-        else if (st) mwait_vm<NST>();
-        else mwait_vm<0>();
+        if (st && dm) wait_vm<NST + NLD>();
+        else if (dm) wait_vm<NLD>();
+        else if (st) wait_vm<NST>();
+        else wait_vm<0>();
     };
     auto step = [&](auto emit, int r, float (&aPN)[CK][2], float (&aC)[CK][2]) {
         const int t = r - (y0 - 1), bi = t & 1;
         wait_row(t);
         fix_row(r, bi);
-        mwave_sync();
+        wave_sync();
         MI_MSTAMP(1)
         row(emit, bi, aPN, aC);
         MI_MSTAMP(2)
@@ -357,7 +350,7 @@ __global__ __launch_bounds__(256, 2) void mstrip_kernel(MstripArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         init_D(bi);     // output row r starts from bias + its skip, the centre pixels of input row r
         __builtin_amdgcn_sched_barrier(0);
-        mwave_sync();   // every read of image bi is issued before the DMA below overwrites it
+        wave_sync();   // every read of image bi is issued before the DMA below overwrites it
         __builtin_amdgcn_s_waitcnt(0xC07F);  // ... and has returned (LDS-DMA writes are not ordered behind this wave's earlier reads)
         if (r + 2 <= y1) issue_row(r + 2, bi);
         MI_MSTAMP(4)
@@ -465,7 +458,7 @@ __global__ __launch_bounds__(512, 2) void mstrip_chain_kernel(MstripChainArgs ca
         }
     }
     issue_row(y0, 1);
-    mwait_vm<NLD>();
+    wait_vm<NLD>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (blk == 0) {   // block 0's constants (plain stores above) are visible to every wave
         __builtin_amdgcn_s_barrier();
@@ -624,16 +617,16 @@ __global__ __launch_bounds__(512, 2) void mstrip_chain_kernel(MstripChainArgs ca
     constexpr int NST = 2 * MT;
     auto wait_row = [&](int t) {  // t = step number (row y0 - 1 + t)
         const bool st = t - 1 >= 2, dm = t == 0 || (t - 1) + 2 <= (y1 - y0 + 1);  // step 0: the prologue's second row is behind it
-        if (st && dm) mwait_vm<NST + NLD>();
-        else if (dm) mwait_vm<NLD>();
-        else if (st) mwait_vm<NST>();
-        else mwait_vm<0>();
+        if (st && dm) wait_vm<NST + NLD>();
+        else if (dm) wait_vm<NLD>();
+        else if (st) wait_vm<NST>();
+        else wait_vm<0>();
     };
     auto step = [&](auto emit, int r, float (&aPN)[CK][2], float (&aC)[CK][2]) {
         const int t = r - (y0 - 1), bi = t & 1;
         wait_row(t);
         fix_row(r, bi);
-        mwave_sync();
+        wave_sync();
         MI_MSTAMP(1)
         row(emit, bi, aPN, aC);
         MI_MSTAMP(2)
@@ -643,7 +636,7 @@ __global__ __launch_bounds__(512, 2) void mstrip_chain_kernel(MstripChainArgs ca
         __builtin_amdgcn_sched_barrier(0);
         init_D(bi);     // output row r starts from bias + its skip, the centre pixels of input row r
         __builtin_amdgcn_sched_barrier(0);
-        mwave_sync();   // every read of image bi is issued before the DMA below overwrites it
+        wave_sync();   // every read of image bi is issued before the DMA below overwrites it
         __builtin_amdgcn_s_waitcnt(0xC07F);  // ... and has returned (LDS-DMA writes are not ordered behind this wave's earlier reads)
         if (r + 2 <= y1) issue_row(r + 2, bi);
         MI_MSTAMP(4)

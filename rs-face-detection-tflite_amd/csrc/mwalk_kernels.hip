@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void mwalk_kernel(MwalkArgs a) {
     if (active) issue_row(y0 - 1, 0);
     for (int i = threadIdx.x; i < K::TOTAL / 4; i += 256) reinterpret_cast<float4*>(wgc)[i] = reinterpret_cast<const float4*>(a.consts)[i];
     if (active) issue_row(y0, 1);
-    if (active) dwait_vm<NLD>(); else dwait_vm<0>();
+    if (active) wait_vm<NLD>(); else wait_vm<0>();
     dwg_barrier();   // the only workgroup-level synchronisation of the kernel
     asm volatile("" ::: "memory");
     // depthwise taps of this lane's channels: tap[ks][t] = w_dw[t][4 ks + kq], resident in registers for the whole kernel
@@ -201,23 +201,23 @@ __global__ __launch_bounds__(256, 2) void mwalk_kernel(MwalkArgs a) {
     constexpr int NST = MT * WT;
     auto wait_row = [&](int t) {  // t = step number (row y0 - 1 + t)
         const bool st = t - 1 >= 2, dm = t == 0 || (t - 1) + 2 <= (y1 - y0 + 1);  // step 0: the prologue's second row is behind it
-        if (st && dm) dwait_vm<NST + NLD>();
-        else if (dm) dwait_vm<NLD>();
-        else if (st) dwait_vm<NST>();
-        else dwait_vm<0>();
+        if (st && dm) wait_vm<NST + NLD>();
+        else if (dm) wait_vm<NLD>();
+        else if (st) wait_vm<NST>();
+        else wait_vm<0>();
     };
     auto step = [&](auto emit, int r, RowAcc<WT> (&aPN)[CK], RowAcc<WT> (&aC)[CK]) {
         const int t = r - (y0 - 1), bi = t & 1;
         wait_row(t);
         fix_row(r, bi);
-        dwave_sync();
+        wave_sync();
         mdb_row<CK, MT, WT, PS, decltype(emit)::value, K::TAPL>(x_lds + (unsigned)(bi * IMG_F * 4), a_lds, tap, aPN, aC, D, reinterpret_cast<const float4*>(wgc + K::OFF_TAP) + kq * 3);
         __builtin_amdgcn_sched_barrier(0);  // (fences: the old and the new accumulator tiles are never live together)
         if constexpr (decltype(emit)::value) epilogue(r - 1);
         __builtin_amdgcn_sched_barrier(0);
         init_D(bi);     // output row r starts from bias + its skip, the centre pixels of input row r
         __builtin_amdgcn_sched_barrier(0);
-        dwave_sync();   // every read of image bi is issued before the DMA below overwrites it
+        wave_sync();   // every read of image bi is issued before the DMA below overwrites it
         __builtin_amdgcn_s_waitcnt(0xC07F);  // ... and has returned (LDS-DMA writes are not ordered behind this wave's earlier reads)
         if (r + 2 <= y1) issue_row(r + 2, bi);
     };

@@ -33,6 +33,7 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "wave_sync.hpp"
 
 namespace mi {
 
@@ -44,13 +45,6 @@ __device__ __forceinline__ float4 rld4(const float* p) { return *reinterpret_cas
 __device__ __forceinline__ float4 rmax4(float4 a, float4 b, float4 c, float4 d) {
     return make_float4(fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x)), fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y)),
                        fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z)), fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w)));
-}
-// LDS traffic between the lanes of ONE wave: the hardware executes a wave's LDS instructions in order; this only stops the
-// compiler from moving accesses across the hand-over.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 __device__ __forceinline__ float* resolve(const ResBases& bs, const ResRef& r, int frame) {
     return bs.p[r.base] + r.root_off * bs.scale[r.base] + r.inner + (long)(frame + bs.frame0[r.base]) * r.fs;

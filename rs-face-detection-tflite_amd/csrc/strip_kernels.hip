@@ -1,6 +1,13 @@
 // strip_kernels.hip — register-resident fused BlazeBlocks for the narrow layers (C in {16, 24, 32}), one block per launch
-// (strip_kernel) or a run of 2..4 blocks per launch with the rows handed from block to block through LDS
-// (strip_pipe_kernel), optionally ended by the stride-2 block that halves the resolution.
+// (strip_kernel) or a run of 2..4 blocks per launch with the rows handed from block to block through LDS (the four row
+// pipelines, option "pipe_rows": strip_pipe_kernel / strip_pipe2_kernel, one row / a row pair per step, pointwise conv as packed
+// FMAs; strip_pipe1m_kernel / strip_pipe2m_kernel, the same two schedules with the pointwise conv on the matrix cores — the
+// default), optionally ended by the stride-2 block that halves the resolution.  The four give bit-equal results.
+//
+// Layout of the file: constant-blob layouts (SK, SK2) | row functions (strip_row*: what a wave computes from one row or row
+// pair) | the frame around them, written once as plain functions (row DMA, transposed store, hand-over, ring clear, barriers,
+// tail store, the MFMA forms' constant prefetch) | the five kernels: step schedules, and the few pieces that had to stay
+// inline (noted where they stand) | launchers, blob packers.
 //
 //   out = act( PW1x1( DW3x3(in) + b_dw ) + b_pw + in )
 //
@@ -16,9 +23,11 @@
 //     channel quad and row — each input element is read from LDS three times instead of nine — and vertical reuse is in
 //     registers: the partial output rows an input row contributes to (ky = 2, 1, 0) stay in VGPR accumulators.
 //   * depthwise AND pointwise weights are wave-uniform in this layout: they arrive through the scalar cache as SGPR-pair
-//     operands of v_pk_fma_f32 (two channels per VALU lane-op), no LDS or VGPR cost.  The 1x1 conv is NOT on the matrix
-//     cores: on gfx950 the f32 MFMA has the packed-FMA peak, does not overlap VALU work, and M = 32 wastes a quarter of it
-//     on 24 channels (the MFMA variant of this kernel, with v_permlane32_swap layout changes, is in the git history).
+//     operands of v_pk_fma_f32 (two channels per VALU lane-op), no LDS or VGPR cost.  In strip_kernel and the packed-FMA
+//     pipelines the 1x1 conv stays on the VALU (the 32x32 f32 MFMA has the packed-FMA peak, does not overlap VALU work, and
+//     M = 32 wastes a quarter of it on 24 channels); the MFMA pipelines run it as v_mfma_f32_4x4x1_16b_f32 in the same
+//     lane = pixel layout, filter resident in NA registers, which leaves only the depthwise taps in the scalar stream
+//     (strip_row2m).
 //   * + bias (folded W b_dw + b_pw) + skip (the centre input row, still in VGPRs) -> activation -> transposed back
 //     through LDS so that every store instruction writes 1 KiB of consecutive bytes (full 128-byte lines instead of
 //     16-byte pieces that have to meet in L2).
@@ -33,6 +42,7 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "wave_sync.hpp"
 
 namespace mi {
 
@@ -72,20 +82,18 @@ struct SK {
     static constexpr int NA = (C * CQ + 15) / 16;
     static constexpr int OFF_DW = 0, OFF_BIAS = K2 * ST_F, OFF_SLOPE = OFF_BIAS + 32, OFF_A = OFF_SLOPE + 32, TOTAL = OFF_A + 64 * NA;
 };
+// constants blob of a stride-2 tail block (C -> NH2 * C channels): the same stage records with NH2 * C wide pointwise columns (at 32 and
+// 32 + Co), then 64 floats of bias, 64 of slopes, and per C output channels (tail wave hf) one C x C filter slice as SK::NA A-operand registers
+template <int CQ, int NH2>
+struct SK2 {
+    static constexpr int C = 4 * CQ, Co = NH2 * C;
+    static constexpr int ST_F = (32 + 2 * Co + 15) / 16 * 16;
+    static constexpr int OFF_BIAS = (C / 2) * ST_F, OFF_SLOPE = OFF_BIAS + 64, OFF_A = OFF_BIAS + 128, TOTAL = OFF_A + NH2 * SK<CQ>::NA * 64;
+};
 
 __device__ __forceinline__ float4 sld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void sst4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-// LDS traffic between the lanes of ONE wave: the hardware executes a wave's LDS instructions in order; this only has to
-// stop the compiler from moving accesses across the hand-over.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ v2f pkfma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-// s_waitcnt vmcnt(N) only (gfx9 encoding: vmcnt = imm[15:14]:imm[3:0], expcnt and lgkmcnt left at their maxima)
-template <int N>
-__device__ __forceinline__ void wait_vm() { __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70); }
 
 // One input row r (pixel-major image in LDS; `me` = this lane's left neighbour in it): its ky = 2 / 1 / 0 taps go to the partial output rows r-1 / r / r+1 (aPN on
 // entry / aC / aPN on exit: the slot of the row that finishes here is re-used for the row that starts here); the finished
@@ -609,7 +617,7 @@ template <int CQ, int NH, int MODE, int PS = 4 * CQ>
 __device__ __forceinline__ void strip_row_s2(const float* me2, const cfloat* cst, int hf, bool has_skip, v2f (&acc)[CQ][2], float4 (&mx)[CQ],
                                              v2f (&oacc)[2 * CQ]) {
     constexpr int C = 4 * CQ, Co = NH * C;
-    constexpr int ST2 = (32 + 2 * Co + 15) / 16 * 16, OFF_BIAS2 = (C / 2) * ST2;
+    constexpr int ST2 = SK2<CQ, NH>::ST_F, OFF_BIAS2 = SK2<CQ, NH>::OFF_BIAS;
     float wd[18], wp0[C], wp1[C];
     float4 xbuf[2][3];
     auto load_first = [&](int st) {
@@ -713,8 +721,8 @@ __device__ __forceinline__ void strip_row_s2(const float* me2, const cfloat* cst
 template <int CQ, int NH, int MODE, int PS>
 __device__ __forceinline__ void strip_row_s2m(const float* me2, const cfloat* cst, int hf, bool has_skip, v2f (&acc)[CQ][2], float4 (&mx)[CQ],
                                               v4f (&oacc)[CQ], const float (&wa)[SK<CQ>::NA]) {
-    constexpr int C = 4 * CQ, Co = NH * C;
-    constexpr int ST2 = (32 + 2 * Co + 15) / 16 * 16, OFF_BIAS2 = (C / 2) * ST2;
+    constexpr int C = 4 * CQ;
+    constexpr int ST2 = SK2<CQ, NH>::ST_F, OFF_BIAS2 = SK2<CQ, NH>::OFF_BIAS;
     float wd[2][18];
     float4 xbuf[2][3];
     auto load_taps = [&](int st) {
@@ -800,8 +808,8 @@ __device__ __forceinline__ void strip_row_s2m(const float* me2, const cfloat* cs
 template <int CQ, int NH>
 __device__ __forceinline__ void strip_flush_s2m(const cfloat* cst, int hf, bool has_skip, const v2f (&acc)[CQ][2], const float4 (&mx)[CQ],
                                                 v4f (&oacc)[CQ], const float (&wa)[SK<CQ>::NA]) {
-    constexpr int C = 4 * CQ, Co = NH * C;
-    constexpr int ST2 = (32 + 2 * Co + 15) / 16 * 16, OFF_BIAS2 = (C / 2) * ST2;
+    constexpr int C = 4 * CQ;
+    constexpr int OFF_BIAS2 = SK2<CQ, NH>::OFF_BIAS;
     const cfloat* bp = cst + OFF_BIAS2 + hf * C;
     asm volatile("" : "+s"(bp));
     if (has_skip) {
@@ -826,6 +834,73 @@ __device__ __forceinline__ void strip_flush_s2m(const cfloat* cst, int hf, bool 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The frame around the row functions, written once for all five kernels: plain functions of scalars and array references, so
+// that a kernel's locals stay its own registers.  Part 1: one wave's strip of 64 pixel columns at x0 — how its input rows
+// arrive, what of a landed row lies outside the picture, how a finished row goes to memory.
+//
+// Row image in LDS: [66 pixels][C] floats, filled by LDS-DMA (global_load_lds_dwordx4: LDS destination = M0 + offset +
+// 16 * lane, source address per lane), so float4 number f = lane + 64k of the image comes from (pixel f / CQ, quad
+// f % CQ) of the strip.  A lane whose pixel lies outside the image (halo of an edge strip, tail of a partial strip)
+// reads a clamped in-image pixel instead; the one pixel column that must be zero (left of x = 0, right of x = W-1)
+// is cleared in LDS after the DMA has landed — no per-lane branches around the memory instructions.
+// The DMA is issued from inline asm: hipcc would otherwise drain vmcnt(0) before every LDS read that follows a DMA
+// it can see (it cannot tell the row buffers apart), which serialises the two-rows-ahead prefetch.
+// strip_goff: byte offset of the lane's float4 from the row start, per DMA instruction.  The rest of the edge (npx, full, zfix, gout) and
+// fix_row stay in the kernels: as shared functions they moved compiler-inserted waits (profiles/strip_frame_isa.txt).
+template <int CQ>
+__device__ __forceinline__ void strip_goff(int lane, int x0, int W, int (&goff)[SK<CQ>::NL]) {
+    using K = SK<CQ>;
+#pragma unroll
+    for (int k = 0; k < K::NL; k++) {
+        const int f = min(lane + 64 * k, K::NF - 1), px = f / CQ, qd = f - px * CQ;
+        goff[k] = (min(max(x0 - 1 + px, 0), W - 1) * K::C + 4 * qd) * 4;
+    }
+}
+// wave-uniform LDS byte address of the wave's buffers: the DMA's M0
+__device__ __forceinline__ unsigned lds_addr(float* p) { return __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)p); }
+// start the DMA of input row r into row buffer bi (always NL instructions, so that counted vmcnt waits stay valid;
+// a row outside the image reads a clamped row and is zeroed when it is consumed)
+template <int CQ>
+__device__ __forceinline__ void strip_issue_row(const float* in, int H, int W, unsigned lds_buf, const int (&goff)[SK<CQ>::NL], int r, int bi) {
+    using K = SK<CQ>;
+    constexpr int C = K::C, NL = K::NL, BUF_F = K::BUF_F;
+    const char* src = reinterpret_cast<const char*>(in + (long)min(max(r, 0), H - 1) * W * C);
+    const unsigned dstb = lds_buf + (unsigned)(bi * BUF_F * 4);
+    constexpr int TAIL = K::NF - 64 * (NL - 1);  // active lanes of the last instruction
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+        if (k < NL - 1 || TAIL == 64) {
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dstb + 1024u * k), "v"(goff[k]), "s"(src) : "memory", "m0");
+        } else {
+            unsigned long long saved;
+            asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %0"
+                         : "=&s"(saved) : "s"(dstb + 1024u * k), "v"(goff[k]), "s"(src), "n"((1ull << (TAIL & 63)) - 1) : "memory", "m0");
+        }
+    }
+}
+// finished (activated) output row y -> memory, transposed through `obuf` so that every store instruction writes 1 KiB of consecutive
+// bytes.  SYNC: a trailing wave_sync(), for callers that write obuf again at once (the two-row forms)
+template <int CQ, bool SYNC>
+__device__ __forceinline__ void strip_store_row(float* obuf, float* out, int W, int lane, long gout, bool full, int npx, int y, const float4 (&o)[CQ]) {
+    constexpr int C = 4 * CQ;
+#pragma unroll
+    for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
+    wave_sync();
+    float* dst = out + (long)y * W * C + gout;
+    if (full) {  // wave-uniform
+#pragma unroll
+        for (int k = 0; k < CQ; k++) sst4(dst + 256 * k, sld4(obuf + 4 * lane + 256 * k));
+    } else {
+#pragma unroll
+        for (int k = 0; k < CQ; k++) {
+            const float4 v = sld4(obuf + 4 * lane + 256 * k);
+            if (lane + 64 * k < npx * CQ) sst4(dst + 256 * k, v);
+        }
+    }
+    if (SYNC) wave_sync();
+}
+
 template <int CQ, bool RELU>
 __global__ __launch_bounds__(256, CQ <= 6 ? 3 : 2) void strip_kernel(StripArgs a) {
     using K = SK<CQ>;
@@ -846,47 +921,17 @@ __global__ __launch_bounds__(256, CQ <= 6 ? 3 : 2) void strip_kernel(StripArgs a
     float* out = a.out + (long)b * a.out_fs;
     // constant address space: the blob is never written while kernels run, and wave-uniform loads from it become s_load
     const cfloat* cst = (const cfloat*)a.consts;
-
-    // Row image in LDS: [66 pixels][C] floats, filled by LDS-DMA (global_load_lds_dwordx4: LDS destination = M0 + offset +
-    // 16 * lane, source address per lane), so float4 number f = lane + 64k of the image comes from (pixel f / CQ, quad
-    // f % CQ) of the strip.  A lane whose pixel lies outside the image (halo of an edge strip, tail of a partial strip)
-    // reads a clamped in-image pixel instead; the one pixel column that must be zero (left of x = 0, right of x = W-1)
-    // is cleared in LDS after the DMA has landed — no per-lane branches around the memory instructions.
-    // The DMA is issued from inline asm: hipcc would otherwise drain vmcnt(0) before every LDS read that follows a DMA
-    // it can see (it cannot tell the three row buffers apart), which serialises the two-rows-ahead prefetch.
-    int goff[NL];  // byte offset of the lane's float4 from the row start, per DMA instruction
-#pragma unroll
-    for (int k = 0; k < NL; k++) {
-        const int f = min(lane + 64 * k, K::NF - 1), px = f / CQ, qd = f - px * CQ;
-        goff[k] = (min(max(x0 - 1 + px, 0), a.W - 1) * C + 4 * qd) * 4;
-    }
+    int goff[NL];
+    strip_goff<CQ>(lane, x0, a.W, goff);
     const int npx = min(64, a.W - x0);              // valid pixels of this strip
     const bool full = npx == 64;
     const int zl = x0 == 0 ? 0 : -1;                // image pixel columns to clear (-1: none)
     const int zr = x0 + 64 >= a.W ? npx + 1 : -1;
     const long gout = (long)x0 * C + 4 * lane;
-    const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)wbase);
-
-    // start the DMA of input row r into row buffer bi (always NL instructions, so that counted vmcnt waits stay valid;
-    // a row outside the image reads a clamped row and is zeroed when it is consumed)
-    auto issue_row = [&](int r, int bi) {
-        const char* src = reinterpret_cast<const char*>(in + (long)min(max(r, 0), a.H - 1) * a.W * C);
-        const unsigned dstb = lds_wave + (unsigned)(bi * BUF_F * 4);
-        constexpr int TAIL = K::NF - 64 * (NL - 1);  // active lanes of the last instruction
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            if (k < NL - 1 || TAIL == 64) {
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dstb + 1024u * k), "v"(goff[k]), "s"(src) : "memory", "m0");
-            } else {
-                unsigned long long saved;
-                asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %0"
-                             : "=&s"(saved) : "s"(dstb + 1024u * k), "v"(goff[k]), "s"(src), "n"((1ull << (TAIL & 63)) - 1) : "memory", "m0");
-            }
-        }
-    };
-    // after the DMA of row r has landed in buffer bi: zero what lies outside the image (zfix: this lane's float offset in
-    // the row image of the border-column float4 it clears, -1 for the lanes that clear nothing)
+    const unsigned lds_wave = lds_addr(wbase);
+    // zfix: this lane's float offset in the row image of the border-column float4 it clears, -1 for the lanes that clear nothing
     const int zfix = lane < CQ ? (zl >= 0 ? zl * C + 4 * lane : -1) : (lane < 2 * CQ ? (zr >= 0 ? zr * C + 4 * (lane - CQ) : -1) : -1);
+    auto issue_row = [&](int r, int bi) { strip_issue_row<CQ>(in, a.H, a.W, lds_wave, goff, r, bi); };
     auto fix_row = [&](int r, int bi) {
         float* buf = wbase + bi * BUF_F;
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -906,23 +951,9 @@ __global__ __launch_bounds__(256, CQ <= 6 ? 3 : 2) void strip_kernel(StripArgs a
     // epilogue of output row y: activation, then transposed through the (now dead) row buffer bi so that every store
     // instruction writes 1 KiB of consecutive bytes
     auto epilogue = [&](int y, int bi) {
-        float* obuf = wbase + bi * BUF_F;
         float4 o[CQ];
         strip_act<CQ, RELU>(oacc, cst + K::OFF_SLOPE, a.hi, o);
-#pragma unroll
-        for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-        wave_sync();
-        float* dst = out + (long)y * a.W * C + gout;
-        if (full) {  // wave-uniform
-#pragma unroll
-            for (int k = 0; k < CQ; k++) sst4(dst + 256 * k, sld4(obuf + 4 * lane + 256 * k));
-        } else {
-#pragma unroll
-            for (int k = 0; k < CQ; k++) {
-                const float4 o = sld4(obuf + 4 * lane + 256 * k);
-                if (lane + 64 * k < npx * CQ) sst4(dst + 256 * k, o);
-            }
-        }
+        strip_store_row<CQ, false>(wbase + bi * BUF_F, out, a.W, lane, gout, full, npx, y, o);
     };
 
     // two partial-row sets and two centre rows alternate roles from one row to the next (the loop is unrolled by two)
@@ -1009,6 +1040,104 @@ struct PipeArgs {
 #endif
 };
 
+// The frame, part 2: the pieces of a pipeline wave.  PXS is the pixel stride of a hand-over row image (floats): C in the packed-FMA
+// forms, C + 4 in the MFMA forms; a row image is 132 pixels, a ring two of them.
+template <int RING_F, int NT>  // clear the hand-over rings once: their border pixel columns (left of x = 0, right of x = W-1) are never written
+__device__ __forceinline__ void clear_rings(float* lds) {
+    for (int i = threadIdx.x; i < RING_F / 4; i += NT) reinterpret_cast<float4*>(lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// hand the finished row e to the next block, into row image `image` (ring * 2 + slot) of the rings; rows outside the image are that
+// block's zero padding
+template <int CQ, int PXS>
+__device__ __forceinline__ void strip_hand_row(float* lds, int image, int img_p, int lane, int H, bool full, int npx, int e, const float4 (&o)[CQ]) {
+    float* dstl = lds + image * (132 * PXS) + img_p + (1 + lane) * PXS;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (e < 0 || e >= H) {  // wave-uniform
+#pragma unroll
+        for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, z);
+    } else if (full) {
+#pragma unroll
+        for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, o[q]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, lane >= npx ? z : o[q]);
+    }
+}
+// workgroup barrier between steps: raw s_barrier with an LDS-only wait, so that the stores of the last block and the DMA of block 0
+// stay in flight across it
+// (MI_ABL_NOBAR, a timing ablation of the two-row forms, now also drops strip_pipe_kernel's barrier, which had no such switch of its own)
+__device__ __forceinline__ void wg_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+#ifndef MI_ABL_NOBAR
+    __builtin_amdgcn_s_barrier();
+#endif
+    asm volatile("" ::: "memory");
+}
+// stride-2 tail: one wave serves both strips (W > 64: lane = output column) or both units (W <= 64: 32 lanes each); this lane's first
+// tap column in the full-width row image `img`
+template <int PXS>
+__device__ __forceinline__ const float* strip_tail_in(const float* img, int strips, int lane) {
+    const int tu = strips == 2 ? 0 : lane >> 5, tox = strips == 2 ? lane : lane & 31;
+    return img + tu * 66 * PXS + (2 * tox + 1) * PXS;
+}
+// stride-2 tail: the output row that band-relative even input row ke finishes — activation, transposition through obuf (coalesced
+// read-back: float4 f = lane + 64 j of the [64 pixels][C] image -> pixel f / CQ (unit, column)), store to the one or two units
+template <int CQ, int NH2, int S, bool RELU, class ACC>
+__device__ __forceinline__ void strip_tail_store(const PipeArgs& a, float* obuf, int lane, int hf, const ACC& oacc, int ke) {
+    using K2 = SK2<CQ, NH2>;
+    constexpr int C = 4 * CQ;
+    float4 o[CQ];
+    strip_act<CQ, RELU>(oacc, (const cfloat*)a.consts[S] + K2::OFF_SLOPE + hf * C, a.hi[S], o);
+#pragma unroll
+    for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
+    wave_sync();
+    const int Wo = a.W >> 1;
+#pragma unroll
+    for (int j = 0; j < CQ; j++) {
+        const int f = lane + 64 * j, px = f / CQ, qd = f - px * CQ;
+        const int u = a.strips == 2 ? 0 : px >> 5, ox = a.strips == 2 ? px : px & 31;
+        const int un = a.strips == 2 ? (int)blockIdx.x : 2 * (int)blockIdx.x + u;
+        const int ub = un % a.bands, bb = min(un / a.bands, a.B - 1);
+        const int uy0 = ub * a.band_rows, uy1 = min(uy0 + a.band_rows, a.H);
+        const float4 v = sld4(obuf + 4 * f);
+        if (un < a.units && uy0 + ke <= uy1 && ox < Wo) {
+            const int oy = (uy0 + ke - 2) >> 1;
+            sst4(a.out + (long)bb * a.out_fs + ((long)oy * Wo + ox) * K2::Co + hf * C + 4 * qd, v);
+        }
+    }
+    wave_sync();
+}
+// The MFMA forms' per-step constants: bias and first-stage taps of the coming step are scalar loads issued before a barrier and complete
+// when it opens (a stride-2 tail wave reads the same offsets of its own, larger blob and ignores them) ...
+template <int CQ>
+__device__ __forceinline__ void prefetch_consts(const cfloat* cst, float (&cb)[4 * CQ], float (&wd)[2][18]) {
+    const cfloat* pc = cst;
+    asm volatile("" : "+s"(pc));
+#pragma unroll
+    for (int i = 0; i < 4 * CQ; i++) cb[i] = pc[SK<CQ>::OFF_BIAS + i];
+#pragma unroll
+    for (int i = 0; i < 18; i++) wd[0][i] = pc[SK<CQ>::OFF_DW + i];
+}
+// ... pinned behind the barrier's lgkmcnt(0), which keeps the loads above in front of it ...
+template <int CQ>
+__device__ __forceinline__ void pin_consts(float (&cb)[4 * CQ], float (&wd)[2][18]) {
+#pragma unroll
+    for (int i = 0; i < 4 * CQ; i++) asm volatile("" : "+s"(cb[i]));
+#pragma unroll
+    for (int i = 0; i < 18; i++) asm volatile("" : "+s"(wd[0][i]));
+}
+// ... and the barrier that carries them (always a barrier: MI_ABL_NOBAR never covered it)
+template <int CQ>
+__device__ __forceinline__ void wg_barrier_consts(const cfloat* cst, float (&cb)[4 * CQ], float (&wd)[2][18]) {
+    prefetch_consts<CQ>(cst, cb, wd);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    pin_consts<CQ>(cb, wd);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
 // NH2 > 0: the chain ends in a stride-2 block (see strip_row_s2) run by NH2 extra waves (one per C output channels); KB
 // counts that block too.
 template <int CQ, int KB, bool RELU, int NH2>
@@ -1043,37 +1172,18 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
     const int lo_j = y0 - (S - 1 - role), hi_j = hi_last + (S - 1 - role);  // this (stride-1) block produces rows [lo_j, hi_j)
     const int img_p = a.strips == 2 ? 64 * C * p : 66 * C * p;           // this wave's window / sub-image inside a row image
 
-    // clear the hand-over rings once: their border pixel columns (left of x = 0, right of x = W-1) are never written
-    for (int i = threadIdx.x; i < RING_F / 4; i += NT) reinterpret_cast<float4*>(lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    clear_rings<RING_F, NT>(lds);
 
-    int goff[NL];  // block 0: byte offset of the lane's float4 from the row start, per DMA instruction (see strip_kernel)
-#pragma unroll
-    for (int k = 0; k < NL; k++) {
-        const int f = min(lane + 64 * k, K::NF - 1), px = f / CQ, qd = f - px * CQ;
-        goff[k] = (min(max(x0 - 1 + px, 0), a.W - 1) * C + 4 * qd) * 4;
-    }
+    int goff[NL];
+    strip_goff<CQ>(lane, x0, a.W, goff);
     const int npx = min(64, a.W - x0);
     const bool full = npx == 64;
     const int zl = x0 == 0 ? 0 : -1;
     const int zr = x0 + 64 >= a.W ? npx + 1 : -1;
     const long gout = (long)x0 * C + 4 * lane;
-    const unsigned lds_scratch = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)scratch);
-    auto issue_row = [&](int r, int bi) {
-        const char* src = reinterpret_cast<const char*>(in + (long)min(max(r, 0), a.H - 1) * a.W * C);
-        const unsigned dstb = lds_scratch + (unsigned)(bi * BUF_F * 4);
-        constexpr int TAIL = K::NF - 64 * (NL - 1);
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            if (k < NL - 1 || TAIL == 64) {
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dstb + 1024u * k), "v"(goff[k]), "s"(src) : "memory", "m0");
-            } else {
-                unsigned long long saved;
-                asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %0"
-                             : "=&s"(saved) : "s"(dstb + 1024u * k), "v"(goff[k]), "s"(src), "n"((1ull << (TAIL & 63)) - 1) : "memory", "m0");
-            }
-        }
-    };
+    const unsigned lds_scratch = lds_addr(scratch);
     const int zfix = lane < CQ ? (zl >= 0 ? zl * C + 4 * lane : -1) : (lane < 2 * CQ ? (zr >= 0 ? zr * C + 4 * (lane - CQ) : -1) : -1);
+    auto issue_row = [&](int r, int bi) { strip_issue_row<CQ>(in, a.H, a.W, lds_scratch, goff, r, bi); };
     auto fix_row = [&](int r, int bi) {
         float* buf = scratch + bi * BUF_F;
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1101,23 +1211,15 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_s_barrier();
 
-    auto wg_barrier = [&]() {
-        // raw s_barrier with an LDS-only wait, so that the stores of block KB-1 and the DMA of block 0 stay in flight across it
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
     // ---- stride-2 tail: one wave serves both strips (W > 64: lane = output column) or both units (W <= 64: 32 lanes each).
     // Its state (partial depthwise row, running max-pool) lives in the registers the stride-1 waves use for acc0 / xa.
     auto tail_step = [&](int t, v2f (&tacc)[CQ][2], float4 (&tmx)[CQ]) {
         if constexpr (NH2 > 0) {
             const int k = t - 3 * S;  // band-relative index of the row the last stride-1 block handed over in step t-1
             if (k < 0 || k > a.band_rows) return;
-            constexpr int Co = NH2 * C;
-            constexpr int ST2 = (32 + 2 * Co + 15) / 16 * 16, OFF_SLOPE2 = (C / 2) * ST2 + 64;
             const cfloat* cst2 = (const cfloat*)a.consts[S];
             const float* img = lds + ((S - 1) * SLOTS + ((t - 1) & 1)) * IMG;
+            // (strip_tail_in, inline in this kernel: through the function <6,3,true,2> lost one compiler-inserted s_waitcnt)
             const int tu = a.strips == 2 ? 0 : lane >> 5, tox = a.strips == 2 ? lane : lane & 31;
             const float* me2 = img + tu * 66 * C + (2 * tox + 1) * C;
             const bool skip = hf == 0 && a.has_res[S] != 0;
@@ -1127,28 +1229,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
                 strip_row_s2<CQ, NH2, 1>(me2, cst2, hf, skip, tacc, tmx, oacc);
             } else {
                 strip_row_s2<CQ, NH2, 2>(me2, cst2, hf, skip, tacc, tmx, oacc);
-                float4 o[CQ];
-                strip_act<CQ, RELU>(oacc, cst2 + OFF_SLOPE2 + hf * C, a.hi[S], o);
-                float* obuf = scratch;
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-                wave_sync();
-                // coalesced read-back: float4 f = lane + 64 j of the [64 pixels][C] image -> pixel f / CQ (unit, column)
-                const int Wo = a.W >> 1;
-#pragma unroll
-                for (int j = 0; j < CQ; j++) {
-                    const int f = lane + 64 * j, px = f / CQ, qd = f - px * CQ;
-                    const int u = a.strips == 2 ? 0 : px >> 5, ox = a.strips == 2 ? px : px & 31;
-                    const int un = a.strips == 2 ? (int)blockIdx.x : 2 * (int)blockIdx.x + u;
-                    const int ub = un % a.bands, bb = min(un / a.bands, a.B - 1);
-                    const int uy0 = ub * a.band_rows, uy1 = min(uy0 + a.band_rows, a.H);
-                    const float4 v = sld4(obuf + 4 * f);
-                    if (un < a.units && uy0 + k <= uy1 && ox < Wo) {
-                        const int oy = (uy0 + k - 2) >> 1;
-                        sst4(a.out + (long)bb * a.out_fs + ((long)oy * Wo + ox) * Co + hf * C + 4 * qd, v);
-                    }
-                }
-                wave_sync();
+                strip_tail_store<CQ, NH2, S, RELU>(a, scratch, lane, hf, oacc, k);
             }
         }
     };
@@ -1175,21 +1256,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
                 if (NH2 || role < S - 1) {
                     hand_over = true;
                 } else {
-                    float* obuf = scratch;
-#pragma unroll
-                    for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-                    wave_sync();
-                    float* dst = out + (long)e * a.W * C + gout;
-                    if (full) {
-#pragma unroll
-                        for (int k = 0; k < CQ; k++) sst4(dst + 256 * k, sld4(obuf + 4 * lane + 256 * k));
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < CQ; k++) {
-                            const float4 v = sld4(obuf + 4 * lane + 256 * k);
-                            if (lane + 64 * k < npx * CQ) sst4(dst + 256 * k, v);
-                        }
-                    }
+                    strip_store_row<CQ, false>(scratch, out, a.W, lane, gout, full, npx, e, o);
                 }
             }
             if (role == 0 && c + 2 <= hi_j) {
@@ -1200,21 +1267,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         if constexpr (NH2 > 0) {
             if (tail) tail_step(t, tacc, tmx);
         }
-        if (hand_over) {
-            // hand the row to the next block; rows outside the image are that block's zero padding
-            float* dstl = lds + (role * SLOTS + (t & 1)) * IMG + img_p + (1 + lane) * C;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < 0 || e >= a.H) {  // wave-uniform
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, z);
-            } else if (full) {
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, o[q]);
-            } else {
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, lane >= npx ? z : o[q]);
-            }
-        }
+        if (hand_over) strip_hand_row<CQ, C>(lds, role * SLOTS + (t & 1), img_p, lane, a.H, full, npx, e, o);
         wg_barrier();
     };
     const int T = NH2 ? a.band_rows + 3 * S + 1 : a.band_rows + 3 * S - 1;
@@ -1265,37 +1318,18 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         if ((a.prio == 1 && (first || last)) || (a.prio == 2 && first) || (a.prio == 3 && last)) __builtin_amdgcn_s_setprio(1);
     }
 
-    // clear the hand-over rings once: their border pixel columns (left of x = 0, right of x = W-1) are never written
-    for (int i = threadIdx.x; i < RING_F / 4; i += NT) reinterpret_cast<float4*>(lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    clear_rings<RING_F, NT>(lds);
 
-    int goff[NL];  // block 0: byte offset of the lane's float4 from the row start, per DMA instruction (see strip_kernel)
-#pragma unroll
-    for (int k = 0; k < NL; k++) {
-        const int f = min(lane + 64 * k, K::NF - 1), px = f / CQ, qd = f - px * CQ;
-        goff[k] = (min(max(x0 - 1 + px, 0), a.W - 1) * C + 4 * qd) * 4;
-    }
+    int goff[NL];
+    strip_goff<CQ>(lane, x0, a.W, goff);
     const int npx = min(64, a.W - x0);
     const bool full = npx == 64;
     const int zl = x0 == 0 ? 0 : -1;
     const int zr = x0 + 64 >= a.W ? npx + 1 : -1;
     const long gout = (long)x0 * C + 4 * lane;
-    const unsigned lds_scratch = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)scratch);
-    auto issue_row = [&](int r, int bi) {
-        const char* src = reinterpret_cast<const char*>(in + (long)min(max(r, 0), a.H - 1) * a.W * C);
-        const unsigned dstb = lds_scratch + (unsigned)(bi * BUF_F * 4);
-        constexpr int TAIL = K::NF - 64 * (NL - 1);
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            if (k < NL - 1 || TAIL == 64) {
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dstb + 1024u * k), "v"(goff[k]), "s"(src) : "memory", "m0");
-            } else {
-                unsigned long long saved;
-                asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %0"
-                             : "=&s"(saved) : "s"(dstb + 1024u * k), "v"(goff[k]), "s"(src), "n"((1ull << (TAIL & 63)) - 1) : "memory", "m0");
-            }
-        }
-    };
+    const unsigned lds_scratch = lds_addr(scratch);
     const int zfix = lane < CQ ? (zl >= 0 ? zl * C + 4 * lane : -1) : (lane < 2 * CQ ? (zr >= 0 ? zr * C + 4 * (lane - CQ) : -1) : -1);
+    auto issue_row = [&](int r, int bi) { strip_issue_row<CQ>(in, a.H, a.W, lds_scratch, goff, r, bi); };
     auto fix_row = [&](int r, int bi) {
         float* buf = scratch + bi * BUF_F;
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1318,64 +1352,38 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         acc0[q][0] = acc0[q][1] = acc1[q][0] = acc1[q][1] = v2f{0.f, 0.f};
         onext[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    auto prefetch_consts = [&]() {  // bias + first-stage taps of the coming step, asked for before the barrier
-        const cfloat* pc = cst;
-        asm volatile("" : "+s"(pc));
-#pragma unroll
-        for (int i = 0; i < C; i++) cb[i] = pc[K::OFF_BIAS + i];
-#pragma unroll
-        for (int i = 0; i < 18; i++) wd[0][i] = pc[K::OFF_DW + i];
-    };
-    auto pin_consts = [&]() {
-#pragma unroll
-        for (int i = 0; i < C; i++) asm volatile("" : "+s"(cb[i]));
-#pragma unroll
-        for (int i = 0; i < 18; i++) asm volatile("" : "+s"(wd[0][i]));
-    };
     if (!tail) {
 #pragma unroll
         for (int i = 0; i < K::NA; i++) wa[i] = a.consts[role][K::OFF_A + 64 * i + lane];
     } else if constexpr (NH2 > 0) {
-        constexpr int ST2h = (32 + 2 * NH2 * C + 15) / 16 * 16, OFF_A2 = (C / 2) * ST2h + 128;
+        constexpr int OFF_A2 = SK2<CQ, NH2>::OFF_A;
 #pragma unroll
         for (int i = 0; i < K::NA; i++) wa[i] = a.consts[S][OFF_A2 + (hf * K::NA + i) * 64 + lane];
     }
-    prefetch_consts();
+    prefetch_consts<CQ>(cst, cb, wd);
     const int c_first = y0 - S - 2 * role;  // row this block would consume at step 0 (it starts at step 3 * role)
     if (role == 0 && active) {
         issue_row(c_first, 0);
         issue_row(c_first + 1, 1);
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
-    pin_consts();
+    pin_consts<CQ>(cb, wd);
     __builtin_amdgcn_s_barrier();
     if (!tail && !has_res) {
 #pragma unroll
         for (int q = 0; q < CQ; q++) onext[q] = make_float4(cb[4 * q], cb[4 * q + 1], cb[4 * q + 2], cb[4 * q + 3]);
     }
 
-    auto wg_barrier = [&]() {
-        // raw s_barrier with an LDS-only wait (and the scalar loads of the next step's constants), so that the stores of block KB-1 and the
-        // DMA of block 0 stay in flight across it
-        prefetch_consts();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        pin_consts();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
+    auto wg_barrier = [&]() { wg_barrier_consts<CQ>(cst, cb, wd); };  // carries the next step's constants
     // ---- stride-2 tail: one wave serves both strips (W > 64: lane = output column) or both units (W <= 64: 32 lanes each).
     // Its state (partial depthwise row, running max-pool) lives in the registers the stride-1 waves use for acc0 / xa.
     auto tail_step = [&](int t, v2f (&tacc)[CQ][2], float4 (&tmx)[CQ]) {
         if constexpr (NH2 > 0) {
             const int k = t - 3 * S;  // band-relative index of the row the last stride-1 block handed over in step t-1
             if (k < 0 || k > a.band_rows) return;
-            constexpr int Co = NH2 * C;
-            constexpr int ST2 = (32 + 2 * Co + 15) / 16 * 16, OFF_SLOPE2 = (C / 2) * ST2 + 64;
             const cfloat* cst2 = (const cfloat*)a.consts[S];
             const float* img = lds + ((S - 1) * SLOTS + ((t - 1) & 1)) * IMG;
-            const int tu = a.strips == 2 ? 0 : lane >> 5, tox = a.strips == 2 ? lane : lane & 31;
-            const float* me2 = img + tu * 66 * PXS + (2 * tox + 1) * PXS;
+            const float* me2 = strip_tail_in<PXS>(img, a.strips, lane);
             const bool skip = hf == 0 && a.has_res[S] != 0;
             if (k & 1) {
                 strip_row_s2m<CQ, NH2, 0, PXS>(me2, cst2, hf, skip, tacc, tmx, toacc, wa);
@@ -1383,28 +1391,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
                 strip_row_s2m<CQ, NH2, 1, PXS>(me2, cst2, hf, skip, tacc, tmx, toacc, wa);
             } else {
                 strip_row_s2m<CQ, NH2, 2, PXS>(me2, cst2, hf, skip, tacc, tmx, toacc, wa);
-                float4 o[CQ];
-                strip_act<CQ, RELU>(toacc, cst2 + OFF_SLOPE2 + hf * C, a.hi[S], o);
-                float* obuf = scratch;
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-                wave_sync();
-                // coalesced read-back: float4 f = lane + 64 j of the [64 pixels][C] image -> pixel f / CQ (unit, column)
-                const int Wo = a.W >> 1;
-#pragma unroll
-                for (int j = 0; j < CQ; j++) {
-                    const int f = lane + 64 * j, px = f / CQ, qd = f - px * CQ;
-                    const int u = a.strips == 2 ? 0 : px >> 5, ox = a.strips == 2 ? px : px & 31;
-                    const int un = a.strips == 2 ? (int)blockIdx.x : 2 * (int)blockIdx.x + u;
-                    const int ub = un % a.bands, bb = min(un / a.bands, a.B - 1);
-                    const int uy0 = ub * a.band_rows, uy1 = min(uy0 + a.band_rows, a.H);
-                    const float4 v = sld4(obuf + 4 * f);
-                    if (un < a.units && uy0 + k <= uy1 && ox < Wo) {
-                        const int oy = (uy0 + k - 2) >> 1;
-                        sst4(a.out + (long)bb * a.out_fs + ((long)oy * Wo + ox) * Co + hf * C + 4 * qd, v);
-                    }
-                }
-                wave_sync();
+                strip_tail_store<CQ, NH2, S, RELU>(a, scratch, lane, hf, toacc, k);
             }
         }
     };
@@ -1436,21 +1423,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
                 if (NH2 || role < S - 1) {
                     hand_over = true;
                 } else {
-                    float* obuf = scratch;
-#pragma unroll
-                    for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-                    wave_sync();
-                    float* dst = out + (long)e * a.W * C + gout;
-                    if (full) {
-#pragma unroll
-                        for (int k = 0; k < CQ; k++) sst4(dst + 256 * k, sld4(obuf + 4 * lane + 256 * k));
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < CQ; k++) {
-                            const float4 v = sld4(obuf + 4 * lane + 256 * k);
-                            if (lane + 64 * k < npx * CQ) sst4(dst + 256 * k, v);
-                        }
-                    }
+                    strip_store_row<CQ, false>(scratch, out, a.W, lane, gout, full, npx, e, o);
                 }
             }
             if (role == 0 && c + 2 <= hi_j) {
@@ -1461,21 +1434,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         if constexpr (NH2 > 0) {
             if (tail) tail_step(t, tacc, tmx);
         }
-        if (hand_over) {
-            // hand the row to the next block; rows outside the image are that block's zero padding
-            float* dstl = lds + (role * SLOTS + (t & 1)) * IMG + img_p + (1 + lane) * PXS;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < 0 || e >= a.H) {  // wave-uniform
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, z);
-            } else if (full) {
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, o[q]);
-            } else {
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, lane >= npx ? z : o[q]);
-            }
-        }
+        if (hand_over) strip_hand_row<CQ, PXS>(lds, role * SLOTS + (t & 1), img_p, lane, a.H, full, npx, e, o);
         wg_barrier();
     };
     const int T = NH2 ? a.band_rows + 3 * S + 1 : a.band_rows + 3 * S - 1;
@@ -1527,36 +1486,18 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
     const int P = (hi_j - lo_j + 2) >> 1;                                   // row pairs it consumes: (lo_j - 1 + 2m, lo_j + 2m)
     const int img_p = a.strips == 2 ? 64 * C * p : 66 * C * p;
 
-    for (int i = threadIdx.x; i < RING_F / 4; i += NT) reinterpret_cast<float4*>(lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    clear_rings<RING_F, NT>(lds);
 
     int goff[NL];
-#pragma unroll
-    for (int k = 0; k < NL; k++) {
-        const int f = min(lane + 64 * k, K::NF - 1), px = f / CQ, qd = f - px * CQ;
-        goff[k] = (min(max(x0 - 1 + px, 0), a.W - 1) * C + 4 * qd) * 4;
-    }
+    strip_goff<CQ>(lane, x0, a.W, goff);
     const int npx = min(64, a.W - x0);
     const bool full = npx == 64;
     const int zl = x0 == 0 ? 0 : -1;
     const int zr = x0 + 64 >= a.W ? npx + 1 : -1;
     const long gout = (long)x0 * C + 4 * lane;
-    const unsigned lds_scratch = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)scratch);
-    auto issue_row = [&](int r, int bi) {
-        const char* src = reinterpret_cast<const char*>(in + (long)min(max(r, 0), a.H - 1) * a.W * C);
-        const unsigned dstb = lds_scratch + (unsigned)(bi * BUF_F * 4);
-        constexpr int TAIL = K::NF - 64 * (NL - 1);
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            if (k < NL - 1 || TAIL == 64) {
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dstb + 1024u * k), "v"(goff[k]), "s"(src) : "memory", "m0");
-            } else {
-                unsigned long long saved;
-                asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %0"
-                             : "=&s"(saved) : "s"(dstb + 1024u * k), "v"(goff[k]), "s"(src), "n"((1ull << (TAIL & 63)) - 1) : "memory", "m0");
-            }
-        }
-    };
+    const unsigned lds_scratch = lds_addr(scratch);
     const int zfix = lane < CQ ? (zl >= 0 ? zl * C + 4 * lane : -1) : (lane < 2 * CQ ? (zr >= 0 ? zr * C + 4 * (lane - CQ) : -1) : -1);
+    auto issue_row = [&](int r, int bi) { strip_issue_row<CQ>(in, a.H, a.W, lds_scratch, goff, r, bi); };
     auto fix_row = [&](int r, int bi) {
         float* buf = scratch + bi * BUF_F;
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1593,33 +1534,9 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
 #else
 #define MI_PSTAMP(k)
 #endif
-    auto wg_barrier = [&]() {
-        // raw s_barrier with an LDS-only wait, so that the stores of the last block and the DMA of block 0 stay in flight across it
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-#ifndef MI_ABL_NOBAR
-        __builtin_amdgcn_s_barrier();
-#endif
-        asm volatile("" ::: "memory");
-    };
-    auto store_row = [&](int e, const float4 (&o)[CQ]) {  // transposed through LDS: 1 KiB of consecutive bytes per store instruction
-        float* obuf = scratch;
-#pragma unroll
-        for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-        wave_sync();
-        float* dst = out + (long)e * a.W * C + gout;
-        if (full) {
-#pragma unroll
-            for (int k = 0; k < CQ; k++) sst4(dst + 256 * k, sld4(obuf + 4 * lane + 256 * k));
-        } else {
-#pragma unroll
-            for (int k = 0; k < CQ; k++) {
-                const float4 v = sld4(obuf + 4 * lane + 256 * k);
-                if (lane + 64 * k < npx * CQ) sst4(dst + 256 * k, v);
-            }
-        }
-        wave_sync();
-    };
+    auto store_row = [&](int e, const float4 (&o)[CQ]) { strip_store_row<CQ, true>(scratch, out, a.W, lane, gout, full, npx, e, o); };
+    // (strip_hand_row, inline in the two-row forms: through the function hipcc puts the outside-picture arm first and the full-strip arm last, and
+    // bench.py loses 1.2 % on strip_pipe2m_kernel with nothing else in its instruction stream changed; profiles/strip_frame_bench.txt)
     auto hand_row = [&](int e, int which, const float4 (&o)[CQ]) {  // rows outside the image are the next block's zero padding
         float* dstl = lds + (role * 2 + which) * IMG + img_p + (1 + lane) * C;
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1640,38 +1557,15 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
             const int mt = t - 2 * S;
             if (mt < 0 || 2 * mt > a.band_rows) return;
             const int k = 2 * mt;  // band-relative index of the even row
-            constexpr int Co = NH2 * C;
-            constexpr int ST2 = (32 + 2 * Co + 15) / 16 * 16, OFF_SLOPE2 = (C / 2) * ST2 + 64;
             const cfloat* cst2 = (const cfloat*)a.consts[S];
             const float* img = lds + ((S - 1) * 2) * IMG;
-            const int tu = a.strips == 2 ? 0 : lane >> 5, tox = a.strips == 2 ? lane : lane & 31;
-            const float* me2 = img + tu * 66 * C + (2 * tox + 1) * C;
+            const float* me2 = strip_tail_in<C>(img, a.strips, lane);
             const bool skip = hf == 0 && a.has_res[S] != 0;
             if (mt == 0) {
                 strip_row_s2<CQ, NH2, 1>(me2, cst2, hf, skip, tacc, tmx, oacc0);
             } else {
                 strip_row_s2<CQ, NH2, 2>(me2, cst2, hf, skip, tacc, tmx, oacc0);
-                float4 o[CQ];
-                strip_act<CQ, RELU>(oacc0, cst2 + OFF_SLOPE2 + hf * C, a.hi[S], o);
-                float* obuf = scratch;
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-                wave_sync();
-                const int Wo = a.W >> 1;
-#pragma unroll
-                for (int j = 0; j < CQ; j++) {
-                    const int f = lane + 64 * j, px = f / CQ, qd = f - px * CQ;
-                    const int u = a.strips == 2 ? 0 : px >> 5, ox = a.strips == 2 ? px : px & 31;
-                    const int un = a.strips == 2 ? (int)blockIdx.x : 2 * (int)blockIdx.x + u;
-                    const int ub = un % a.bands, bb = min(un / a.bands, a.B - 1);
-                    const int uy0 = ub * a.band_rows, uy1 = min(uy0 + a.band_rows, a.H);
-                    const float4 v = sld4(obuf + 4 * f);
-                    if (un < a.units && uy0 + k <= uy1 && ox < Wo) {
-                        const int oy = (uy0 + k - 2) >> 1;
-                        sst4(a.out + (long)bb * a.out_fs + ((long)oy * Wo + ox) * Co + hf * C + 4 * qd, v);
-                    }
-                }
-                wave_sync();
+                strip_tail_store<CQ, NH2, S, RELU>(a, scratch, lane, hf, oacc0, k);
             }
             if (k + 1 < a.band_rows) strip_row_s2<CQ, NH2, 0>(me2 + IMG, cst2, hf, skip, tacc, tmx, oacc0);
         }
@@ -1805,36 +1699,18 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
     const int kskip = whole && !tail ? (S - role) >> 1 : 0;                 // pairs this block skips
     const int img_p = a.strips == 2 ? 64 * PXS * p : 66 * PXS * p;
 
-    for (int i = threadIdx.x; i < RING_F / 4; i += NT) reinterpret_cast<float4*>(lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    clear_rings<RING_F, NT>(lds);
 
     int goff[NL];
-#pragma unroll
-    for (int k = 0; k < NL; k++) {
-        const int f = min(lane + 64 * k, K::NF - 1), px = f / CQ, qd = f - px * CQ;
-        goff[k] = (min(max(x0 - 1 + px, 0), a.W - 1) * C + 4 * qd) * 4;
-    }
+    strip_goff<CQ>(lane, x0, a.W, goff);
     const int npx = min(64, a.W - x0);
     const bool full = npx == 64;
     const int zl = x0 == 0 ? 0 : -1;
     const int zr = x0 + 64 >= a.W ? npx + 1 : -1;
     const long gout = (long)x0 * C + 4 * lane;
-    const unsigned lds_scratch = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)scratch);
-    auto issue_row = [&](int r, int bi) {
-        const char* src = reinterpret_cast<const char*>(in + (long)min(max(r, 0), a.H - 1) * a.W * C);
-        const unsigned dstb = lds_scratch + (unsigned)(bi * BUF_F * 4);
-        constexpr int TAIL = K::NF - 64 * (NL - 1);
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            if (k < NL - 1 || TAIL == 64) {
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dstb + 1024u * k), "v"(goff[k]), "s"(src) : "memory", "m0");
-            } else {
-                unsigned long long saved;
-                asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %0"
-                             : "=&s"(saved) : "s"(dstb + 1024u * k), "v"(goff[k]), "s"(src), "n"((1ull << (TAIL & 63)) - 1) : "memory", "m0");
-            }
-        }
-    };
+    const unsigned lds_scratch = lds_addr(scratch);
     const int zfix = lane < CQ ? (zl >= 0 ? zl * C + 4 * lane : -1) : (lane < 2 * CQ ? (zr >= 0 ? zr * C + 4 * (lane - CQ) : -1) : -1);
+    auto issue_row = [&](int r, int bi) { strip_issue_row<CQ>(in, a.H, a.W, lds_scratch, goff, r, bi); };
     auto fix_row = [&](int r, int bi) {
         float* buf = scratch + bi * BUF_F;
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1858,30 +1734,15 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         aA[q][0] = aA[q][1] = aB[q][0] = aB[q][1] = v2f{0.f, 0.f};
         onext[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    // bias and first-stage taps of the coming step: scalar loads issued before a barrier, complete when it opens
-    auto prefetch_consts = [&]() {  // (a stride-2 tail wave reads the same offsets of its own, larger blob and ignores them)
-        const cfloat* pc = cst;
-        asm volatile("" : "+s"(pc));
-#pragma unroll
-        for (int i = 0; i < C; i++) cb[i] = pc[K::OFF_BIAS + i];
-#pragma unroll
-        for (int i = 0; i < 18; i++) wd[0][i] = pc[K::OFF_DW + i];
-    };
-    auto pin_consts = [&]() {  // behind the barrier's lgkmcnt(0): keeps the loads above in front of it
-#pragma unroll
-        for (int i = 0; i < C; i++) asm volatile("" : "+s"(cb[i]));
-#pragma unroll
-        for (int i = 0; i < 18; i++) asm volatile("" : "+s"(wd[0][i]));
-    };
     if (!tail) {
 #pragma unroll
         for (int i = 0; i < K::NA; i++) wa[i] = a.consts[role][K::OFF_A + 64 * i + lane];
     } else if constexpr (NH2 > 0) {  // this tail wave's C x C slice of the stride-2 block's filter (strip_pack_consts_s2)
-        constexpr int ST2h = (32 + 2 * NH2 * C + 15) / 16 * 16, OFF_A2 = (C / 2) * ST2h + 128;
+        constexpr int OFF_A2 = SK2<CQ, NH2>::OFF_A;
 #pragma unroll
         for (int i = 0; i < K::NA; i++) wa[i] = a.consts[S][OFF_A2 + (hf * K::NA + i) * 64 + lane];
     }
-    prefetch_consts();
+    prefetch_consts<CQ>(cst, cb, wd);
     if (role == 0 && active) {  // the first two pairs block 0 executes (pairs D, D + 1: it runs pair t + D in step t, on buffer pair t & 1)
         const int r0 = lo_j - 1 + 2 * D;
         issue_row(r0, 0);
@@ -1892,7 +1753,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         }
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
-    pin_consts();
+    pin_consts<CQ>(cb, wd);
     __builtin_amdgcn_s_barrier();
     if (!tail && !has_res) {  // no skip: the first finished row of every step starts from the bias alone
 #pragma unroll
@@ -1905,33 +1766,9 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
 #else
 #define MI_PSTAMP(k)
 #endif
-    auto wg_barrier = [&]() {
-        // raw s_barrier with an LDS-only wait, so that the stores of the last block and the DMA of block 0 stay in flight across it
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-#ifndef MI_ABL_NOBAR
-        __builtin_amdgcn_s_barrier();
-#endif
-        asm volatile("" ::: "memory");
-    };
-    auto store_row = [&](int e, const float4 (&o)[CQ]) {  // transposed through LDS: 1 KiB of consecutive bytes per store instruction
-        float* obuf = scratch;
-#pragma unroll
-        for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-        wave_sync();
-        float* dst = out + (long)e * a.W * C + gout;
-        if (full) {
-#pragma unroll
-            for (int k = 0; k < CQ; k++) sst4(dst + 256 * k, sld4(obuf + 4 * lane + 256 * k));
-        } else {
-#pragma unroll
-            for (int k = 0; k < CQ; k++) {
-                const float4 v = sld4(obuf + 4 * lane + 256 * k);
-                if (lane + 64 * k < npx * CQ) sst4(dst + 256 * k, v);
-            }
-        }
-        wave_sync();
-    };
+    auto store_row = [&](int e, const float4 (&o)[CQ]) { strip_store_row<CQ, true>(scratch, out, a.W, lane, gout, full, npx, e, o); };
+    // (strip_hand_row, inline in the two-row forms: through the function hipcc puts the outside-picture arm first and the full-strip arm last, and
+    // bench.py loses 1.2 % on strip_pipe2m_kernel with nothing else in its instruction stream changed; profiles/strip_frame_bench.txt)
     auto hand_row = [&](int e, int which, const float4 (&o)[CQ]) {  // rows outside the image are the next block's zero padding
         float* dstl = lds + (role * 2 + which) * IMG + img_p + (1 + lane) * PXS;
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1952,36 +1789,11 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
             const int mt = t + D - 2 * S;
             if (mt < 0 || 2 * mt > a.band_rows) return;
             const int k = 2 * mt;  // band-relative index of the even row
-            constexpr int Co = NH2 * C;
-            constexpr int ST2 = (32 + 2 * Co + 15) / 16 * 16, OFF_SLOPE2 = (C / 2) * ST2 + 64;
             const cfloat* cst2 = (const cfloat*)a.consts[S];
             const float* img = lds + ((S - 1) * 2) * IMG;
-            const int tu = a.strips == 2 ? 0 : lane >> 5, tox = a.strips == 2 ? lane : lane & 31;
-            const float* me2 = img + tu * 66 * PXS + (2 * tox + 1) * PXS;
+            const float* me2 = strip_tail_in<PXS>(img, a.strips, lane);
             const bool skip = hf == 0 && a.has_res[S] != 0;
-            auto store_out = [&](int ke) {  // the output row that band-relative even row ke finishes: activation, transposition, store
-                float4 o[CQ];
-                strip_act<CQ, RELU>(toacc, cst2 + OFF_SLOPE2 + hf * C, a.hi[S], o);
-                float* obuf = scratch;
-#pragma unroll
-                for (int q = 0; q < CQ; q++) sst4(obuf + lane * C + 4 * q, o[q]);
-                wave_sync();
-                const int Wo = a.W >> 1;
-#pragma unroll
-                for (int j = 0; j < CQ; j++) {
-                    const int f = lane + 64 * j, px = f / CQ, qd = f - px * CQ;
-                    const int u = a.strips == 2 ? 0 : px >> 5, ox = a.strips == 2 ? px : px & 31;
-                    const int un = a.strips == 2 ? (int)blockIdx.x : 2 * (int)blockIdx.x + u;
-                    const int ub = un % a.bands, bb = min(un / a.bands, a.B - 1);
-                    const int uy0 = ub * a.band_rows, uy1 = min(uy0 + a.band_rows, a.H);
-                    const float4 v = sld4(obuf + 4 * f);
-                    if (un < a.units && uy0 + ke <= uy1 && ox < Wo) {
-                        const int oy = (uy0 + ke - 2) >> 1;
-                        sst4(a.out + (long)bb * a.out_fs + ((long)oy * Wo + ox) * Co + hf * C + 4 * qd, v);
-                    }
-                }
-                wave_sync();
-            };
+            auto store_out = [&](int ke) { strip_tail_store<CQ, NH2, S, RELU>(a, scratch, lane, hf, toacc, ke); };
             if (mt == 0) {
                 strip_row_s2m<CQ, NH2, 1, PXS>(me2, cst2, hf, skip, tacc, tmx, toacc, wa);
             } else {
@@ -2060,12 +1872,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         }
         MI_PSTAMP(2)
 #endif
-        prefetch_consts();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        pin_consts();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        wg_barrier_consts<CQ>(cst, cb, wd);  // carries the next step's constants
         MI_PSTAMP(3)
     };
     // interior bands: 2 S - 1 fill steps + band_rows / 2 (+ 2 with a tail: its own lag and its flush step); whole frames: D fewer, and no flush
@@ -2085,16 +1892,11 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
 template <int CQ, int KB, bool RELU, int NH2>
 int launch_pipe_inst(const PipeArgs& pa, hipStream_t s) {
     using K = SK<CQ>;
-    const bool two = pa.rows_per_step >= 2;
-    if (pa.rows_per_step == 4) {  // one row per step, MFMA pointwise convs
-        auto k1 = strip_pipe1m_kernel<CQ, KB, RELU, NH2>;
-        const size_t lds1 = (size_t)((KB - 1) * 2 * 132 * (K::C + 4) + 6 * K::BUF_F) * 4;
-        if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(k1)); e != hipSuccess) return (int)e;
-        const int wgs1 = pa.strips == 2 ? pa.units : (pa.units + 1) / 2;
-        return (int)launch_kernel(k1, dim3((unsigned)wgs1), dim3(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB), lds1, s, pa);
-    }
-    const bool mf = pa.rows_per_step == 3;
-    auto kern = mf ? strip_pipe2m_kernel<CQ, KB, RELU, NH2> : (two ? strip_pipe2_kernel<CQ, KB, RELU, NH2> : strip_pipe_kernel<CQ, KB, RELU, NH2>);
+    const int rps = pa.rows_per_step;  // 1 / 4: one row per step, 2 / 3: two; 3 / 4: MFMA pointwise convs (ring pixel stride C + 4)
+    const bool two = rps == 2 || rps == 3, mf = rps >= 3;
+    auto kern = rps == 4 ? strip_pipe1m_kernel<CQ, KB, RELU, NH2>
+              : (rps == 3 ? strip_pipe2m_kernel<CQ, KB, RELU, NH2> : (two ? strip_pipe2_kernel<CQ, KB, RELU, NH2> : strip_pipe_kernel<CQ, KB, RELU, NH2>));
+    // rings + per strip / unit the DMA row buffers of block 0 + one transposition buffer for the waves that store
     const size_t lds_bytes = (size_t)((KB - 1) * 2 * 132 * (mf ? K::C + 4 : K::C) + (two ? 10 : 6) * K::BUF_F) * 4;
     if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
     const int wgs = pa.strips == 2 ? pa.units : (pa.units + 1) / 2;
@@ -2158,23 +1960,37 @@ bool strip_kernel_supports(const BlockArgs& a) {
 
 bool strip_shape_ok(int C, int Co) { return C == Co && (C == 16 || C == 24 || C == 32); }
 
-static int strip_stage_floats(int C) { return 32 + 2 * C + (16 - (2 * C) % 16) % 16; }
-int strip_consts_floats(int C) { return C / 2 * strip_stage_floats(C) + 64 + 64 * ((C * (C / 4) + 15) / 16); }
+namespace {
 
-// w_dw [3][3][C], b_dw [C] or null, w_pw [Co][C] (TFLite OHWI with H = W = 1), bias [Co] or null, alpha [Co] or null.
-void strip_pack_consts(int C, const float* w_dw, const float* b_dw, const float* w_pw, const float* bias, const float* alpha, int act, float* dst) {
-    const int SF = strip_stage_floats(C);
-    std::fill(dst, dst + strip_consts_floats(C), 0.f);
+// SK<C / 4> (nh2 = 0: a stride-1 block) or SK2<C / 4, nh2> (a stride-2 tail to nh2 * C channels) for a run-time channel count; all zero for
+// a shape no kernel is instantiated for
+// (the size functions used to return the formula's value for any C; every caller asks strip_shape_ok / strip_tail_shape_ok first)
+struct StripBlob { int ST_F, OFF_BIAS, OFF_SLOPE, OFF_A, NA, TOTAL; };
+template <class L, class K>
+constexpr StripBlob strip_blob_of() { return {L::ST_F, L::OFF_BIAS, L::OFF_SLOPE, L::OFF_A, K::NA, L::TOTAL}; }
+StripBlob strip_blob(int C, int nh2) {
+    auto of = [&](auto k) -> StripBlob {
+        using K = decltype(k);
+        constexpr int CQ = K::C / 4;
+        return nh2 == 0 ? strip_blob_of<K, K>() : (nh2 == 1 ? strip_blob_of<SK2<CQ, 1>, K>() : (nh2 == 2 ? strip_blob_of<SK2<CQ, 2>, K>() : StripBlob{}));
+    };
+    return C == 16 ? of(SK<4>{}) : (C == 24 ? of(SK<6>{}) : (C == 32 ? of(SK<8>{}) : StripBlob{}));
+}
+
+// Both blobs: w_dw [3][3][C], b_dw [C] or null, w_pw [Co][C] (TFLite OHWI with H = W = 1), bias [Co] or null, alpha [Co] or null.
+void strip_pack_blob(const StripBlob& L, int C, int Co, const float* w_dw, const float* b_dw, const float* w_pw, const float* bias, const float* alpha, int act, float* dst) {
+    std::fill(dst, dst + L.TOTAL, 0.f);
+    if (!L.TOTAL) return;
     for (int st = 0; st < C / 2; st++) {  // input channels (2st, 2st+1)
-        float* rec = dst + (size_t)st * SF;
+        float* rec = dst + (size_t)st * L.ST_F;
         for (int t = 0; t < 9; t++)
             for (int e = 0; e < 2; e++) rec[2 * t + e] = w_dw[t * C + 2 * st + e];
         for (int half = 0; half < 2; half++)
-            for (int o = 0; o < C; o++) rec[32 + half * C + o] = w_pw[(size_t)o * C + 2 * st + half];
+            for (int o = 0; o < Co; o++) rec[32 + half * Co + o] = w_pw[(size_t)o * C + 2 * st + half];
     }
-    float* pb = dst + (size_t)(C / 2) * SF;
-    float* ps = pb + 32;
-    for (int c = 0; c < C; c++) {
+    float* pb = dst + L.OFF_BIAS;
+    float* ps = dst + L.OFF_SLOPE;
+    for (int c = 0; c < Co; c++) {
         // PW(dw + b_dw) + b_pw = PW(dw) + (W b_dw + b_pw): the depthwise bias is folded into the pointwise bias
         double acc = bias ? bias[c] : 0.0;
         if (b_dw)
@@ -2182,15 +1998,25 @@ void strip_pack_consts(int C, const float* w_dw, const float* b_dw, const float*
         pb[c] = (float)acc;
         ps[c] = act == ACT_PRELU ? alpha[c] : (act == ACT_NONE ? 1.f : 0.f);
     }
-    // A operands of v_mfma_f32_4x4x1_16b_f32 (SK::OFF_A): register n / 16, lanes 4 (n % 16) + i = W[4t + i][k], n = k CQ + t
-    float* pa = ps + 32;
+    // A operands of v_mfma_f32_4x4x1_16b_f32, one C x C slice of NA registers per C output channels (hf; the tail waves of the MFMA forms take
+    // one each): register n / 16, lanes 4 (n % 16) + i = W[hf C + 4t + i][k], n = k CQ + t
+    float* pa = dst + L.OFF_A;
     const int CQ = C / 4;
-    for (int k = 0; k < C; k++)
-        for (int t = 0; t < CQ; t++)
-            for (int i = 0; i < 4; i++) {
-                const int n = k * CQ + t;
-                pa[(n >> 4) * 64 + 4 * (n & 15) + i] = w_pw[(size_t)(4 * t + i) * C + k];
-            }
+    for (int hf = 0; hf < Co / C; hf++)
+        for (int k = 0; k < C; k++)
+            for (int t = 0; t < CQ; t++)
+                for (int i = 0; i < 4; i++) {
+                    const int n = k * CQ + t;
+                    pa[(size_t)(hf * L.NA + (n >> 4)) * 64 + 4 * (n & 15) + i] = w_pw[(size_t)(hf * C + 4 * t + i) * C + k];
+                }
+}
+
+}  // namespace
+
+int strip_consts_floats(int C) { return strip_blob(C, 0).TOTAL; }
+
+void strip_pack_consts(int C, const float* w_dw, const float* b_dw, const float* w_pw, const float* bias, const float* alpha, int act, float* dst) {
+    strip_pack_blob(strip_blob(C, 0), C, C, w_dw, b_dw, w_pw, bias, alpha, act, dst);
 }
 
 const char* strip_kernel_label(const BlockArgs& a, char* buf, size_t cap) {
@@ -2245,39 +2071,11 @@ bool strip_pipe_supports(const BlockArgs* blocks, int n) {
 bool strip_pipe_shape_ok(int C, int W) { return getenv("MI_NO_PIPE") == nullptr && (C == 16 || C == 24) && W <= 128; }
 bool strip_tail_shape_ok(int C, int Co, int H, int W) { return C == 24 && (Co == C || Co == 2 * C) && !(H & 1) && !(W & 1) && W <= 128; }
 
-int strip_consts_s2_floats(int C, int Co) { return C / 2 * ((32 + 2 * Co + 15) / 16 * 16) + 128 + (Co / C) * ((C * (C / 4) + 15) / 16) * 64; }
+int strip_consts_s2_floats(int C, int Co) { return Co % C ? 0 : strip_blob(C, Co / C).TOTAL; }
 
-// constants of a stride-2 tail block: w_dw [3][3][C], b_dw [C] or null, w_pw [Co][C], bias [Co] or null, alpha [Co] or null
+// constants of a stride-2 tail block (SK2)
 void strip_pack_consts_s2(int C, int Co, const float* w_dw, const float* b_dw, const float* w_pw, const float* bias, const float* alpha, int act, float* dst) {
-    const int SF = (32 + 2 * Co + 15) / 16 * 16;
-    std::fill(dst, dst + strip_consts_s2_floats(C, Co), 0.f);
-    for (int st = 0; st < C / 2; st++) {
-        float* rec = dst + (size_t)st * SF;
-        for (int t = 0; t < 9; t++)
-            for (int e = 0; e < 2; e++) rec[2 * t + e] = w_dw[t * C + 2 * st + e];
-        for (int half = 0; half < 2; half++)
-            for (int o = 0; o < Co; o++) rec[32 + half * Co + o] = w_pw[(size_t)o * C + 2 * st + half];
-    }
-    float* pb = dst + (size_t)(C / 2) * SF;
-    float* ps = pb + 64;
-    for (int c = 0; c < Co; c++) {
-        double acc = bias ? bias[c] : 0.0;
-        if (b_dw)
-            for (int k = 0; k < C; k++) acc += (double)w_pw[(size_t)c * C + k] * b_dw[k];
-        pb[c] = (float)acc;
-        ps[c] = act == ACT_PRELU ? alpha[c] : (act == ACT_NONE ? 1.f : 0.f);
-    }
-    // A operands of v_mfma_f32_4x4x1_16b_f32 for the tail waves of strip_pipe2m_kernel, one C x C slice per C output channels (hf):
-    // register n / 16, lanes 4 (n % 16) + i = W[hf C + 4t + i][k], n = k CQ + t
-    const int CQ = C / 4, NA = (C * CQ + 15) / 16;
-    float* pa = pb + 128;
-    for (int hf = 0; hf < Co / C; hf++)
-        for (int k = 0; k < C; k++)
-            for (int t = 0; t < CQ; t++)
-                for (int i = 0; i < 4; i++) {
-                    const int n = k * CQ + t;
-                    pa[(size_t)(hf * NA + (n >> 4)) * 64 + 4 * (n & 15) + i] = w_pw[(size_t)(hf * C + 4 * t + i) * C + k];
-                }
+    strip_pack_blob(Co % C ? StripBlob{} : strip_blob(C, Co / C), C, Co, w_dw, b_dw, w_pw, bias, alpha, act, dst);
 }
 
 // rows a pipeline step handles: two (strip_pipe2_kernel) whenever the height is even

@@ -24,8 +24,9 @@ CASES = {
     "tail_kernels.hip": ([], [""]),
     # round 5: the single-launch plan — one workgroup per CU, 256 registers a lane available, none of them in scratch
     "bandnet_kernels.hip": ([], [""]),
-    # the row pipelines of BASELINE config 2 (four stages, 24 channels, plain and with either stride-2 tail)
-    "strip_kernels.hip": (["-DMI_DEV_ONE"], ["strip_pipe2m_kernel<6, 4, true, 0>", "strip_pipe2m_kernel<6, 4, true, 1>", "strip_pipe2m_kernel<6, 4, true, 2>"]),
+    # the strip kernels and the row pipelines of BASELINE config 2 (four stages, 24 channels, plain and with either stride-2 tail), all four
+    # forms: they share the frame functions of strip_kernels.hip, so a change to one of those is a change to every kernel
+    "strip_kernels.hip": (["-DMI_DEV_ONE"], [""]),
 }
 
 
@@ -56,5 +57,7 @@ def test_register_limit_kernels_do_not_spill():
                 assert k["vgpr"] + k["agpr"] <= 256, (name, k["pretty"])      # two waves per SIMD
                 if name == "mdblock_kernels.hip" and "mdblock_kernel<MD<4, 4, 1, 2, 3," in k["pretty"]:
                     assert k["vgpr"] + k["agpr"] <= 168, (name, k["pretty"], k["vgpr"])   # the face mesh's block pair (with and without the first convolution in front): three waves per SIMD, four workgroups per CU
+                if k["pretty"].startswith(("strip_kernel<4,", "strip_kernel<6,")):
+                    assert k["vgpr"] + k["agpr"] <= 168, (name, k["pretty"], k["vgpr"])   # their launch bound: three waves per SIMD
                 if "tail_kernel<false>" in k["pretty"]:
                     assert k["vgpr"] + k["agpr"] <= 128, (name, k["pretty"], k["vgpr"])   # four waves per SIMD

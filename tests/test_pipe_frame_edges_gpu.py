@@ -5,7 +5,9 @@ the step that consumes the picture's last row pair instead of in a flush step of
 Skipping a step is equivalent to running it on rows of zeros, so everything here is bit for bit (np.testing.assert_array_equal on all raw network
 outputs): the whole-frame run against (a) the same bands on strip_pipe2_kernel ("pipe_rows" = 2), which this change does not touch, and (b)
 strip_pipe2m_kernel on interior bands ("pipe_band" = 2: every band but the first starts inside the picture) and on the automatic bands ("pipe_band"
-= 0).  Against the oracle the tolerance is test_gpu_parity.py's for raw network outputs.
+= 0).  Against the oracle the tolerance is test_gpu_parity.py's for raw network outputs.  The synthetic graphs also run the two one-row forms
+("pipe_rows" = 1: strip_pipe_kernel, 4: strip_pipe1m_kernel) on automatic and whole-frame bands, bit for bit against the default form: they
+share the row DMA, store, hand-over and tail-store functions with the two-row forms, and these sizes reach their partial-strip and inactive-unit paths.
 
 Every case forces the batched plan ("band" = 0) and the pipelines ("small_chain" = 0, "fuse" = 4), and reads from profile() which instantiations
 ran.  The synthetic frames are the smallest at which a schedule that is off by one step shows: 18 x 18 (band_rows / 2 = 9 row pairs against a fill
@@ -78,6 +80,21 @@ def _whole_frame_against_the_other_forms(m, x, tag):
         np.testing.assert_array_equal(a, b, err_msg="%s: strip_pipe2m_kernel differs from strip_pipe2_kernel on whole frames" % tag)
     m.set_option("pipe_rows", 0)
     return whole
+
+
+ONE_ROW_FORMS = {1: "strip_pipe_kernel<", 4: "strip_pipe1m_kernel<"}   # "pipe_rows" -> the kernel it selects
+
+
+def _one_row_forms_agree(m, x, whole, tag):
+    """The one-row forms share the row DMA, store, hand-over and tail-store functions with the two-row forms; at these sizes they reach their
+    partial-strip and inactive-unit paths.  Automatic and whole-frame bands, bit for bit against the default form's outputs."""
+    for rows, prefix in ONE_ROW_FORMS.items():
+        for band in (0, 4096):
+            got = _run(m, x, band, pipe_rows=rows)
+            _instantiations(m, x, prefix)
+            for a, b in zip(whole, got):
+                np.testing.assert_array_equal(a, b, err_msg="%s: pipe_rows %d at pipe_band %d differs from the default form" % (tag, rows, band))
+    m.set_option("pipe_rows", 0)
 
 
 @pytest.mark.parametrize("pipe", [2, 3, 4])
@@ -153,6 +170,7 @@ def test_synthetic_graphs_whole_frame_bands(gpu, oracle, synth_models, case):
     for nb in SYNTH[case][3]:
         x = np.random.RandomState(700 + nb).uniform(-1, 1, (nb, h, w, 3)).astype(np.float32)
         whole = _whole_frame_against_the_other_forms(m, x, "%s B=%d" % (case, nb))
+        _one_row_forms_agree(m, x, whole, "%s B=%d" % (case, nb))
         for o, r in zip(whole, oracle.Model(path).run(x, nthreads=max(1, nb))):
             _raw_close(o, r)
     m.close()
