@@ -151,57 +151,22 @@ __global__ __launch_bounds__(K::NWV * 64, 2) void mdblock_kernel(MdbArgs a) {
         }
 #pragma unroll
         for (int nt = 0; nt < SWT; nt++) {
-            const df32x4 v = D0[nt];
-            float4 o = make_float4(fminf(fmaxf(v.x, 0.f) + sl.x * fminf(v.x, 0.f), a.hi0), fminf(fmaxf(v.y, 0.f) + sl.y * fminf(v.y, 0.f), a.hi0),
-                                   fminf(fmaxf(v.z, 0.f) + sl.z * fminf(v.z, 0.f), a.hi0), fminf(fmaxf(v.w, 0.f) + sl.w * fminf(v.w, 0.f), a.hi0));
-            if (!inside) o = make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4*>(dstp + 16 * nt * PS) = o;
+            df32x4 v = mrow_act<false>(D0[nt], sl, a.hi0);
+            if (!inside) v = df32x4{0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<float4*>(dstp + 16 * nt * PS) = make_float4(v.x, v.y, v.z, v.w);
         }
     };
 
-    // ---- LDS-DMA of this wave's part of one input row: instruction k brings in pixels [x0 + 4 k, x0 + 4 k + 4): lane -> (pixel
-    // lane / QP, quad min(lane % QP, CK1 - 1)), lanes >= 4 QP idle; the immediate offset moves source and destination alike, M0 makes
-    // up the difference between the image's pixel stride and the tensor's
-    const int goff = ((lane / QP) * C + 4 * min(lane % QP, CK1 - 1)) * 4;
+    // ---- LDS-DMA of this wave's part of one input row (clamped to the frame; mrow_dma1: NLD instructions of DPX pixels) into x image `slot`
+    const int goff = mrow_goff<CK1>(lane);
     const unsigned lds_x = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)ximg);
     auto issue_row = [&](int r, int slot) {
         if constexpr (K::STEM) return;
-        const char* src = reinterpret_cast<const char*>(in + ((long)min(max(r, 0), a.H - 1) * W + x0) * C);
-        const unsigned dstb = lds_x + (unsigned)((slot * XIMG_F + (1 + x0) * PS) * 4);
-        unsigned long long saved;
-#define MI_MDB_DMA(k) "s_add_u32 m0, m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1 offset:" #k "*%6\n\t"
-        if constexpr (NLD == 8) {
-            asm volatile("s_mov_b64 %0, exec\n\ts_mov_b32 exec_lo, -1\n\ts_mov_b32 exec_hi, %4\n\t"
-                         "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\t"
-                         MI_MDB_DMA(1) MI_MDB_DMA(2) MI_MDB_DMA(3) MI_MDB_DMA(4) MI_MDB_DMA(5) MI_MDB_DMA(6) MI_MDB_DMA(7)
-                         "s_mov_b64 exec, %0"
-                         : "=&s"(saved)
-                         : "s"(src), "v"(goff), "s"(dstb), "n"((1u << (K::ACTIVE - 32)) - 1), "n"(K::DPX * (PS - C) * 4), "n"(K::DPX * C * 4)
-                         : "memory", "scc", "m0");
-        } else {
-            asm volatile("s_mov_b64 %0, exec\n\ts_mov_b32 exec_lo, -1\n\ts_mov_b32 exec_hi, %4\n\t"
-                         "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\t"
-                         MI_MDB_DMA(1) MI_MDB_DMA(2) MI_MDB_DMA(3)
-                         "s_mov_b64 exec, %0"
-                         : "=&s"(saved)
-                         : "s"(src), "v"(goff), "s"(dstb), "n"((1u << (K::ACTIVE - 32)) - 1), "n"(K::DPX * (PS - C) * 4), "n"(K::DPX * C * 4)
-                         : "memory", "scc", "m0");
-        }
-#undef MI_MDB_DMA
+        mrow_dma1<NLD, C, PS, K::DPX, K::ACTIVE>(reinterpret_cast<const char*>(in + ((long)min(max(r, 0), a.H - 1) * W + x0) * C),
+                                                 lds_x + (unsigned)((slot * XIMG_F + (1 + x0) * PS) * 4), goff);
     };
-    // rows outside the image are zero padding: the landed (clamped) row is cleared before anybody reads it
-    auto fix_row = [&](int r, int slot) {
-        if (K::STEM || (r >= 0 && r < a.H)) return;  // wave-uniform
-        float zz = 0.f;
-        asm volatile("" : "+v"(zz));
-        const float4 z = make_float4(zz, zz, zz, zz);
-        float* part = ximg + slot * XIMG_F + (1 + x0) * PS;
-        constexpr int N4 = K::SW * QP;
-#pragma unroll
-        for (int k = 0; k < (N4 + 63) / 64; k++)
-            if (64 * (k + 1) <= N4 || lane < N4 - 64 * k) *reinterpret_cast<float4*>(part + 4 * (lane + 64 * k)) = z;
-    };
-    // border pixel columns of the four images are never written afterwards: cleared once
+    // border pixel columns of the four images are never written afterwards
+    // (inline: as mrow_clear_border the compiler places other lgkmcnt waits in the STEM form)
     if (wave == 0) {
         if (lane < 2 * QP) {
             const int col = lane / QP, qd = lane - col * QP;
@@ -248,75 +213,41 @@ __global__ __launch_bounds__(K::NWV * 64, 2) void mdblock_kernel(MdbArgs a) {
 #pragma unroll
     for (int ks = 0; ks < CK2; ks++) { p2A[ks].clear(); p2B[ks].clear(); }
     df32x4 D1[MT1][WT], PA[MT2][WT], PB[MT2][WT];   // PA / PB: accumulators of the output rows of even / odd steps, waiting with bias + skip inside
-    // D1 <- bias1 (+ with PAIR the first block's skip: the centre pixels of the x row in image `slot`, for the a row of the same index)
-    auto init_D1 = [&](int slot) {
+    const float* b1 = wgc + K::OFF_B1 + 4 * kq;   // this lane's biases and slopes of a 16-channel tile (stage 1's slopes: written out at mrow_store_a,
+                                                  // a named pointer moves a wait of the STEM form)
+    const float* b2 = wgc + K::OFF_B2 + 4 * kq;
+    const float* s2 = wgc + K::OFF_S2 + 4 * kq;
+    // PAIR: D1 <- bias1 + the first block's skip, the centre pixels of the x row in image `slot`, for the a row of the same index
+    // (inline, tile by tile: as mrow_init_acc, all reads in front of the adds, the STEM form gets other lgkmcnt waits)
+    auto init_D1_skip = [&](int slot) {
 #pragma unroll
         for (int mt = 0; mt < MT1; mt++) {
-            const float4 bs = *reinterpret_cast<const float4*>(wgc + K::OFF_B1 + 16 * mt + 4 * kq);
+            const float4 bs = *reinterpret_cast<const float4*>(b1 + 16 * mt);
 #pragma unroll
             for (int nt = 0; nt < WT; nt++) {
                 float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (K::PAIR && 16 * mt < C) x = *reinterpret_cast<const float4*>(sme + slot * XIMG_F + 16 * nt * PS + 16 * mt);
+                if (16 * mt < C) x = *reinterpret_cast<const float4*>(sme + slot * XIMG_F + 16 * nt * PS + 16 * mt);
                 D1[mt][nt] = df32x4{bs.x + x.x, bs.y + x.y, bs.z + x.z, bs.w + x.w};
             }
         }
     };
-    // P <- bias2 + skip for the output row whose centre input row sits in x image `slot`
+    // rows outside the image are zero padding: the landed (clamped) row is cleared before anybody reads it
+    // (inline: as mrow_clear_row one compiler-placed wait of MD<8,8,2,1,3,true,4,..,PAIR> with RELU goes)
+    auto fix_row = [&](int r, int slot) {
+        if (r >= 0 && r < a.H) return;  // wave-uniform
+        float zz = 0.f;
+        asm volatile("" : "+v"(zz));
+        const float4 z = make_float4(zz, zz, zz, zz);
+        float* part = ximg + slot * XIMG_F + (1 + x0) * PS;
+        constexpr int N4 = K::SW * QP;
+#pragma unroll
+        for (int k = 0; k < (N4 + 63) / 64; k++)
+            if (64 * (k + 1) <= N4 || lane < N4 - 64 * k) *reinterpret_cast<float4*>(part + 4 * (lane + 64 * k)) = z;
+    };
+    // P <- bias2 + skip for the output row whose centre input row sits in x image `slot` (PAIR: the second block's skip, the a row in a image `slot`)
     auto init_P = [&](df32x4 (&P)[MT2][WT], int slot) {
-        float4 bs[MT2], x[MT2][WT];
-#pragma unroll
-        for (int mt = 0; mt < MT2; mt++) bs[mt] = *reinterpret_cast<const float4*>(wgc + K::OFF_B2 + 16 * mt + 4 * kq);
-#pragma unroll
-        for (int mt = 0; mt < MT2; mt++)
-#pragma unroll
-            for (int nt = 0; nt < WT; nt++) {
-                x[mt][nt] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (K::PAIR) {  // the second block's skip: the a row in image `slot` (same pixels, D layout)
-                    if (16 * mt < K::Cm) x[mt][nt] = *reinterpret_cast<const float4*>(awr + slot * AIMG_F + 16 * nt * PSA + 16 * mt);
-                } else if (16 * mt < C) {
-                    x[mt][nt] = *reinterpret_cast<const float4*>(sme + slot * XIMG_F + 16 * nt * PS + 16 * mt);  // channels >= C: the zero channel-pad of the skip
-                }
-            }
-#pragma unroll
-        for (int mt = 0; mt < MT2; mt++)
-#pragma unroll
-            for (int nt = 0; nt < WT; nt++) P[mt][nt] = df32x4{x[mt][nt].x + bs[mt].x, x[mt][nt].y + bs[mt].y, x[mt][nt].z + bs[mt].z, x[mt][nt].w + bs[mt].w};
-    };
-    auto act = [&](df32x4 v, const float4& sl, float hi) {
-        if (RELU) return df32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        // act(v) = min(max(v,0) + slope*min(v,0), hi): ReLU (slope 0), PReLU (alpha), none (1), ReLU6 (hi = 6)
-        return df32x4{fminf(fmaxf(v.x, 0.f) + sl.x * fminf(v.x, 0.f), hi), fminf(fmaxf(v.y, 0.f) + sl.y * fminf(v.y, 0.f), hi),
-                      fminf(fmaxf(v.z, 0.f) + sl.z * fminf(v.z, 0.f), hi), fminf(fmaxf(v.w, 0.f) + sl.w * fminf(v.w, 0.f), hi)};
-    };
-    // a row q (image row; zeros outside the image: the next depthwise conv's padding) -> a image `slot`
-    auto store_a = [&](int q, int slot) {
-        const bool inside = q >= 0 && q < a.H;
-#pragma unroll
-        for (int mt = 0; mt < MT1; mt++) {
-            float4 sl = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!RELU) sl = *reinterpret_cast<const float4*>(wgc + K::OFF_S1 + 16 * mt + 4 * kq);
-            if (16 * mt + 4 * kq < K::Cm) {
-#pragma unroll
-                for (int nt = 0; nt < WT; nt++) {
-                    df32x4 v = act(D1[mt][nt], sl, a.hi1);
-                    if (!inside) v = df32x4{0.f, 0.f, 0.f, 0.f};
-                    *reinterpret_cast<float4*>(awr + slot * AIMG_F + 16 * nt * PSA + 16 * mt) = make_float4(v.x, v.y, v.z, v.w);
-                }
-            }
-        }
-    };
-    typedef __attribute__((address_space(1))) char gchar;
-    typedef __attribute__((address_space(1))) df32x4 gf32x4;
-    auto epilogue = [&](df32x4 (&P)[MT2][WT], int y) {
-        gchar* dst = (gchar*)(a.out + (long)b * a.out_fs + (long)y * W * Co);
-        asm volatile("" : "+s"(dst));
-#pragma unroll
-        for (int mt = 0; mt < MT2; mt++) {
-            float4 sl = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!RELU) sl = *reinterpret_cast<const float4*>(wgc + K::OFF_S2 + 16 * mt + 4 * kq);
-#pragma unroll
-            for (int nt = 0; nt < WT; nt++) *(gf32x4*)(dst + ooff + (unsigned)((16 * nt * Co + 16 * mt) * 4)) = act(P[mt][nt], sl, a.hi2);
-        }
+        if constexpr (K::PAIR) mrow_init_acc<K::Cm, PSA>(P, b2, awr + slot * AIMG_F, true);
+        else mrow_init_acc<C, PS>(P, b2, sme + slot * XIMG_F, true);
     };
 
     // vmcnt bookkeeping: vector-memory operations retire in issue order.  A step's operations: the stores of its output row (NST, from
@@ -324,30 +255,25 @@ __global__ __launch_bounds__(K::NWV * 64, 2) void mdblock_kernel(MdbArgs a) {
     // issued behind its DMA is outstanding: the previous step's stores and DMA.
     constexpr int NST = MT2 * WT;
     const int TL = (y1 - y0) + 3;   // last step; step t handles x row y0 - 2 + t, a row y0 - 3 + t (from t = 2), y row y0 - 4 + t (from t = 4)
-    auto wait_row = [&](int t) {
-        if constexpr (K::STEM) return;   // (no DMA: the compiler counts the loads and stores it sees)
-        const bool st = t - 1 >= 4, dm = t == 0 || t + 1 <= TL;  // step 0: the prologue's second row is behind it
-        if (st && dm) wait_vm<NST + NLD>();
-        else if (dm) wait_vm<NLD>();
-        else if (st) wait_vm<NST>();
-        else wait_vm<0>();
-    };
     // e1 / e2: stage 1 / stage 2 finish a row in this step
     auto step = [&](auto e1c, auto e2c, int t, RowAcc<WT> (&q1PN)[CK1], RowAcc<WT> (&q1C)[CK1], RowAcc<WT> (&q2PN)[CK2], RowAcc<WT> (&q2C)[CK2], df32x4 (&P)[MT2][WT]) {
         constexpr bool E1 = decltype(e1c)::value, E2 = decltype(e2c)::value;
         const int r = y0 - 2 + t, slot = t & 1;
         if constexpr (K::STEM) stem_load(r + 1);   // the picture's values for x row r + 1: on their way during this step
-        wait_row(t);
-        fix_row(r, slot);
+        // (STEM: no DMA, the compiler counts the loads and stores it sees; stem_emit writes the rows outside the frame as zeros)
+        if constexpr (!K::STEM) {
+            mrow_wait<NST, NLD>(t - 1 >= 4, t == 0 || t + 1 <= TL);  // step 0: the prologue's second row is behind it
+            fix_row(r, slot);
+        }
         dwg_barrier();   // x row r is complete (every wave's part has landed and is fixed / with STEM: was written in the previous step)
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (E1 && !K::PAIR) init_D1(slot);
+        if constexpr (E1 && !K::PAIR) mrow_init_acc<C, PS>(D1, b1, sme, false);
         mdb_row<CK1, MT1, WT, PS, E1>(x_lds + (unsigned)(slot * XIMG_F * 4), a1_lds, tap1, q1PN, q1C, D1);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (K::PAIR) {
             // the next a row (r) starts from bias + ITS skip, the centre pixels of x row r, and waits in D1 for one step
-            if constexpr (E1) store_a(r - 1, slot);
-            init_D1(slot);
+            if constexpr (E1) mrow_store_a<RELU, K::Cm, PSA>(D1, awr + slot * AIMG_F, wgc + K::OFF_S1 + 4 * kq, a.hi1, r - 1 >= 0 && r - 1 < a.H, kq);
+            init_D1_skip(slot);
             if constexpr (E1) {
                 dwg_barrier();   // a row r - 1 is complete
                 __builtin_amdgcn_sched_barrier(0);
@@ -355,14 +281,14 @@ __global__ __launch_bounds__(K::NWV * 64, 2) void mdblock_kernel(MdbArgs a) {
                 if constexpr (E2) init_P(P, slot ^ 1);
             }
         } else if constexpr (E1) {
-            store_a(r - 1, slot);
+            mrow_store_a<RELU, K::Cm, PSA>(D1, awr + slot * AIMG_F, wgc + K::OFF_S1 + 4 * kq, a.hi1, r - 1 >= 0 && r - 1 < a.H, kq);
             dwg_barrier();   // a row r - 1 is complete
             __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (E1) {
             mdb_row<CK2, MT2, WT, PSA, E2, K::TAPL2>(a_lds + (unsigned)(slot * AIMG_F * 4), a2_lds, tap2, q2PN, q2C, P, reinterpret_cast<const float4*>(wgc + K::OFF_T2) + kq * 3);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (E2) epilogue(P, r - 2);
+            if constexpr (E2) mrow_store_row<RELU, Co, 16 * WT>(P, (gchar*)(a.out + (long)b * a.out_fs + (long)(r - 2) * W * Co), ooff, s2, a.hi2, p);
             __builtin_amdgcn_sched_barrier(0);
         } else {
             dwg_barrier();   // priming steps: the neighbours have read this row's halo pixels before this wave's next DMA lands on them
@@ -445,39 +371,14 @@ __global__ __launch_bounds__(K::NF * K::NWV * 64, 2) void mbneck_kernel(MdbArgs 
     const int x0 = strip * K::SW;
     const float* in = a.in + (long)b * a.in_fs;
 
-    const int goff = ((lane / QP) * C + 4 * min(lane % QP, CK1 - 1)) * 4;
+    const int goff = mrow_goff<CK1>(lane);
     const unsigned lds_x = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)ximg);
     auto issue_row = [&](int r, int slot) {
-        const char* src = reinterpret_cast<const char*>(in + ((long)min(max(r, 0), a.H - 1) * W + x0) * C);
-        const unsigned dstb = lds_x + (unsigned)((slot * XIMG_F + (1 + x0) * PS) * 4);
-        unsigned long long saved;
-#define MI_MDB_DMA(k) "s_add_u32 m0, m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1 offset:" #k "*%6\n\t"
-        asm volatile("s_mov_b64 %0, exec\n\ts_mov_b32 exec_lo, -1\n\ts_mov_b32 exec_hi, %4\n\t"
-                     "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\t"
-                     MI_MDB_DMA(1) MI_MDB_DMA(2) MI_MDB_DMA(3) MI_MDB_DMA(4) MI_MDB_DMA(5) MI_MDB_DMA(6) MI_MDB_DMA(7)
-                     "s_mov_b64 exec, %0"
-                     : "=&s"(saved)
-                     : "s"(src), "v"(goff), "s"(dstb), "n"((1u << (K::ACTIVE - 32)) - 1), "n"(K::DPX * (PS - C) * 4), "n"(K::DPX * C * 4)
-                     : "memory", "scc", "m0");
-#undef MI_MDB_DMA
+        mrow_dma1<NLD, C, PS, K::DPX, K::ACTIVE>(reinterpret_cast<const char*>(in + ((long)min(max(r, 0), a.H - 1) * W + x0) * C),
+                                                 lds_x + (unsigned)((slot * XIMG_F + (1 + x0) * PS) * 4), goff);
     };
-    auto fix_row = [&](int r, int slot) {
-        if (r >= 0 && r < a.H) return;  // wave-uniform
-        float zz = 0.f;
-        asm volatile("" : "+v"(zz));
-        const float4 z = make_float4(zz, zz, zz, zz);
-        float* part = ximg + slot * XIMG_F + (1 + x0) * PS;
-        constexpr int N4 = K::SW * QP;
-#pragma unroll
-        for (int k = 0; k < (N4 + 63) / 64; k++)
-            if (64 * (k + 1) <= N4 || lane < N4 - 64 * k) *reinterpret_cast<float4*>(part + 4 * (lane + 64 * k)) = z;
-    };
-    // border pixel columns of the a images are never written afterwards: cleared once (x's border columns are never read: stage 1 is pointwise)
-    if (strip == 0 && lane < 2 * QPA) {
-        const int col = lane / QPA, qd = lane - col * QPA;
-#pragma unroll
-        for (int s = 0; s < 2; s++) *reinterpret_cast<float4*>(aimg + s * AIMG_F + col * (W + 1) * PSA + 4 * qd) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    // border pixel columns of the a images are never written afterwards (x's border columns are never read: stage 1 is pointwise)
+    if (strip == 0) mrow_clear_border<QPA, 2, AIMG_F, (W + 1) * PSA>(aimg, lane);
     issue_row(y0 - 1, 0);
     for (int i = threadIdx.x; i < K::TOTAL / 4; i += NF * NWV * 64) reinterpret_cast<float4*>(wgc)[i] = reinterpret_cast<const float4*>(a.consts)[i];
     issue_row(y0, 1);
@@ -499,92 +400,31 @@ __global__ __launch_bounds__(K::NF * K::NWV * 64, 2) void mbneck_kernel(MdbArgs 
 #pragma unroll
     for (int ks = 0; ks < CK2; ks++) { p2A[ks].clear(); p2B[ks].clear(); }
     df32x4 D1[MT1][WT], PA[MT2][WT], PB[MT2][WT];
-    auto init_D1 = [&]() {
-#pragma unroll
-        for (int mt = 0; mt < MT1; mt++) {
-            const float4 bs = *reinterpret_cast<const float4*>(wgc + K::OFF_B1 + 16 * mt + 4 * kq);
-#pragma unroll
-            for (int nt = 0; nt < WT; nt++) D1[mt][nt] = df32x4{bs.x, bs.y, bs.z, bs.w};
-        }
-    };
-    auto init_P = [&](df32x4 (&P)[MT2][WT], int slot) {
-        float4 bs[MT2], x[MT2][WT];
-#pragma unroll
-        for (int mt = 0; mt < MT2; mt++) bs[mt] = *reinterpret_cast<const float4*>(wgc + K::OFF_B2 + 16 * mt + 4 * kq);
-#pragma unroll
-        for (int mt = 0; mt < MT2; mt++)
-#pragma unroll
-            for (int nt = 0; nt < WT; nt++) {
-                x[mt][nt] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (16 * mt < C) x[mt][nt] = *reinterpret_cast<const float4*>(sme + slot * XIMG_F + 16 * nt * PS + 16 * mt);
-            }
-#pragma unroll
-        for (int mt = 0; mt < MT2; mt++)
-#pragma unroll
-            for (int nt = 0; nt < WT; nt++) P[mt][nt] = df32x4{x[mt][nt].x + bs[mt].x, x[mt][nt].y + bs[mt].y, x[mt][nt].z + bs[mt].z, x[mt][nt].w + bs[mt].w};
-    };
-    auto act = [&](df32x4 v, const float4& sl, float hi) {
-        if (RELU) return df32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        return df32x4{fminf(fmaxf(v.x, 0.f) + sl.x * fminf(v.x, 0.f), hi), fminf(fmaxf(v.y, 0.f) + sl.y * fminf(v.y, 0.f), hi),
-                      fminf(fmaxf(v.z, 0.f) + sl.z * fminf(v.z, 0.f), hi), fminf(fmaxf(v.w, 0.f) + sl.w * fminf(v.w, 0.f), hi)};
-    };
-    auto store_a = [&](int q, int slot) {
-        const bool inside = q >= 0 && q < a.H;
-#pragma unroll
-        for (int mt = 0; mt < MT1; mt++) {
-            float4 sl = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!RELU) sl = *reinterpret_cast<const float4*>(wgc + K::OFF_S1 + 16 * mt + 4 * kq);
-            if (16 * mt + 4 * kq < K::Cm) {
-#pragma unroll
-                for (int nt = 0; nt < WT; nt++) {
-                    df32x4 v = act(D1[mt][nt], sl, a.hi1);
-                    if (!inside) v = df32x4{0.f, 0.f, 0.f, 0.f};
-                    *reinterpret_cast<float4*>(awr + slot * AIMG_F + 16 * nt * PSA + 16 * mt) = make_float4(v.x, v.y, v.z, v.w);
-                }
-            }
-        }
-    };
-    typedef __attribute__((address_space(1))) char gchar;
-    typedef __attribute__((address_space(1))) df32x4 gf32x4;
-    auto epilogue = [&](df32x4 (&P)[MT2][WT], int y) {
-        gchar* dst = (gchar*)(a.out + (long)b * a.out_fs + (long)y * W * Co);
-        asm volatile("" : "+s"(dst));
-#pragma unroll
-        for (int mt = 0; mt < MT2; mt++) {
-            float4 sl = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!RELU) sl = *reinterpret_cast<const float4*>(wgc + K::OFF_S2 + 16 * mt + 4 * kq);
-#pragma unroll
-            for (int nt = 0; nt < WT; nt++) *(gf32x4*)(dst + ooff + (unsigned)((16 * nt * Co + 16 * mt) * 4)) = act(P[mt][nt], sl, a.hi2);
-        }
-    };
+    const float* b1 = wgc + K::OFF_B1 + 4 * kq;   // this lane's biases and slopes of a 16-channel tile
+    const float* b2 = wgc + K::OFF_B2 + 4 * kq;
+    const float* s1 = wgc + K::OFF_S1 + 4 * kq;
+    const float* s2 = wgc + K::OFF_S2 + 4 * kq;
     // step t handles x row and a row y0 - 1 + t, y row y0 - 2 + t (from t = 2).  vmcnt: the stores of a step's output row (NST, from the
     // third step on), then the DMA of the row two steps ahead; "row r has landed" = at most the previous step's stores and DMA are outstanding.
     constexpr int NST = MT2 * WT;
     const int TL = (y1 - y0) + 1;
-    auto wait_row = [&](int t) {
-        const bool st = t - 1 >= 2, dm = t == 0 || t + 1 <= TL;
-        if (st && dm) wait_vm<NST + NLD>();
-        else if (dm) wait_vm<NLD>();
-        else if (st) wait_vm<NST>();
-        else wait_vm<0>();
-    };
     auto step = [&](auto e2c, int t, RowAcc<WT> (&q2PN)[CK2], RowAcc<WT> (&q2C)[CK2], df32x4 (&Pc)[MT2][WT], df32x4 (&Pi)[MT2][WT]) {
         constexpr bool E2 = decltype(e2c)::value;
         const int r = y0 - 1 + t, slot = t & 1;
-        wait_row(t);
-        fix_row(r, slot);
+        mrow_wait<NST, NLD>(t - 1 >= 2, t == 0 || t + 1 <= TL);
+        if (r < 0 || r >= a.H) mrow_clear_row<K::SW * QP>(ximg + slot * XIMG_F + (1 + x0) * PS, lane);  // wave-uniform
         wave_sync();
-        init_D1();
+        mrow_init_acc<C, PS>(D1, b1, sme, false);
         mpw_row<CK1, MT1, WT, PS>(xc_lds + (unsigned)(slot * XIMG_F * 4), a1_lds, D1);
         __builtin_amdgcn_sched_barrier(0);
-        store_a(r, slot);
+        mrow_store_a<RELU, K::Cm, PSA>(D1, awr + slot * AIMG_F, s1, a.hi1, r >= 0 && r < a.H, kq);
         dwg_barrier();   // a row r is complete (the neighbours' pixels included)
         __builtin_amdgcn_sched_barrier(0);
         mdb_row<CK2, MT2, WT, PSA, E2>(a_lds + (unsigned)(slot * AIMG_F * 4), a2_lds, tap2, q2PN, q2C, Pc);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (E2) epilogue(Pc, r - 1);
+        if constexpr (E2) mrow_store_row<RELU, Co, 16 * WT>(Pc, (gchar*)(a.out + (long)b * a.out_fs + (long)(r - 1) * W * Co), ooff, s2, a.hi2, p);
         __builtin_amdgcn_sched_barrier(0);
-        init_P(Pi, slot);   // output row r starts from bias + its skip, the centre pixels of x row r
+        mrow_init_acc<C, PS>(Pi, b2, sme + slot * XIMG_F, true);   // output row r starts from bias + its skip, the centre pixels of x row r
         __builtin_amdgcn_sched_barrier(0);
         wave_sync();
         __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -608,29 +448,11 @@ void mbn_pack(const float* w_pw1, const float* b1, const float* alpha1, int act1
               const float* alpha2, int act2, float* dst) {
     constexpr int C = K::C, Cm = K::Cm, Co = K::Co;
     std::fill(dst, dst + K::TOTAL, 0.f);
-    for (int ks = 0; ks < K::CK1; ks++)
-        for (int mt = 0; mt < K::MT1; mt++)
-            for (int l = 0; l < 64; l++) {
-                const int o = 16 * mt + (l & 15);
-                if (o < Cm) dst[K::OFF_A1 + (ks * K::MT1 + mt) * 64 + l] = w_pw1[(size_t)o * C + 4 * ks + (l >> 4)];
-            }
-    for (int ks = 0; ks < K::CK2; ks++)
-        for (int mt = 0; mt < K::MT2; mt++)
-            for (int l = 0; l < 64; l++) dst[K::OFF_A2 + (ks * K::MT2 + mt) * 64 + l] = w_pw2[(size_t)(16 * mt + (l & 15)) * Cm + 4 * ks + (l >> 4)];
-    for (int ks = 0; ks < K::CK2; ks++)
-        for (int kq = 0; kq < 4; kq++)
-            for (int t = 0; t < 9; t++) dst[K::OFF_T2 + (ks * 4 + kq) * 12 + t] = w_dw2[t * Cm + 4 * ks + kq];
-    for (int c = 0; c < Cm; c++) {
-        dst[K::OFF_B1 + c] = b1 ? b1[c] : 0.f;
-        dst[K::OFF_S1 + c] = act1 == ACT_PRELU ? alpha1[c] : (act1 == ACT_NONE ? 1.f : 0.f);
-    }
-    for (int c = 0; c < Co; c++) {
-        double acc = b2 ? b2[c] : 0.0;
-        if (b_dw2)
-            for (int k = 0; k < Cm; k++) acc += (double)w_pw2[(size_t)c * Cm + k] * b_dw2[k];
-        dst[K::OFF_B2 + c] = (float)acc;
-        dst[K::OFF_S2 + c] = act2 == ACT_PRELU ? alpha2[c] : (act2 == ACT_NONE ? 1.f : 0.f);
-    }
+    mrow_pack_a(dst + K::OFF_A1, w_pw1, K::CK1, K::MT1, Cm);
+    mrow_pack_a(dst + K::OFF_A2, w_pw2, K::CK2, K::MT2, Co);
+    mrow_pack_taps(dst + K::OFF_T2, w_dw2, K::CK2);
+    mrow_pack_bias(dst + K::OFF_B1, dst + K::OFF_S1, Cm, C, w_pw1, nullptr, b1, alpha1, act1);   // (no depthwise stage in front: b1 as it is)
+    mrow_pack_bias(dst + K::OFF_B2, dst + K::OFF_S2, Co, Cm, w_pw2, b_dw2, b2, alpha2, act2);
 }
 
 using MD96 = MD<8, 2, 2, 2, 3>;    // 96 x 96: 32 -> 8 -> 32
@@ -646,38 +468,12 @@ void mdb_pack(const float* w_dw1, const float* b_dw1, const float* w_pw1, const 
               const float* w_pw2, const float* b2, const float* alpha2, int act2, float* dst) {
     constexpr int C = K::C, Cm = K::Cm, Co = K::Co;
     std::fill(dst, dst + K::TOTAL, 0.f);
-    // A operand of v_mfma_f32_16x16x4_f32 for (k-step ks, output tile mt): lane l holds W[16 mt + l % 16][4 ks + l / 16]
-    for (int ks = 0; ks < K::CK1; ks++)
-        for (int mt = 0; mt < K::MT1; mt++)
-            for (int l = 0; l < 64; l++) {
-                const int o = 16 * mt + (l & 15);
-                if (o < Cm) dst[K::OFF_A1 + (ks * K::MT1 + mt) * 64 + l] = w_pw1[(size_t)o * C + 4 * ks + (l >> 4)];
-            }
-    for (int ks = 0; ks < K::CK2; ks++)
-        for (int mt = 0; mt < K::MT2; mt++)
-            for (int l = 0; l < 64; l++) dst[K::OFF_A2 + (ks * K::MT2 + mt) * 64 + l] = w_pw2[(size_t)(16 * mt + (l & 15)) * Cm + 4 * ks + (l >> 4)];
-    // taps [ks][kq][12]: the nine taps of channel 4 ks + kq (three float4 loads per k-step)
-    for (int ks = 0; ks < K::CK1; ks++)
-        for (int kq = 0; kq < 4; kq++)
-            for (int t = 0; t < 9; t++) dst[K::OFF_T1 + (ks * 4 + kq) * 12 + t] = w_dw1[t * C + 4 * ks + kq];
-    for (int ks = 0; ks < K::CK2; ks++)
-        for (int kq = 0; kq < 4; kq++)
-            for (int t = 0; t < 9; t++) dst[K::OFF_T2 + (ks * 4 + kq) * 12 + t] = w_dw2[t * Cm + 4 * ks + kq];
-    // PW(dw + b_dw) + b_pw = PW(dw) + (W b_dw + b_pw): the depthwise biases are folded into the pointwise biases
-    for (int c = 0; c < Cm; c++) {
-        double acc = b1 ? b1[c] : 0.0;
-        if (b_dw1)
-            for (int k = 0; k < C; k++) acc += (double)w_pw1[(size_t)c * C + k] * b_dw1[k];
-        dst[K::OFF_B1 + c] = (float)acc;
-        dst[K::OFF_S1 + c] = act1 == ACT_PRELU ? alpha1[c] : (act1 == ACT_NONE ? 1.f : 0.f);
-    }
-    for (int c = 0; c < Co; c++) {
-        double acc = b2 ? b2[c] : 0.0;
-        if (b_dw2)
-            for (int k = 0; k < Cm; k++) acc += (double)w_pw2[(size_t)c * Cm + k] * b_dw2[k];
-        dst[K::OFF_B2 + c] = (float)acc;
-        dst[K::OFF_S2 + c] = act2 == ACT_PRELU ? alpha2[c] : (act2 == ACT_NONE ? 1.f : 0.f);
-    }
+    mrow_pack_a(dst + K::OFF_A1, w_pw1, K::CK1, K::MT1, Cm);
+    mrow_pack_a(dst + K::OFF_A2, w_pw2, K::CK2, K::MT2, Co);
+    mrow_pack_taps(dst + K::OFF_T1, w_dw1, K::CK1);
+    mrow_pack_taps(dst + K::OFF_T2, w_dw2, K::CK2);
+    mrow_pack_bias(dst + K::OFF_B1, dst + K::OFF_S1, Cm, C, w_pw1, b_dw1, b1, alpha1, act1);
+    mrow_pack_bias(dst + K::OFF_B2, dst + K::OFF_S2, Co, Cm, w_pw2, b_dw2, b2, alpha2, act2);
 }
 
 template <class K>
@@ -701,14 +497,7 @@ int mdb_launch(const DblockArgs& a, hipStream_t s) {
     const bool relu = a.act1 == ACT_RELU && a.act2 == ACT_RELU;
     const dim3 grid((unsigned)((long)a.B * ma.bands));
     const size_t lds_bytes = (size_t)K::LDS_F * 4;
-    if (relu) {
-        auto kern = mdblock_kernel<K, true>;
-        if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-        return (int)launch_kernel(kern, grid, dim3(K::NWV * 64), lds_bytes, s, ma);
-    }
-    auto kern = mdblock_kernel<K, false>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, grid, dim3(K::NWV * 64), lds_bytes, s, ma);
+    return mrow_launch(mdblock_kernel<K, true>, mdblock_kernel<K, false>, relu, grid, dim3(K::NWV * 64), lds_bytes, s, ma);
 }
 
 // 0: none; 1: 96 wide 32 -> 8 -> 32; 2: 48 wide 48 -> 12 -> 48; 3: 48 wide 48 -> 16 -> 64; 4: 48 wide 48 -> 24 -> 48;
@@ -843,15 +632,7 @@ int launch_mbneck(const BneckArgs& a, void* stream) {
     const bool relu = a.blocks[0].act1 == ACT_RELU && a.blocks[0].act2 == ACT_RELU;
     const dim3 grid((unsigned)((long)groups * ma.bands));
     const size_t lds_bytes = (size_t)K::LDS_F * 4;
-    hipStream_t s = (hipStream_t)stream;
-    if (relu) {
-        auto kern = mbneck_kernel<K, true>;
-        if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-        return (int)launch_kernel(kern, grid, dim3(K::NF * K::NWV * 64), lds_bytes, s, ma);
-    }
-    auto kern = mbneck_kernel<K, false>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, grid, dim3(K::NF * K::NWV * 64), lds_bytes, s, ma);
+    return mrow_launch(mbneck_kernel<K, true>, mbneck_kernel<K, false>, relu, grid, dim3(K::NF * K::NWV * 64), lds_bytes, (hipStream_t)stream, ma);
 }
 
 }  // namespace mi

@@ -96,8 +96,7 @@ __device__ __forceinline__ void ms2_row(const unsigned src, const unsigned aop, 
         float (&aw)[MT] = av[ks & 1];
         float w[9];
         if constexpr (TAPL) {
-            const float4 t0 = tapl[ks * 12], t1 = tapl[ks * 12 + 1], t2 = tapl[ks * 12 + 2];
-            w[0] = t0.x; w[1] = t0.y; w[2] = t0.z; w[3] = t0.w; w[4] = t1.x; w[5] = t1.y; w[6] = t1.z; w[7] = t1.w; w[8] = t2.x;
+            mrow_taps9(tapl + ks * 12, w);
         } else {
 #pragma unroll
             for (int t = 0; t < 9; t++) w[t] = tap[ks][t];
@@ -152,34 +151,19 @@ __global__ __launch_bounds__(K::NF * K::NWV * 64, 2) void ms2_kernel(Ms2Args a) 
     const int ngrp = npx / (4 * K::DPX);               // DMA groups of four instructions
     const float* in = a.in + (long)b * a.in_fs;
 
-    const int goff = ((lane / QP) * C + 4 * min(lane % QP, CK - 1)) * 4;
+    const int goff = mrow_goff<CK>(lane);
     const unsigned lds_img = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)img);
     auto issue_row = [&](int r, int slot) {   // input row r (clamped: rows below the image are cleared after landing) -> image `slot`
         const char* src = reinterpret_cast<const char*>(in + ((long)min(r, Hi - 1) * WI + 2 * xo0) * C);
         unsigned dstb = lds_img + (unsigned)((slot * IMG_F + 2 * xo0 * PS) * 4);
-        for (int gi = 0; gi < ngrp; gi++) {   // wave-uniform
-            unsigned long long saved;
-#define MI_MS2_DMA(k) "s_add_u32 m0, m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1 offset:" #k "*%6\n\t"
-            asm volatile("s_mov_b64 %0, exec\n\ts_mov_b32 exec_lo, -1\n\ts_mov_b32 exec_hi, %4\n\t"
-                         "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\t"
-                         MI_MS2_DMA(1) MI_MS2_DMA(2) MI_MS2_DMA(3)
-                         "s_mov_b64 exec, %0"
-                         : "=&s"(saved)
-                         : "s"(src), "v"(goff), "s"(dstb), "n"(K::ACTIVE == 64 ? 0xffffffffu : ((1u << (K::ACTIVE - 32)) - 1)), "n"(K::DPX * (PS - C) * 4), "n"(K::DPX * C * 4)
-                         : "memory", "scc", "m0");
-#undef MI_MS2_DMA
+        for (int gi = 0; gi < ngrp; gi++) {   // wave-uniform: groups of four instructions (mrow_dma1)
+            mrow_dma1<4, C, PS, K::DPX, K::ACTIVE>(src, dstb, goff);
             src += 4 * K::DPX * C * 4;
             dstb += 4 * K::DPX * PS * 4;
         }
     };
-    auto fix_row = [&](int r, int slot) {   // rows below the image: zeros
-        if (r < Hi) return;  // wave-uniform
-        float zz = 0.f;
-        asm volatile("" : "+v"(zz));
-        const float4 z = make_float4(zz, zz, zz, zz);
-        float* part = img + slot * IMG_F + 2 * xo0 * PS;
-        const int n4 = npx * QP;
-        for (int k = lane; k < n4; k += 64) *reinterpret_cast<float4*>(part + 4 * k) = z;
+    auto fix_row = [&](int r, int slot) {   // rows below the image: zeros (wave-uniform)
+        if (r >= Hi) mrow_clear_row(img + slot * IMG_F + 2 * xo0 * PS, lane, npx * QP);
     };
     // the zero column right of the last input pixel: never written afterwards
     if (strip == 0 && lane < QP) {
@@ -196,20 +180,7 @@ __global__ __launch_bounds__(K::NF * K::NWV * 64, 2) void ms2_kernel(Ms2Args a) 
     dwg_barrier();
     asm volatile("" ::: "memory");
     float tap[K::TAPL ? 1 : CK][9];
-    if constexpr (!K::TAPL) {
-        const float4* tp = reinterpret_cast<const float4*>(wgc + K::OFF_TAP) + kq * 3;
-#pragma unroll
-        for (int ks = 0; ks < CK; ks++) {
-            const float4 t0 = tp[ks * 12], t1 = tp[ks * 12 + 1], t2 = tp[ks * 12 + 2];
-            tap[ks][0] = t0.x; tap[ks][1] = t0.y; tap[ks][2] = t0.z; tap[ks][3] = t0.w;
-            tap[ks][4] = t1.x; tap[ks][5] = t1.y; tap[ks][6] = t1.z; tap[ks][7] = t1.w;
-            tap[ks][8] = t2.x;
-        }
-#pragma unroll
-        for (int ks = 0; ks < CK; ks++)
-#pragma unroll
-            for (int t = 0; t < 9; t++) asm volatile("" : "+v"(tap[ks][t]));
-    }
+    if constexpr (!K::TAPL) mrow_load_taps9<CK>(reinterpret_cast<const float4*>(wgc + K::OFF_TAP) + kq * 3, tap);
     // ---- per-lane addresses (a lane whose output pixel lies right of the frame works on the last real one and stores nothing)
     typedef __attribute__((address_space(3))) float lfloat;
     const int xo = min(xo0 + p, WO - 1);
@@ -240,22 +211,13 @@ __global__ __launch_bounds__(K::NF * K::NWV * 64, 2) void ms2_kernel(Ms2Args a) 
             D[mt] = df32x4{bs.x + m.x, bs.y + m.y, bs.z + m.z, bs.w + m.w};
         }
     };
-    typedef __attribute__((address_space(1))) char gchar;
-    typedef __attribute__((address_space(1))) df32x4 gf32x4;
-    auto epilogue = [&](int y) {
+    auto epilogue = [&](int y) {   // (one tile per wave: only live pixels and real channels are stored)
         gchar* dst = (gchar*)(a.out + (long)b * a.out_fs + (long)y * WO * CO);
         asm volatile("" : "+s"(dst));
 #pragma unroll
         for (int mt = 0; mt < MT; mt++) {
-            float4 sl = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!RELU) sl = *reinterpret_cast<const float4*>(wgc + K::OFF_SLOPE + 16 * mt + 4 * kq);
-            df32x4 v = D[mt];
-            if (RELU) {
-                v = df32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-            } else {
-                v = df32x4{fminf(fmaxf(v.x, 0.f) + sl.x * fminf(v.x, 0.f), a.hi), fminf(fmaxf(v.y, 0.f) + sl.y * fminf(v.y, 0.f), a.hi),
-                           fminf(fmaxf(v.z, 0.f) + sl.z * fminf(v.z, 0.f), a.hi), fminf(fmaxf(v.w, 0.f) + sl.w * fminf(v.w, 0.f), a.hi)};
-            }
+            const float4 sl = mrow_slope<RELU>(wgc + K::OFF_SLOPE + 16 * mt + 4 * kq);
+            const df32x4 v = mrow_act<RELU>(D[mt], sl, a.hi);
             if (live && 16 * mt + 4 * kq < CO) *(gf32x4*)(dst + ooff + (unsigned)(16 * mt * 4)) = v;
         }
     };
@@ -297,22 +259,9 @@ template <class K>
 void ms2_pack(const float* w_dw, const float* b_dw, const float* w_pw, const float* bias, const float* alpha, int act, float* dst) {
     constexpr int C = K::C, CO = K::CO;
     std::fill(dst, dst + K::TOTAL, 0.f);
-    for (int ks = 0; ks < K::CK; ks++)
-        for (int mt = 0; mt < K::MT; mt++)
-            for (int l = 0; l < 64; l++) {
-                const int o = 16 * mt + (l & 15);
-                if (o < CO) dst[K::OFF_A + (ks * K::MT + mt) * 64 + l] = w_pw[(size_t)o * C + 4 * ks + (l >> 4)];
-            }
-    for (int ks = 0; ks < K::CK; ks++)
-        for (int kq = 0; kq < 4; kq++)
-            for (int t = 0; t < 9; t++) dst[K::OFF_TAP + (ks * 4 + kq) * 12 + t] = w_dw[t * C + 4 * ks + kq];
-    for (int c = 0; c < CO; c++) {
-        double acc = bias ? bias[c] : 0.0;
-        if (b_dw)
-            for (int k = 0; k < C; k++) acc += (double)w_pw[(size_t)c * C + k] * b_dw[k];
-        dst[K::OFF_BIAS + c] = (float)acc;
-        dst[K::OFF_SLOPE + c] = act == ACT_PRELU ? alpha[c] : (act == ACT_NONE ? 1.f : 0.f);
-    }
+    mrow_pack_a(dst + K::OFF_A, w_pw, K::CK, K::MT, CO);
+    mrow_pack_taps(dst + K::OFF_TAP, w_dw, K::CK);
+    mrow_pack_bias(dst + K::OFF_BIAS, dst + K::OFF_SLOPE, CO, C, w_pw, b_dw, bias, alpha, act);
 }
 
 template <class K>
@@ -332,14 +281,7 @@ int ms2_launch(const BlockArgs& a, hipStream_t s) {
     ma.bands = (a.Ho + rows - 1) / rows;
     const dim3 grid((unsigned)((long)groups * ma.bands));
     const size_t lds_bytes = (size_t)K::LDS_F * 4;
-    if (a.ep.act == ACT_RELU) {
-        auto kern = ms2_kernel<K, true>;
-        if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-        return (int)launch_kernel(kern, grid, dim3(K::NF * K::NWV * 64), lds_bytes, s, ma);
-    }
-    auto kern = ms2_kernel<K, false>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, grid, dim3(K::NF * K::NWV * 64), lds_bytes, s, ma);
+    return mrow_launch(ms2_kernel<K, true>, ms2_kernel<K, false>, a.ep.act == ACT_RELU, grid, dim3(K::NF * K::NWV * 64), lds_bytes, s, ma);
 }
 
 // 0: none; 1: 48 wide 32 -> 64 with the max-pool skip; 2: 96 wide 32 -> 12, no skip; 3: 48 wide 64 -> 24, no skip; 4: 96 wide 16 -> 32 with the skip  (W = INPUT width)

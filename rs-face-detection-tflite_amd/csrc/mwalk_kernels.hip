@@ -83,47 +83,13 @@ __global__ __launch_bounds__(256, 2) void mwalk_kernel(MwalkArgs a) {
     const int y0 = band * a.band_rows, y1 = min(y0 + a.band_rows, a.H);
     const float* in = a.in + (long)b * a.in_fs;
 
-    // ---- LDS-DMA of one input row: instruction k brings in pixels [DPX k, DPX k + DPX): lane -> (pixel lane / QP, quad
-    // min(lane % QP, CK - 1)), lanes >= DPX * QP idle; the immediate offset moves source and destination alike, M0 makes up the
-    // difference between the image's pixel stride and the tensor's
-    const int goff = ((lane / QP) * C + 4 * min(lane % QP, CK - 1)) * 4;
+    // ---- LDS-DMA of one input row (clamped to the frame; mrow_dma2) into image bi
+    const int goff = mrow_goff<CK>(lane);
     const unsigned lds_img = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)img);
     auto issue_row = [&](int r, int bi) {
-        const char* src = reinterpret_cast<const char*>(in + (long)min(max(r, 0), a.H - 1) * W * C);
-        const char* src1 = src + (NLD / 2) * K::DPX * C * 4;
-        const unsigned dstb = lds_img + (unsigned)((bi * IMG_F + PS) * 4);
-        unsigned long long saved;
-#define MI_MW_DMA(base, k) "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, " base " offset:" #k "*%8\n\t"
-        asm volatile("s_mov_b64 %0, exec\n\ts_mov_b32 exec_lo, -1\n\ts_mov_b32 exec_hi, %6\n\t"
-                     "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %1\n\t"
-                     MI_MW_DMA("%1", 1) MI_MW_DMA("%1", 2) MI_MW_DMA("%1", 3)
-                     "s_add_u32 m0, m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %2\n\t"
-                     MI_MW_DMA("%2", 1) MI_MW_DMA("%2", 2) MI_MW_DMA("%2", 3)
-                     "s_mov_b64 exec, %0"
-                     : "=&s"(saved)
-                     : "s"(src), "s"(src1), "v"(goff), "s"(dstb), "n"((NLD / 2) * K::DPX * PS * 4 - (NLD / 2 - 1) * K::DPX * (PS - C) * 4),
-                       "n"((1u << (K::ACTIVE - 32)) - 1), "n"(K::DPX * (PS - C) * 4), "n"(K::DPX * C * 4)
-                     : "memory", "scc", "m0");
-#undef MI_MW_DMA
+        mrow_dma2<C, PS, K::DPX, K::ACTIVE>(reinterpret_cast<const char*>(in + (long)min(max(r, 0), a.H - 1) * W * C), lds_img + (unsigned)((bi * IMG_F + PS) * 4), goff);
     };
-    // rows outside the image are zero padding: the landed (clamped) row is cleared before it is read
-    auto fix_row = [&](int r, int bi) {
-        if (r >= 0 && r < a.H) return;  // wave-uniform
-        float zz = 0.f;
-        asm volatile("" : "+v"(zz));
-        const float4 z = make_float4(zz, zz, zz, zz);
-        float* part = img + bi * IMG_F + PS;
-        constexpr int N4 = W * QP;
-#pragma unroll
-        for (int k = 0; k < (N4 + 63) / 64; k++)
-            if (64 * (k + 1) <= N4 || lane < N4 - 64 * k) *reinterpret_cast<float4*>(part + 4 * (lane + 64 * k)) = z;
-    };
-    // border pixel columns (left of x = 0, right of x = W - 1) are never written by the DMA: cleared once
-    if (lane < 2 * QP) {
-        const int col = lane / QP, qd = lane - col * QP;
-#pragma unroll
-        for (int bi = 0; bi < NBUF; bi++) *reinterpret_cast<float4*>(img + bi * IMG_F + col * (W + 1) * PS + 4 * qd) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    mrow_clear_border<QP, NBUF, IMG_F, (W + 1) * PS>(img, lane);   // left of x = 0, right of x = W - 1
 
     // the first row is on its way while the constants are fetched; the second goes out behind them, and only it may still be in flight
     // when the row loop starts (vector-memory operations retire in issue order; the loop's counted waits assume nothing else is outstanding)
@@ -148,74 +114,21 @@ __global__ __launch_bounds__(256, 2) void mwalk_kernel(MwalkArgs a) {
 #pragma unroll
     for (int ks = 0; ks < CK; ks++) { accA[ks].clear(); accB[ks].clear(); }
     df32x4 D[MT][WT];
-    // D <- bias + skip for the output row whose centre input row sits in image bi
-    auto init_D = [&](int bi) {
-        float4 bs[MT], x[MT][WT];
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) bs[mt] = *reinterpret_cast<const float4*>(wgc + K::OFF_BIAS + 16 * mt + 4 * kq);
-        if (a.has_res) {  // wave-uniform; one branch around all the reads
-#pragma unroll
-            for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-                for (int nt = 0; nt < WT; nt++) {
-                    x[mt][nt] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (16 * mt < C) x[mt][nt] = *reinterpret_cast<const float4*>(sme + bi * IMG_F + 16 * nt * PS + 16 * mt);
-                }
-#pragma unroll
-            for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-                for (int nt = 0; nt < WT; nt++) D[mt][nt] = df32x4{x[mt][nt].x + bs[mt].x, x[mt][nt].y + bs[mt].y, x[mt][nt].z + bs[mt].z, x[mt][nt].w + bs[mt].w};
-        } else {
-#pragma unroll
-            for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-                for (int nt = 0; nt < WT; nt++) D[mt][nt] = df32x4{bs[mt].x, bs[mt].y, bs[mt].z, bs[mt].w};
-        }
-    };
-    typedef __attribute__((address_space(1))) char gchar;
-    typedef __attribute__((address_space(1))) df32x4 gf32x4;
-    auto epilogue = [&](int y) {
-        gchar* dst = (gchar*)(a.out + (long)b * a.out_fs + (long)y * W * Co);
-        asm volatile("" : "+s"(dst));
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) {
-            float4 sl = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!RELU) sl = *reinterpret_cast<const float4*>(wgc + K::OFF_SLOPE + 16 * mt + 4 * kq);
-#pragma unroll
-            for (int nt = 0; nt < WT; nt++) {
-                df32x4 v = D[mt][nt];
-                if (RELU) {
-                    v = df32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-                } else {  // act(v) = min(max(v,0) + slope*min(v,0), hi): ReLU (slope 0), PReLU (alpha), none (1), ReLU6 (hi = 6)
-                    v = df32x4{fminf(fmaxf(v.x, 0.f) + sl.x * fminf(v.x, 0.f), a.hi), fminf(fmaxf(v.y, 0.f) + sl.y * fminf(v.y, 0.f), a.hi),
-                               fminf(fmaxf(v.z, 0.f) + sl.z * fminf(v.z, 0.f), a.hi), fminf(fmaxf(v.w, 0.f) + sl.w * fminf(v.w, 0.f), a.hi)};
-                }
-                if (16 * (nt + 1) <= W || 16 * nt + p < W) *(gf32x4*)(dst + ooff + (unsigned)((16 * nt * Co + 16 * mt) * 4)) = v;   // (a partly used last tile)
-            }
-        }
-    };
-
-    // vmcnt bookkeeping: vector-memory operations retire in issue order.  A step's operations: the stores of its output row (NST, from
-    // the third step on), then the DMA of the row two steps ahead (NLD, while the band has one).  "Row r has landed" = at most what was
-    // issued behind its DMA is outstanding: the previous step's stores and DMA.
+    // A step's vector-memory operations: the stores of its output row (NST, from the third step on), then the DMA of the row two steps
+    // ahead (NLD, while the band has one): mrow_wait
     constexpr int NST = MT * WT;
-    auto wait_row = [&](int t) {  // t = step number (row y0 - 1 + t)
-        const bool st = t - 1 >= 2, dm = t == 0 || (t - 1) + 2 <= (y1 - y0 + 1);  // step 0: the prologue's second row is behind it
-        if (st && dm) wait_vm<NST + NLD>();
-        else if (dm) wait_vm<NLD>();
-        else if (st) wait_vm<NST>();
-        else wait_vm<0>();
-    };
     auto step = [&](auto emit, int r, RowAcc<WT> (&aPN)[CK], RowAcc<WT> (&aC)[CK]) {
         const int t = r - (y0 - 1), bi = t & 1;
-        wait_row(t);
-        fix_row(r, bi);
+        mrow_wait<NST, NLD>(t - 1 >= 2, t == 0 || (t - 1) + 2 <= (y1 - y0 + 1));  // t = step number; step 0: the prologue's second row is behind it
+        if (r < 0 || r >= a.H) mrow_clear_row<W * QP>(img + bi * IMG_F + PS, lane);  // wave-uniform
         wave_sync();
         mdb_row<CK, MT, WT, PS, decltype(emit)::value, K::TAPL>(x_lds + (unsigned)(bi * IMG_F * 4), a_lds, tap, aPN, aC, D, reinterpret_cast<const float4*>(wgc + K::OFF_TAP) + kq * 3);
         __builtin_amdgcn_sched_barrier(0);  // (fences: the old and the new accumulator tiles are never live together)
-        if constexpr (decltype(emit)::value) epilogue(r - 1);
+        if constexpr (decltype(emit)::value)   // (a partly used last tile stores its pixels < W only)
+            mrow_store_row<RELU, Co, W>(D, (gchar*)(a.out + (long)b * a.out_fs + (long)(r - 1) * W * Co), ooff, wgc + K::OFF_SLOPE + 4 * kq, a.hi, p);
         __builtin_amdgcn_sched_barrier(0);
-        init_D(bi);     // output row r starts from bias + its skip, the centre pixels of input row r
+        // output row r starts from bias + its skip, the centre pixels of input row r
+        mrow_init_acc<C, PS>(D, wgc + K::OFF_BIAS + 4 * kq, sme + bi * IMG_F, a.has_res != 0);
         __builtin_amdgcn_sched_barrier(0);
         wave_sync();   // every read of image bi is issued before the DMA below overwrites it
         __builtin_amdgcn_s_waitcnt(0xC07F);  // ... and has returned (LDS-DMA writes are not ordered behind this wave's earlier reads)
@@ -237,22 +150,9 @@ template <class K>
 void mw_pack(const float* w_dw, const float* b_dw, const float* w_pw, const float* bias, const float* alpha, int act, float* dst) {
     constexpr int C = K::C, Co = K::Co;
     std::fill(dst, dst + K::TOTAL, 0.f);
-    // A operand of v_mfma_f32_16x16x4_f32 for (k-step ks, output tile mt): lane l holds W[16 mt + l % 16][4 ks + l / 16]
-    for (int ks = 0; ks < K::CK; ks++)
-        for (int mt = 0; mt < K::MT; mt++)
-            for (int l = 0; l < 64; l++) dst[K::OFF_A + (ks * K::MT + mt) * 64 + l] = w_pw[(size_t)(16 * mt + (l & 15)) * C + 4 * ks + (l >> 4)];
-    // taps [ks][kq][12]: the nine taps of channel 4 ks + kq (three float4 loads per k-step)
-    for (int ks = 0; ks < K::CK; ks++)
-        for (int kq = 0; kq < 4; kq++)
-            for (int t = 0; t < 9; t++) dst[K::OFF_TAP + (ks * 4 + kq) * 12 + t] = w_dw[t * C + 4 * ks + kq];
-    for (int c = 0; c < Co; c++) {
-        // PW(dw + b_dw) + b_pw = PW(dw) + (W b_dw + b_pw): the depthwise bias is folded into the pointwise bias
-        double acc = bias ? bias[c] : 0.0;
-        if (b_dw)
-            for (int k = 0; k < C; k++) acc += (double)w_pw[(size_t)c * C + k] * b_dw[k];
-        dst[K::OFF_BIAS + c] = (float)acc;
-        dst[K::OFF_SLOPE + c] = act == ACT_PRELU ? alpha[c] : (act == ACT_NONE ? 1.f : 0.f);
-    }
+    mrow_pack_a(dst + K::OFF_A, w_pw, K::CK, K::MT, Co);
+    mrow_pack_taps(dst + K::OFF_TAP, w_dw, K::CK);
+    mrow_pack_bias(dst + K::OFF_BIAS, dst + K::OFF_SLOPE, Co, C, w_pw, b_dw, bias, alpha, act);
 }
 
 template <class K>
@@ -273,14 +173,7 @@ int mw_launch(const BlockArgs& a, hipStream_t s) {
     const long units = (long)a.B * ma.bands;
     const size_t lds_bytes = (size_t)K::LDS_F * 4;
     const dim3 grid((unsigned)((units + 3) / 4));
-    if (a.ep.act == ACT_RELU) {
-        auto kern = mwalk_kernel<K, true>;
-        if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-        return (int)launch_kernel(kern, grid, dim3(256), lds_bytes, s, ma);
-    }
-    auto kern = mwalk_kernel<K, false>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, grid, dim3(256), lds_bytes, s, ma);
+    return mrow_launch(mwalk_kernel<K, true>, mwalk_kernel<K, false>, a.ep.act == ACT_RELU, grid, dim3(256), lds_bytes, s, ma);
 }
 
 }  // namespace
