@@ -40,6 +40,7 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
 
 namespace mi {
 
@@ -66,13 +67,13 @@ __device__ __forceinline__ unsigned poll(const unsigned* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// n / d for 0 <= n < 2^16 through d's magic number m = ceil(2^32 / d) (0 stands for d = 1)
-__device__ __forceinline__ int mdiv(int n, unsigned m) { return m ? (int)__umulhi((unsigned)n, m) : n; }
+// The depthwise chunk, the activation and the 2x2 max below work on f32x4 register vectors (the kernels sit at their register limits,
+// tests/test_isa_checks.py), not on float4: they stay written out; from mfma32.hpp come magic_div (here: 0 <= n < 2^16) and the stamp.
 
 #ifdef MI_BAND_STAMPS
 // diagnostic builds only (tools/band_stamps.py): 10 s_memtime stamps per (workgroup of frame 0, stage)
 unsigned long long* g_band_stamps = nullptr;
-#define MI_BAND_STAMP(k) if (a.stamps && f == 0 && tid == 0) { __builtin_amdgcn_sched_barrier(0); a.stamps[((long)w * 64 + s) * 10 + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+#define MI_BAND_STAMP(k) if (a.stamps && f == 0 && tid == 0) MI_STAMP_AT(a.stamps[((long)w * 64 + s) * 10 + (k)])
 #else
 #define MI_BAND_STAMP(k)
 #endif
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void bandnet_kernel(BandLaunch a) {
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int i = tid + u * kThreads, ic = min(i, total - 1);
-                const int hr = mdiv(ic, st.mrowq), e = ic - hr * rowq, px = mdiv(e, st.mC4), q = e - px * C4;
+                const int hr = magic_div(ic, st.mrowq), e = ic - hr * rowq, px = magic_div(e, st.mC4), q = e - px * C4;
                 const int y = hr < nA ? ya + hr : p0 + Rin + (hr - nA);
                 dsto[u] = i < total ? ((y - p0 + 1) * TW + px + 1) * Cs + 4 * q : -1;
                 real[u] = i < total && y >= 0 && y < st.H;
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(kThreads) void bandnet_kernel(BandLaunch a) {
             // the program's input: plain memory, complete before the launch
             const float* src = a.base[st.src_base] + st.src_off + (long)f * st.src_fs;
             for (int i = tid; i < total; i += kThreads) {
-                const int hr = mdiv(i, st.mrowq), e = i - hr * rowq, px = mdiv(e, st.mC4), q = e - px * C4;
+                const int hr = magic_div(i, st.mrowq), e = i - hr * rowq, px = magic_div(e, st.mC4), q = e - px * C4;
                 const int y = hr < nA ? ya + hr : p0 + Rin + (hr - nA);
                 f32x4 v = zero4;
                 if (y >= 0 && y < st.H) v = *reinterpret_cast<const f32x4*>(src + ((long)y * W + px) * C + 4 * q);
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(kThreads) void bandnet_kernel(BandLaunch a) {
                 const float* wdw = a.consts + st.w_c + 32 * nct;
                 const float* bdw = wdw + 9 * C;
                 for (int i = tid; i < npx * C4; i += kThreads) {
-                    const int px = mdiv(i, st.mC4), q = i - px * C4, oy = mdiv(px, st.mWo), ox = px - oy * Wo;
+                    const int px = magic_div(i, st.mC4), q = i - px * C4, oy = magic_div(px, st.mWo), ox = px - oy * Wo;
                     const float* t = tile + ((trow + S * oy) * TW + S * ox + (S - 1 - pre)) * Cs + 4 * q;
                     f32x4 k[9];
 #pragma unroll
@@ -370,7 +371,7 @@ __global__ __launch_bounds__(kThreads) void bandnet_kernel(BandLaunch a) {
             const float* wdw = lC + 32 * nct;
             const float* bdw = wdw + 9 * C;
             for (int i = tid; i < npx * C4; i += kThreads) {
-                const int px = mdiv(i, st.mC4), q = i - px * C4, oy = mdiv(px, st.mWo), ox = px - oy * Wo;
+                const int px = magic_div(i, st.mC4), q = i - px * C4, oy = magic_div(px, st.mWo), ox = px - oy * Wo;
                 const float* t = tile + ((trow + S * oy) * TW + S * ox + (S - 1 - pre)) * Cs + 4 * q;
                 f32x4 acc = *reinterpret_cast<const f32x4*>(bdw + 4 * q);
 #pragma unroll
@@ -409,7 +410,7 @@ __global__ __launch_bounds__(kThreads) void bandnet_kernel(BandLaunch a) {
               for (int ct = myct; ct < (WIDE ? nct : myct + 1); ct += kThreads / 64) {   // (one turn unless the stage has more than eight output tiles — wpc == 1 then —: no loop at all outside the WIDE instantiation)
                 for (int pt = mypt; pt < npt; pt += wpc) {
                     const int px = 16 * pt + n, pxc = min(px, npx - 1);
-                    const int oy = mdiv(pxc, st.mWo), ox = pxc - oy * Wo;
+                    const int oy = magic_div(pxc, st.mWo), ox = pxc - oy * Wo;
                     const float* bp = blk ? dwb + pxc * Cs : tile + ((1 + oy) * TW + ox + 1) * Cs;
                     // four accumulators, one per k-step of a 16-channel chunk: a chain of dependent MFMAs runs at a quarter of the issue rate
                     f32x4 D = zero4, D1 = zero4, D2 = zero4, D3 = zero4;
@@ -628,18 +629,17 @@ bool bandnet_pack(const BandStage& st, BandPacked* out) {
 }
 
 int launch_bandnet(const BandLaunch& a, void* stream) {
-    if (a.nstages < 1 || a.nstages > 63 || a.NW < 1 || a.F < 1 || a.lds_bytes > 160 * 1024 || a.tiles_floats < 0 || (a.tiles_floats & 3)) return (int)hipErrorInvalidValue;
+    if (a.nstages < 1 || a.nstages > 63 || a.NW < 1 || a.F < 1 || a.lds_bytes > kLdsBytes || a.tiles_floats < 0 || (a.tiles_floats & 3)) return (int)hipErrorInvalidValue;
     if (bandnet_lds_bytes(a.tiles_floats, a.dw_floats, a.nstages) > a.lds_bytes) return (int)hipErrorInvalidValue;
     if ((long)a.NW * a.F > device_cu_count()) return (int)hipErrorInvalidValue;   // every workgroup must be resident: one per CU
     auto kern = a.wide ? bandnet_kernel<false, false, true> : (a.cv2 ? bandnet_kernel<true, false, false> : (a.xb ? bandnet_kernel<false, true, false> : bandnet_kernel<false, false, false>));
     if ((a.cv2 && a.xb) || (a.wide && (a.cv2 || a.xb))) return (int)hipErrorInvalidValue;   // (no such program: the planner does not build one)
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
 #ifdef MI_BAND_STAMPS
     BandLaunch b = a;
     b.stamps = g_band_stamps;
-    return (int)launch_kernel(kern, dim3((unsigned)a.NW, (unsigned)a.F), dim3(kThreads), (size_t)a.lds_bytes, (hipStream_t)stream, b);
+    return launch_full_lds(kern, dim3((unsigned)a.NW, (unsigned)a.F), dim3(kThreads), (size_t)a.lds_bytes, (hipStream_t)stream, b);
 #else
-    return (int)launch_kernel(kern, dim3((unsigned)a.NW, (unsigned)a.F), dim3(kThreads), (size_t)a.lds_bytes, (hipStream_t)stream, a);
+    return launch_full_lds(kern, dim3((unsigned)a.NW, (unsigned)a.F), dim3(kThreads), (size_t)a.lds_bytes, (hipStream_t)stream, a);
 #endif
 }
 

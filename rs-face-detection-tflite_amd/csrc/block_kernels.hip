@@ -35,16 +35,14 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
 
 namespace mi {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
 constexpr int kPrefetch = 8;          // float4 registers per thread for the next step's rows
 constexpr int kALdsMax = 40 * 1024;   // pointwise weights are staged in LDS when they fit in this many bytes
-static int cu_count() { return device_cu_count(); }  // launch.hpp: per device
 
 int lds_budget() {
     static const int v = getenv("MI_BLOCK_LDS") ? atoi(getenv("MI_BLOCK_LDS")) : 80 * 1024;  // tuning aid
@@ -68,12 +66,6 @@ struct BlockGeom {
     int nsplit, wmod, mt_per;  // mt_per: tiles per (workgroup, tile share)
     unsigned long long* stamps;  // diagnostic builds only (MI_BLOCK_STAMPS): 8 accumulators per wave
 };
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 max4(float4 a, float4 b, float4 c, float4 d) {
-    return make_float4(fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x)), fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y)),
-                       fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z)), fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w)));
-}
 
 __device__ __forceinline__ float4 res_from_global(const Epilogue& ep, int b, int oy, int ox, int Wo, int ch) {
     // generic float4 skip read (channels ch..ch+3 < res_C guaranteed by the caller)
@@ -295,10 +287,7 @@ __global__ __launch_bounds__(256, (SLOW && MTG <= 2) ? 2 : 1) void block_kernel(
                         for (int kx = 0; kx < 3; kx++)
 #pragma unroll
                             for (int p = 0; p < PG; p++) {
-                                bf[p].x = fmaf(dq[p][kx].x, wq[kx].x, bf[p].x);
-                                bf[p].y = fmaf(dq[p][kx].y, wq[kx].y, bf[p].y);
-                                bf[p].z = fmaf(dq[p][kx].z, wq[kx].z, bf[p].z);
-                                bf[p].w = fmaf(dq[p][kx].w, wq[kx].w, bf[p].w);
+                                fma4(dq[p][kx], wq[kx], bf[p]);
                             }
                         if (ky < 2) {
 #pragma unroll
@@ -311,7 +300,7 @@ __global__ __launch_bounds__(256, (SLOW && MTG <= 2) ? 2 : 1) void block_kernel(
                     }
                     float4 bb = ld4(bdw + h * g.Ch + 4 * j);
 #pragma unroll
-                    for (int p = 0; p < PG; p++) { bf[p].x += bb.x; bf[p].y += bb.y; bf[p].z += bb.z; bf[p].w += bb.w; }
+                    for (int p = 0; p < PG; p++) bf[p] = add4(bf[p], bb);
                 } else {
 #pragma unroll
                     for (int p = 0; p < PG; p++) bf[p] = ld4(tile + base[p][0] + 4 * j);
@@ -319,12 +308,7 @@ __global__ __launch_bounds__(256, (SLOW && MTG <= 2) ? 2 : 1) void block_kernel(
 #pragma unroll
                 for (int m = 0; m < MTG; m++) {
 #pragma unroll
-                    for (int p = 0; p < PG; p++) {
-                        D[p][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].x, bf[p].x, D[p][m], 0, 0, 0);
-                        D[p][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].y, bf[p].y, D[p][m], 0, 0, 0);
-                        D[p][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].z, bf[p].z, D[p][m], 0, 0, 0);
-                        D[p][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].w, bf[p].w, D[p][m], 0, 0, 0);
-                    }
+                    for (int p = 0; p < PG; p++) mfma32_quad(av[m], bf[p], D[p][m]);
                 }
             }
             } else {
@@ -346,15 +330,12 @@ __global__ __launch_bounds__(256, (SLOW && MTG <= 2) ? 2 : 1) void block_kernel(
 #pragma unroll
                                 for (int p = 0; p < PG; p++) {
                                     const float4 d = ld4(tile + base[p][ky] + kx * g.PS + 4 * j);
-                                    bf[p].x = fmaf(d.x, w.x, bf[p].x);
-                                    bf[p].y = fmaf(d.y, w.y, bf[p].y);
-                                    bf[p].z = fmaf(d.z, w.z, bf[p].z);
-                                    bf[p].w = fmaf(d.w, w.w, bf[p].w);
+                                    fma4(d, w, bf[p]);
                                 }
                             }
                         const float4 bb = ld4(bdw + h * g.Ch + 4 * j);
 #pragma unroll
-                        for (int p = 0; p < PG; p++) { bf[p].x += bb.x; bf[p].y += bb.y; bf[p].z += bb.z; bf[p].w += bb.w; }
+                        for (int p = 0; p < PG; p++) bf[p] = add4(bf[p], bb);
                     } else {
 #pragma unroll
                         for (int p = 0; p < PG; p++) bf[p] = ld4(tile + base[p][0] + 4 * j);
@@ -372,12 +353,7 @@ __global__ __launch_bounds__(256, (SLOW && MTG <= 2) ? 2 : 1) void block_kernel(
 #pragma unroll
                     for (int m = 0; m < MTG; m++)
 #pragma unroll
-                        for (int p = 0; p < PG; p++) {
-                            D[p][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].x, bf[p].x, D[p][m], 0, 0, 0);
-                            D[p][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].y, bf[p].y, D[p][m], 0, 0, 0);
-                            D[p][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].z, bf[p].z, D[p][m], 0, 0, 0);
-                            D[p][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].w, bf[p].w, D[p][m], 0, 0, 0);
-                        }
+                        for (int p = 0; p < PG; p++) mfma32_quad(av[m], bf[p], D[p][m]);
                 };
                 float4 bf[PG], av[MTG];
                 dw_chunk(0, bf);
@@ -426,7 +402,7 @@ __global__ __launch_bounds__(256, (SLOW && MTG <= 2) ? 2 : 1) void block_kernel(
 #pragma unroll
                     for (int p = 0; p < PG; p++) {
                         if (!valid[p]) continue;
-                        float4 v = make_float4(D[p][m][4 * gq] + bb.x, D[p][m][4 * gq + 1] + bb.y, D[p][m][4 * gq + 2] + bb.z, D[p][m][4 * gq + 3] + bb.w);
+                        float4 v = add4(quad4(D[p][m], gq), bb);
                         float4 rva = make_float4(0.f, 0.f, 0.f, 0.f);  // skip that joins behind the activation (Epilogue::res_after)
                         if (has_res) {
                             float4 rv;
@@ -435,14 +411,10 @@ __global__ __launch_bounds__(256, (SLOW && MTG <= 2) ? 2 : 1) void block_kernel(
                             else if (SLOW) rv = rvq[SLOW ? p : 0][SLOW ? m : 0][gq];
                             else rv = make_float4(0.f, 0.f, 0.f, 0.f);
                             if (a.ep.res_after) rva = rv;
-                            else { v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w; }
+                            else v = add4(v, rv);
                         }
                         // act(v) = min(max(v,0) + slope*min(v,0), hi): ReLU (slope 0), PReLU (alpha), none (1), ReLU6 (hi = 6)
-                        v.x = fminf(fmaxf(v.x, 0.f) + al.x * fminf(v.x, 0.f), hi);
-                        v.y = fminf(fmaxf(v.y, 0.f) + al.y * fminf(v.y, 0.f), hi);
-                        v.z = fminf(fmaxf(v.z, 0.f) + al.z * fminf(v.z, 0.f), hi);
-                        v.w = fminf(fmaxf(v.w, 0.f) + al.w * fminf(v.w, 0.f), hi);
-                        v.x += rva.x; v.y += rva.y; v.z += rva.z; v.w += rva.w;
+                        v = add4(act4(v, al, hi), rva);
                         *reinterpret_cast<float4*>(op[p] + ch) = v;  // plain store: the 3 x 16 B pieces of a pixel merge in L2 (nontemporal stores measured 2.3x slower)
                     }
                 }
@@ -503,7 +475,7 @@ bool make_geom_pg(const BlockArgs& a, int PG, BlockGeom* out) {
     // block_kernel launches 0.260 -> 0.226 ms; 16 pixels: 0.217, 64: 0.242).  The arithmetic of a pixel does not depend on the band it is in.
     static const int rcap_px = getenv("MI_BLOCK_RCAP_PX") ? atoi(getenv("MI_BLOCK_RCAP_PX")) : 32;  // tuning aid (0: off)
     int Rfull = std::max(1, std::min(a.Ho, (128 * PG) / a.Wo));  // rows that fill every lane of the 4 waves
-    if (rcap_px > 0 && (long)a.B * ((a.Ho + Rfull - 1) / Rfull) * 8 <= cu_count()) Rfull = std::max(1, std::min(Rfull, rcap_px / a.Wo));
+    if (rcap_px > 0 && (long)a.B * ((a.Ho + Rfull - 1) / Rfull) * 8 <= device_cu_count()) Rfull = std::max(1, std::min(Rfull, rcap_px / a.Wo));
     int R = Rfull;
     while (R > 1 && (lds_for(R) > lds_budget() || !pf_ok(R))) R--;
     if (R * a.Wo * 4 < 128 * PG * 3) {  // step under 75% full: small, channel-heavy layer -> spend the whole LDS of a CU on one workgroup
@@ -534,9 +506,9 @@ bool make_geom_pg(const BlockArgs& a, int PG, BlockGeom* out) {
     g.lds_bytes = off * 4;
     // bands: about one resident wave of workgroups over the chip (prologue + halo paid once per band)
     static const int max_per_cu = getenv("MI_BLOCK_PERCU") ? atoi(getenv("MI_BLOCK_PERCU")) : 2;  // tuning aid
-    const int per_cu = std::max(1, std::min(max_per_cu, (160 * 1024) / g.lds_bytes));
+    const int per_cu = std::max(1, std::min(max_per_cu, kLdsBytes / g.lds_bytes));
     const int max_bands = (a.Ho + R - 1) / R;
-    int bands = std::min(max_bands, std::max(1, (cu_count() * per_cu + a.B / 2) / std::max(1, a.B)));
+    int bands = std::min(max_bands, std::max(1, (device_cu_count() * per_cu + a.B / 2) / std::max(1, a.B)));
     g.band = single_step ? R : ((a.Ho + bands - 1) / bands + R - 1) / R * R;
     g.bands = (a.Ho + g.band - 1) / g.band;
     g.nsplit = 1; g.wmod = 4; g.mt_per = g.MT;
@@ -544,9 +516,9 @@ bool make_geom_pg(const BlockArgs& a, int PG, BlockGeom* out) {
         static const int no_split = getenv("MI_BLOCK_NOSPLIT") ? atoi(getenv("MI_BLOCK_NOSPLIT")) : 0;  // tuning aid
         const long wgs = (long)a.B * g.bands;
         const int groups = (std::min(R, a.Ho) * a.Wo + 32 * PG - 1) / (32 * PG);  // waves of a step that have pixels
-        if (!no_split && g.MT >= 2 && wgs * 2 <= cu_count()) {
+        if (!no_split && g.MT >= 2 && wgs * 2 <= device_cu_count()) {
             const int wmod = groups <= 1 ? 1 : (groups == 2 ? 2 : 4), wdiv = 4 / wmod;
-            int nsplit = (int)std::min<long>((2L * cu_count() + wgs - 1) / wgs, (g.MT + wdiv - 1) / wdiv);
+            int nsplit = (int)std::min<long>((2L * device_cu_count() + wgs - 1) / wgs, (g.MT + wdiv - 1) / wdiv);
             nsplit = std::max(1, nsplit);
             const int per = (g.MT + nsplit * wdiv - 1) / (nsplit * wdiv);
             nsplit = (g.MT + per * wdiv - 1) / (per * wdiv);
@@ -560,7 +532,6 @@ bool make_geom_pg(const BlockArgs& a, int PG, BlockGeom* out) {
         if (a.ep.res_mode == RES_MAXPOOL && S == 2 && a.has_dw && a.pt == 0 && a.pl == 0 && a.H == 2 * a.Ho && a.W == 2 * a.Wo) g.res_lds = 1;
     }
     if (a.ep.res_mode != RES_NONE && a.ep.res_C % 4) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!aligned16(a.in) || !aligned16(a.out) || (a.in_fs & 3) || (a.out_fs & 3)) return false;
     if (a.ep.res && (!aligned16(a.ep.res) || (a.ep.res_fs & 3))) return false;
     *out = g;
@@ -584,9 +555,7 @@ bool make_geom(const BlockArgs& a, BlockGeom* out) {
 
 template <int MTG, int S, int KS, int PG, bool SLOW, int CPT, bool ALDS>
 int launch_inst4(const BlockArgs& a, const BlockGeom& g, hipStream_t s) {
-    auto kern = block_kernel<MTG, S, KS, PG, SLOW, CPT, ALDS>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, dim3((unsigned)(a.B * g.bands * g.nsplit)), dim3(256), (size_t)g.lds_bytes, s, a, g);
+    return launch_full_lds(block_kernel<MTG, S, KS, PG, SLOW, CPT, ALDS>, dim3((unsigned)(a.B * g.bands * g.nsplit)), dim3(256), (size_t)g.lds_bytes, s, a, g);
 }
 
 template <int MTG, int S, int KS, int PG, bool SLOW, int CPT>

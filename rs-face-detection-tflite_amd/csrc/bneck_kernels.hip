@@ -27,14 +27,12 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
+#include "wave_sync.hpp"
 
 namespace mi {
 
-typedef float nf32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
-
-__device__ __forceinline__ float4 nld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 struct BneckGeom {
     int R;          // rows of the frame a workgroup owns (R * W <= 256)
@@ -50,7 +48,7 @@ struct BneckGeom {
 };
 #ifdef MI_BNECK_STAMPS
 unsigned long long* g_bneck_stamps = nullptr;
-#define MI_BN_STAMP(k) if (g.stamps && (threadIdx.x & 63) == 0) { __builtin_amdgcn_sched_barrier(0); g.stamps[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+#define MI_BN_STAMP(k) if (g.stamps && (threadIdx.x & 63) == 0) MI_STAMP_AT(g.stamps[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (k)])
 #else
 #define MI_BN_STAMP(k)
 #endif
@@ -79,14 +77,6 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
     float* my_r = rt + (oy + 1) * g.RSa + (ox + 1) * PSa;
     const int total = a.B * a.bands;
 
-    // workgroup barrier that orders LDS traffic only (raw s_barrier behind lgkmcnt(0)): __syncthreads() also waits for every global
-    // load and store in flight — the next item's x, the previous item's stores — which is exactly what must stay in flight
-    auto wg_barrier = [&]() {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
     float cr[NCR];
     auto fetch_consts = [&](const BneckBlock& bk) {
 #pragma unroll
@@ -116,7 +106,7 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
         const float* xg = a.in + (long)frame * a.in_fs + ((long)r0 * W + wave * 32) * C;
 #pragma unroll
         for (int k = 0; k < NLD; k++)  // unconditional loads at clamped addresses; pieces past the valid pixels are zeroed where xv is consumed
-            xv[k] = nld4(xg + 4 * min(lane + 64 * k, max(nv * C4 - 1, 0)));  // (a select here would make the wave wait for the data at once)
+            xv[k] = ld4(xg + 4 * min(lane + 64 * k, max(nv * C4 - 1, 0)));  // (a select here would make the wave wait for the data at once)
     };
 
     // r = act1(W1 . x + b1) for one 32-pixel group whose x comes from `xb` (static register indices: the chunk loop is unrolled);
@@ -125,7 +115,7 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
         // weights: from LDS in the walking (row-band) kernels — a global load here would have to wait for the next item's x, which was
         // issued before it (vmcnt retires in order) — from L2 otherwise
         const float* w1p = WL ? lds + g.off_w : bk.w1;
-        nf32x16 Da[MTA];
+        f32x16 Da[MTA];
 #pragma unroll
         for (int t = 0; t < MTA; t++)
 #pragma unroll
@@ -133,7 +123,7 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
         float4 ring[4][MTA];
         auto a_frag = [&](int j, float4 (&av)[MTA]) {
 #pragma unroll
-            for (int t = 0; t < MTA; t++) av[t] = nld4(w1p + ((t * NCH1 + j) * 64 + lane) * 4);
+            for (int t = 0; t < MTA; t++) av[t] = ld4(w1p + ((t * NCH1 + j) * 64 + lane) * 4);
         };
 #pragma unroll
         for (int j = 0; j < 4; j++) a_frag(j, ring[j]);
@@ -141,13 +131,7 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
         for (int j = 0; j < NCH1; j++) {
             const float4 bf = xb(j);
 #pragma unroll
-            for (int t = 0; t < MTA; t++) {
-                const float4 av = ring[j & 3][t];
-                Da[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bf.x, Da[t], 0, 0, 0);
-                Da[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bf.y, Da[t], 0, 0, 0);
-                Da[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bf.z, Da[t], 0, 0, 0);
-                Da[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bf.w, Da[t], 0, 0, 0);
-            }
+            for (int t = 0; t < MTA; t++) mfma32_quad(ring[j & 3][t], bf, Da[t]);
             if (j + 4 < NCH1) a_frag(j + 4, ring[j & 3]);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -156,14 +140,12 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
 #pragma unroll
             for (int gq = 0; gq < 4; gq++) {
                 const int ch = 32 * t + 8 * gq + 4 * h;
-                const float4 bb = nld4(cst + ch), sl = nld4(cst + OFF_SL1 + ch);
+                const float4 bb = ld4(cst + ch), sl = ld4(cst + OFF_SL1 + ch);
+                // D + bias stays written out: as add4(quad4(Da[t], gq), bb) it moved register counts and s_waitcnt in all six instantiations
                 float4 v = make_float4(Da[t][4 * gq] + bb.x, Da[t][4 * gq + 1] + bb.y, Da[t][4 * gq + 2] + bb.z, Da[t][4 * gq + 3] + bb.w);
-                v.x = fminf(fmaxf(v.x, 0.f) + sl.x * fminf(v.x, 0.f), bk.hi1);
-                v.y = fminf(fmaxf(v.y, 0.f) + sl.y * fminf(v.y, 0.f), bk.hi1);
-                v.z = fminf(fmaxf(v.z, 0.f) + sl.z * fminf(v.z, 0.f), bk.hi1);
-                v.w = fminf(fmaxf(v.w, 0.f) + sl.w * fminf(v.w, 0.f), bk.hi1);
+                v = act4(v, sl, bk.hi1);
                 if (!keep) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (store) *reinterpret_cast<float4*>(dst + ch) = v;
+                if (store) st4(dst + ch, v);
             }
     };
 
@@ -177,8 +159,8 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
     }
     if (WL) {
         for (int i = tid; i < (C * Cm) >> 2; i += 512) {
-            reinterpret_cast<float4*>(lds + g.off_w)[i] = nld4(a.blocks[0].w1 + 4 * i);
-            reinterpret_cast<float4*>(lds + g.off_w + C * Cm)[i] = nld4(a.blocks[0].w2 + 4 * i);
+            reinterpret_cast<float4*>(lds + g.off_w)[i] = ld4(a.blocks[0].w1 + 4 * i);
+            reinterpret_cast<float4*>(lds + g.off_w + C * Cm)[i] = ld4(a.blocks[0].w2 + 4 * i);
         }
     }
     for (;;) {  // one item (a frame, or a band of one) per trip; only the walking kernels come round again
@@ -186,7 +168,7 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
         const int nvalid = nvalid_of(item);
         const bool valid = pl < nvalid;
         // ---- x: this lane's pixel, channels 32 m + 8 gq + 4 h + e in X[m][4 gq + e]
-        nf32x16 X[MT];
+        f32x16 X[MT];
         if (PERSIST) {
 #pragma unroll
             for (int k = 0; k < NLD; k++) {
@@ -202,21 +184,19 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
                     const int i = lane + 64 * (k0 + k);
-                    t[k] = nld4(xg + 4 * min(i, max(nvalid * C4 - 1, 0)));
+                    t[k] = ld4(xg + 4 * min(i, max(nvalid * C4 - 1, 0)));
                     if (i >= nvalid * C4) t[k] = make_float4(0.f, 0.f, 0.f, 0.f);
                 }
 #pragma unroll
                 for (int k = 0; k < 8; k++) *reinterpret_cast<float4*>(slab + sl_off(lane, k0 + k)) = t[k];
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
 #pragma unroll
         for (int m = 0; m < MT; m++)
 #pragma unroll
             for (int gq = 0; gq < 4; gq++) {
-                const float4 t = nld4(slab + pl * PSx + 32 * m + 8 * gq + 4 * h);
+                const float4 t = ld4(slab + pl * PSx + 32 * m + 8 * gq + 4 * h);
                 X[m][4 * gq] = t.x; X[m][4 * gq + 1] = t.y; X[m][4 * gq + 2] = t.z; X[m][4 * gq + 3] = t.w;
             }
         // ---- row bands: this wave's piece of the rows above / below the band (the last 2 ceil(W / 32) waves have one each); its x is
@@ -230,17 +210,17 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
         if (PERSIST && hrow) {  // wave-uniform
             const float* xh = a.in + (long)frame * a.in_fs + ((long)hiy * W + (hv ? hx : 0)) * C + 4 * h;
 #pragma unroll
-            for (int j = 0; j < NCH1; j++) xq[PERSIST ? j : 0] = nld4(xh + 32 * (j >> 2) + 8 * (j & 3));
+            for (int j = 0; j < NCH1; j++) xq[PERSIST ? j : 0] = ld4(xh + 32 * (j >> 2) + 8 * (j & 3));
         }
         // ... and, behind it, the next item's x: it has this whole item to arrive.  (vmcnt retires in order: any global load issued
         // after the prefetch would have to wait for it — which is why the walking kernels keep their weights in LDS.)
         if (PERSIST && item + (int)gridDim.x < total) prefetch_x(item + gridDim.x);
         if (!g.slab_sep) {  // the slabs lie over r's region: every wave has its x before r is cleared
-            wg_barrier();
+            lds_barrier();
             for (int i = tid; i < ((g.R + 2) * g.RSa) >> 2; i += 512) reinterpret_cast<float4*>(rt)[i] = zero4;
             commit_consts(0);
         }
-        wg_barrier();
+        lds_barrier();
         MI_BN_STAMP(1)
 
         for (int blk = 0; blk < a.nblocks; blk++) {
@@ -266,10 +246,10 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
             }
             MI_BN_STAMP(3)
             if (more) commit_consts((blk + 1) & 1);  // the other half: its last readers finished before the previous block's closing barrier
-            wg_barrier();
+            lds_barrier();
             MI_BN_STAMP(4)
             // ---- depthwise 3x3 on r (this lane: 4 channels of its half per chunk) -> second pointwise conv over all C output channels
-            nf32x16 D[MT];
+            f32x16 D[MT];
 #pragma unroll
             for (int m = 0; m < MT; m++)
 #pragma unroll
@@ -277,24 +257,11 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
             {
                 const float* t0 = rt + oy * g.RSa + ox * PSa + h * Chm;  // tap (ky, kx) of this lane's pixel: + ky RSa + kx PSa
                 const float* wdw = cst + OFF_WDW + h * Chm;
-                auto dw = [&](int j, float4& bf) {
-                    bf = nld4(cst + OFF_BDW + h * Chm + 4 * j);
-#pragma unroll
-                    for (int ky = 0; ky < 3; ky++)
-#pragma unroll
-                        for (int kx = 0; kx < 3; kx++) {
-                            const float4 w = nld4(wdw + (ky * 3 + kx) * Cm + 4 * j);
-                            const float4 d = nld4(t0 + ky * g.RSa + kx * PSa + 4 * j);
-                            bf.x = fmaf(d.x, w.x, bf.x);
-                            bf.y = fmaf(d.y, w.y, bf.y);
-                            bf.z = fmaf(d.z, w.z, bf.z);
-                            bf.w = fmaf(d.w, w.w, bf.w);
-                        }
-                };
+                auto dw = [&](int j, float4& bf) { bf = dw3x3_quad<true>(wdw + 4 * j, Cm, t0 + 4 * j, g.RSa, PSa, cst + OFF_BDW + h * Chm + 4 * j); };
                 const float* w2p = WL ? lds + g.off_w + C * Cm : bk.w2;
                 auto a_frag = [&](int j, float4 (&av)[MT]) {
 #pragma unroll
-                    for (int m = 0; m < MT; m++) av[m] = nld4(w2p + ((m * NCH2 + j) * 64 + lane) * 4);
+                    for (int m = 0; m < MT; m++) av[m] = ld4(w2p + ((m * NCH2 + j) * 64 + lane) * 4);
                 };
                 // weights one chunk ahead: a chunk is 4 MT MFMAs (512 - 1024 cycles), an L2 round trip
                 float4 bf, av[MT];
@@ -305,12 +272,7 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
                     float4 bn = bf, an[MT];
                     if (j + 1 < NCH2) { a_frag(j + 1, an); dw(j + 1, bn); }
 #pragma unroll
-                    for (int m = 0; m < MT; m++) {
-                        D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].x, bf.x, D[m], 0, 0, 0);
-                        D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].y, bf.y, D[m], 0, 0, 0);
-                        D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].z, bf.z, D[m], 0, 0, 0);
-                        D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].w, bf.w, D[m], 0, 0, 0);
-                    }
+                    for (int m = 0; m < MT; m++) mfma32_quad(av[m], bf, D[m]);
                     bf = bn;
                     if (j + 1 < NCH2) {
 #pragma unroll
@@ -326,40 +288,34 @@ __global__ __launch_bounds__(512, 2) void bneck_kernel(BneckArgs a, BneckGeom g)
 #pragma unroll
                 for (int gq = 0; gq < 4; gq++) {
                     const int ch = 32 * m + 8 * gq + 4 * h;
-                    const float4 bb = nld4(cst + OFF_B2 + ch), sl = nld4(cst + OFF_SL2 + ch);
-                    const float4 v = make_float4(D[m][4 * gq] + bb.x + X[m][4 * gq], D[m][4 * gq + 1] + bb.y + X[m][4 * gq + 1],
-                                                 D[m][4 * gq + 2] + bb.z + X[m][4 * gq + 2], D[m][4 * gq + 3] + bb.w + X[m][4 * gq + 3]);
-                    X[m][4 * gq] = fminf(fmaxf(v.x, 0.f) + sl.x * fminf(v.x, 0.f), bk.hi2);
-                    X[m][4 * gq + 1] = fminf(fmaxf(v.y, 0.f) + sl.y * fminf(v.y, 0.f), bk.hi2);
-                    X[m][4 * gq + 2] = fminf(fmaxf(v.z, 0.f) + sl.z * fminf(v.z, 0.f), bk.hi2);
-                    X[m][4 * gq + 3] = fminf(fmaxf(v.w, 0.f) + sl.w * fminf(v.w, 0.f), bk.hi2);
+                    const float4 bb = ld4(cst + OFF_B2 + ch), sl = ld4(cst + OFF_SL2 + ch);
+                    const float4 v = bias_skip_act4(quad4(D[m], gq), bb, quad4(X[m], gq), sl, bk.hi2);
+                    X[m][4 * gq] = v.x; X[m][4 * gq + 1] = v.y; X[m][4 * gq + 2] = v.z; X[m][4 * gq + 3] = v.w;
                 }
-            if (more) wg_barrier();  // every wave has read r: the next block may overwrite it
+            if (more) lds_barrier();  // every wave has read r: the next block may overwrite it
         }
         MI_BN_STAMP(6)
         // ---- the result leaves the registers the way x came in
-        if (!g.slab_sep) wg_barrier();  // every wave is done with r: the slabs may overwrite it
+        if (!g.slab_sep) lds_barrier();  // every wave is done with r: the slabs may overwrite it
 #pragma unroll
         for (int m = 0; m < MT; m++)
 #pragma unroll
             for (int gq = 0; gq < 4; gq++)
                 *reinterpret_cast<float4*>(slab + pl * PSx + 32 * m + 8 * gq + 4 * h) = make_float4(X[m][4 * gq], X[m][4 * gq + 1], X[m][4 * gq + 2], X[m][4 * gq + 3]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         {
             float* yg = a.out + (long)frame * a.out_fs + ((long)r0 * W + wave * 32) * C;
             int ln = lane;
             asm volatile("" : "+v"(ln));  // recomputed here: shared with the write at the top, the slab offsets would stay live across the item
 #pragma unroll
             for (int k = 0; k < NLD; k++)
-                if (ln + 64 * k < nvalid * C4) *reinterpret_cast<float4*>(yg + 4 * (ln + 64 * k)) = nld4(slab + sl_off(ln, k));
+                if (ln + 64 * k < nvalid * C4) *reinterpret_cast<float4*>(yg + 4 * (ln + 64 * k)) = ld4(slab + sl_off(ln, k));
         }
         MI_BN_STAMP(7)
         if (!PERSIST) break;
         item += gridDim.x;
         if (item >= total) break;
-        wg_barrier();  // the next item overwrites r
+        lds_barrier();  // the next item overwrites r
     }
 }
 
@@ -374,7 +330,7 @@ bool make_bneck_geom(const BneckArgs& a, BneckGeom* out) {
     g.PSx = a.C + 4;
     g.cfl = (12 * a.Cm + 2 * a.C + 3) & ~3;
     const int rfl = ((g.R + 2) * g.RSa + 3) & ~3, sfl = 8 * 32 * g.PSx;
-    g.slab_sep = (rfl + 2 * g.cfl + sfl) * 4 <= 160 * 1024 - 256;
+    g.slab_sep = (rfl + 2 * g.cfl + sfl) * 4 <= kLdsBudget;
     int off = g.slab_sep ? rfl : std::max(rfl, sfl);
     g.off_c = off;
     off += 2 * g.cfl;
@@ -382,13 +338,12 @@ bool make_bneck_geom(const BneckArgs& a, BneckGeom* out) {
     if (g.slab_sep) off += sfl;
     g.off_w = -1;
     if (a.bands > 1) {  // row bands: the walking kernel (weights in LDS, slabs beside r)
-        if (!g.slab_sep || (off + 2 * a.C * a.Cm) * 4 > 160 * 1024 - 256) return false;
+        if (!g.slab_sep || (off + 2 * a.C * a.Cm) * 4 > kLdsBudget) return false;
         g.off_w = off;
         off += 2 * a.C * a.Cm;
     }
     g.lds_bytes = off * 4;
-    if (g.lds_bytes > 160 * 1024 - 256) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (g.lds_bytes > kLdsBudget) return false;
     if (!aligned16(a.in) || !aligned16(a.out) || (a.in_fs & 3) || (a.out_fs & 3)) return false;
     for (int k = 0; k < a.nblocks; k++)
         if (!a.blocks[k].w1 || !a.blocks[k].w2 || !a.blocks[k].consts || !aligned16(a.blocks[k].w1) || !aligned16(a.blocks[k].w2)) return false;
@@ -396,16 +351,12 @@ bool make_bneck_geom(const BneckArgs& a, BneckGeom* out) {
     return true;
 }
 
-int bneck_cu_count() { return device_cu_count(); }  // launch.hpp: per device
-
 template <int MT, int MTA, bool WL>
 int launch_bneck_inst(const BneckArgs& a, const BneckGeom& g, hipStream_t s) {
-    auto kern = bneck_kernel<MT, MTA, WL>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
     // row bands: one workgroup per CU walks over its share of the bands (the next band's x in flight under the current band's MFMAs)
     unsigned grid = (unsigned)(a.B * a.bands);
-    if (WL) grid = std::min(grid, (unsigned)bneck_cu_count());  // walking kernels: one workgroup per CU
-    return (int)launch_kernel(kern, dim3(grid), dim3(512), (size_t)g.lds_bytes, s, a, g);
+    if (WL) grid = std::min(grid, (unsigned)device_cu_count());  // walking kernels: one workgroup per CU
+    return launch_full_lds(bneck_kernel<MT, MTA, WL>, dim3(grid), dim3(512), (size_t)g.lds_bytes, s, a, g);
 }
 
 }  // namespace

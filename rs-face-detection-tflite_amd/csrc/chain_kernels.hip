@@ -23,16 +23,14 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
 
 namespace mi {
 
-typedef float f32x16c __attribute__((ext_vector_type(16)));
 typedef float f32x2c __attribute__((ext_vector_type(2)));
 typedef float f32x4c __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ __forceinline__ float4 cld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 struct ChainGeom {
     int Cp, Ch, C4, PS, RS, MT;
@@ -45,7 +43,7 @@ struct ChainGeom {
 };
 #ifdef MI_CHAIN_STAMPS
 unsigned long long* g_chain_stamps = nullptr;
-#define MI_CHAIN_STAMP(k) if (g.stamps && threadIdx.x == 0) { __builtin_amdgcn_sched_barrier(0); g.stamps[(long)blockIdx.x * 24 + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+#define MI_CHAIN_STAMP(k) if (g.stamps && threadIdx.x == 0) MI_STAMP_AT(g.stamps[(long)blockIdx.x * 24 + (k)])
 #else
 #define MI_CHAIN_STAMP(k)
 #endif
@@ -58,7 +56,7 @@ constexpr int chain_pre_passes(int C, int H, int W, int Cin, int post_Co, int MT
         const int RP = (H + P - 1) / P, GP = (RP * W + 31) / 32;
         const long stage = (long)(2 * RP + 1) * pre_RS;
         const long rest = 9 * C + C + 8 * 32 + 64 + (post_Co ? (long)(H >> 1) * (W >> 1) * (post_Co + 4) : 0);
-        if ((P - 1) * RP < H && P * GP * (split ? MT : 1) <= 8 && ((stage > tile ? stage : tile) + rest) * 4 <= 160 * 1024 - 256) return P;
+        if ((P - 1) * RP < H && P * GP * (split ? MT : 1) <= 8 && ((stage > tile ? stage : tile) + rest) * 4 <= kLdsBudget) return P;
     }
     return 0;
 }
@@ -218,16 +216,17 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         if constexpr (GP::fixed) {  // a wave-uniform address stepped on the scalar unit plus this lane's loop-invariant 32-bit offsets
             if (nchk == nch) {
 #pragma unroll
-                for (int m = 0; m < MT; m++) av[m] = cld4(cb.w_pw + (long)j * 256 + (size_t)aoff[m]);
+                for (int m = 0; m < MT; m++) av[m] = ld4(cb.w_pw + (long)j * 256 + (size_t)aoff[m]);
                 return;
             }
         }
 #pragma unroll
-        for (int m = 0; m < MT; m++) av[m] = cld4(cb.w_pw + (((long)m * nchk + j) * 64 + lane) * 4);
+        for (int m = 0; m < MT; m++) av[m] = ld4(cb.w_pw + (((long)m * nchk + j) * 64 + lane) * 4);
 #endif
     };
-    // first: the contraction's first chunk, whose first MFMA takes a zero C operand (the accumulators are never cleared by moves)
-    const f32x16c zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // first: the contraction's first chunk, whose first MFMA takes a zero C operand (the accumulators are never cleared by moves).
+    // The MFMA quads of this file (here, contract1, contract1_ph) stay written out for that first MFMA: fixed-shape code, not mfma32_quad.
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     auto mfma_chunk = [&](const float4 (&av)[MT], const float4& bf, auto& D, auto first) {
 #ifdef MI_ABL_CHAIN_NOMFMA  // timing ablation: one VALU op per chunk and tile instead of the four MFMAs
 #pragma unroll
@@ -282,12 +281,12 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
     // waves idle (the 8x8 / 6x6 frames, the stride-2 block behind the chain, the output heads).  A unit is only 4 nchk dependent
     // MFMAs, too short to hide an L2 round trip per chunk behind the previous chunk: every weight chunk is in flight up front.
     constexpr int NJ = MT * 4;  // K <= 32 MT  ->  nchk <= 4 MT
-    auto contract1 = [&](const float* w_pw, int nchk, int mt, auto&& dw, f32x16c& D1) {
+    auto contract1 = [&](const float* w_pw, int nchk, int mt, auto&& dw, f32x16& D1) {
         const float* wa = w_pw + ((long)mt * nchk * 64 + lane) * 4;
         float4 aw[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; j++)
-            if (j < nchk) aw[j] = cld4(wa + 256 * j);
+            if (j < nchk) aw[j] = ld4(wa + 256 * j);
         if constexpr (!GP::fixed) {
 #pragma unroll
             for (int e = 0; e < 16; e++) D1[e] = 0.f;
@@ -355,13 +354,13 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         step(NCH - 1, av[1], av[1], std::false_type{}, std::true_type{});
     };
     // one output tile of a group (contract1's unit): every weight fragment in flight up front, the chunks unrolled
-    [[maybe_unused]] auto contract1_ph = [&](auto form, auto nchk_c, const float* w_pw, int mt, unsigned wa, unsigned ta, f32x16c& D1) {
+    [[maybe_unused]] auto contract1_ph = [&](auto form, auto nchk_c, const float* w_pw, int mt, unsigned wa, unsigned ta, f32x16& D1) {
         using F = decltype(form);
         constexpr int NCH = decltype(nchk_c)::value;
         const float* wag = w_pw + ((long)mt * NCH * 64 + lane) * 4;
         float4 aw[NCH];
 #pragma unroll
-        for (int j = 0; j < NCH; j++) aw[j] = cld4(wag + 256 * j);
+        for (int j = 0; j < NCH; j++) aw[j] = ld4(wag + 256 * j);
         DwTaps t;
         float4 bf;
         dw_request<F>(wa, ta, t);
@@ -390,7 +389,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         }
     };
     // bias (+ skip) + activation of the 4 channels ch .. ch + 3 (register quad gq) of this lane, in place
-    auto finish1 = [&](f32x16c& D1, int ch, int gq, const float4& skip, float hi) {
+    auto finish1 = [&](f32x16& D1, int ch, int gq, const float4& skip, float hi) {
         if constexpr (ACT == ACT_RELU) {
             // the same two adds in the same order, packed, then one max: for finite values the bits of the general form with a slope
             // of 0 and no upper bound (where v < 0 that one gives 0 + (-0) = +0)
@@ -403,12 +402,9 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
             D1[4 * gq + 3] = fmaxf(v1.y, 0.f);
             return;
         }
-        const float4 bb = cld4(lds + geo.off_bias() + ch), al = cld4(lds + geo.off_alpha() + ch);
-        const float4 v = make_float4(D1[4 * gq] + bb.x + skip.x, D1[4 * gq + 1] + bb.y + skip.y, D1[4 * gq + 2] + bb.z + skip.z, D1[4 * gq + 3] + bb.w + skip.w);
-        D1[4 * gq] = fminf(fmaxf(v.x, 0.f) + al.x * fminf(v.x, 0.f), hi);
-        D1[4 * gq + 1] = fminf(fmaxf(v.y, 0.f) + al.y * fminf(v.y, 0.f), hi);
-        D1[4 * gq + 2] = fminf(fmaxf(v.z, 0.f) + al.z * fminf(v.z, 0.f), hi);
-        D1[4 * gq + 3] = fminf(fmaxf(v.w, 0.f) + al.w * fminf(v.w, 0.f), hi);
+        const float4 bb = ld4(lds + geo.off_bias() + ch), al = ld4(lds + geo.off_alpha() + ch);
+        const float4 v = bias_skip_act4(quad4(D1, gq), bb, skip, al, hi);
+        D1[4 * gq] = v.x; D1[4 * gq + 1] = v.y; D1[4 * gq + 2] = v.z; D1[4 * gq + 3] = v.w;
     };
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 
@@ -439,7 +435,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         fetch_consts(a.blocks[0], geo.C(), geo.C(), cr);  // block 0's constants travel while this stage runs
         const float* wdw = lds + geo.off_wdw();
         const float* bdw = lds + geo.off_bdw();
-        f32x16c D[SPLIT ? 1 : MT];
+        f32x16 D[SPLIT ? 1 : MT];
         bool mine = false;
         float* my_centre = tile;
         int my_mt = 0;
@@ -450,7 +446,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
             if (p) __syncthreads();               // the previous pass has read its rows
             for (int i = tid; i < nrows * rowf4i; i += 512) {
                 const int rr = i / rowf4i, e = i - rr * rowf4i, px = e / C4i, c4 = e - px * C4i, iy = 2 * r0 + rr;
-                *reinterpret_cast<float4*>(lds + rr * RSi + px * PSi + 4 * c4) = iy < Hi ? cld4(src + ((long)iy * rowf4i + e) * 4) : zero4;
+                *reinterpret_cast<float4*>(lds + rr * RSi + px * PSi + 4 * c4) = iy < Hi ? ld4(src + ((long)iy * rowf4i + e) * 4) : zero4;
             }
             for (int i = tid; i < nrows * C4i; i += 512) {
                 const int rr = i / C4i, c4 = i - rr * C4i;
@@ -467,17 +463,15 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                 const float* t0 = lds + (2 * oyl) * RSi + (2 * oxp) * PSi;  // tap (ky, kx) of this lane's output pixel
                 auto dw = [&](int j, float4& bf) {
                     const int c0 = h * Chp + 4 * j;
-                    bf = cld4(bdw + c0);
+                    // the loop stays here (fma4 only): as dw3x3_quad the run-time-geometry instantiations trade packed FMAs for plain ones
+                    bf = ld4(bdw + c0);
 #pragma unroll
                     for (int ky = 0; ky < 3; ky++)
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) {
-                            const float4 w = cld4(wdw + (ky * 3 + kx) * geo.Cp() + c0);
-                            const float4 d = cld4(t0 + ky * RSi + kx * PSi + c0);
-                            bf.x = fmaf(d.x, w.x, bf.x);
-                            bf.y = fmaf(d.y, w.y, bf.y);
-                            bf.z = fmaf(d.z, w.z, bf.z);
-                            bf.w = fmaf(d.w, w.w, bf.w);
+                            const float4 w = ld4(wdw + (ky * 3 + kx) * geo.Cp() + c0);
+                            const float4 d = ld4(t0 + ky * RSi + kx * PSi + c0);
+                            fma4(d, w, bf);
                         }
                 };
                 if constexpr (SCHED == 1 && !SPLIT) {
@@ -495,7 +489,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                         if (ch >= geo.C()) continue;
                         float4 sk = zero4;
                         if (cb.has_res && ch < Cin) {  // 2x2 max-pool of the input, channels above Cin are the zero pad
-                            const float4 s0 = cld4(t0 + ch), s1 = cld4(t0 + PSi + ch), s2 = cld4(t0 + RSi + ch), s3 = cld4(t0 + RSi + PSi + ch);
+                            const float4 s0 = ld4(t0 + ch), s1 = ld4(t0 + PSi + ch), s2 = ld4(t0 + RSi + ch), s3 = ld4(t0 + RSi + PSi + ch);
                             sk = make_float4(fmaxf(fmaxf(s0.x, s1.x), fmaxf(s2.x, s3.x)), fmaxf(fmaxf(s0.y, s1.y), fmaxf(s2.y, s3.y)),
                                              fmaxf(fmaxf(s0.z, s1.z), fmaxf(s2.z, s3.z)), fmaxf(fmaxf(s0.w, s1.w), fmaxf(s2.w, s3.w)));
                         }
@@ -527,7 +521,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         for (int i = tid; i < geo.H() * rowf4; i += 512) {
             int r = i / rowf4, e = i - r * rowf4;
             int px = e / geo.C4(), c4 = e - px * geo.C4();
-            *reinterpret_cast<float4*>(tile + (r + 1) * geo.RS() + (px + 1) * geo.PS() + 4 * c4) = cld4(in + 4 * (long)i);
+            *reinterpret_cast<float4*>(tile + (r + 1) * geo.RS() + (px + 1) * geo.PS() + 4 * c4) = ld4(in + 4 * (long)i);
         }
         commit_consts(cr);
     }
@@ -547,7 +541,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         int wlane = geo.off_wdw() + h * geo.Ch();
         if constexpr (GP::fixed) asm volatile("" : "+v"(wlane));
 
-        f32x16c D[SPLIT ? 1 : MT];
+        f32x16 D[SPLIT ? 1 : MT];
         if (wave_active) {
             auto dw = [&](int j, float4& bf) {
                 if constexpr (GP::fixed) {
@@ -559,12 +553,12 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                     for (int ky = 0; ky < 3; ky++)
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) {
-                            const float4 w = cld4(wj + (ky * 3 + kx) * geo.Cp());
-                            const float4 d = cld4(tj + ky * geo.RS() + kx * geo.PS());
+                            const float4 w = ld4(wj + (ky * 3 + kx) * geo.Cp());
+                            const float4 d = ld4(tj + ky * geo.RS() + kx * geo.PS());
                             lo = __builtin_elementwise_fma(f32x2c{d.x, d.y}, f32x2c{w.x, w.y}, lo);
                             up = __builtin_elementwise_fma(f32x2c{d.z, d.w}, f32x2c{w.z, w.w}, up);
                         }
-                    const float4 bb = cld4(wj + 9 * geo.Cp());  // the depthwise bias lies behind the nine taps
+                    const float4 bb = ld4(wj + 9 * geo.Cp());  // the depthwise bias lies behind the nine taps
                     lo += f32x2c{bb.x, bb.y};
                     up += f32x2c{bb.z, bb.w};
                     bf = make_float4(lo.x, lo.y, up.x, up.y);
@@ -573,22 +567,18 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                 const float* wj = wdw + h * geo.Ch() + 4 * j;
                 bf = zero4;
 #ifdef MI_ABL_CHAIN_NODW  // timing ablation: centre tap only
-                bf = cld4(tile + base0 + geo.RS() + geo.PS() + 4 * j);
+                bf = ld4(tile + base0 + geo.RS() + geo.PS() + 4 * j);
                 return;
 #endif
 #pragma unroll
                 for (int ky = 0; ky < 3; ky++)
 #pragma unroll
                     for (int kx = 0; kx < 3; kx++) {
-                        const float4 w = cld4(wj + (ky * 3 + kx) * geo.Cp());
-                        const float4 d = cld4(tile + base0 + ky * geo.RS() + kx * geo.PS() + 4 * j);
-                        bf.x = fmaf(d.x, w.x, bf.x);
-                        bf.y = fmaf(d.y, w.y, bf.y);
-                        bf.z = fmaf(d.z, w.z, bf.z);
-                        bf.w = fmaf(d.w, w.w, bf.w);
+                        const float4 w = ld4(wj + (ky * 3 + kx) * geo.Cp());
+                        const float4 d = ld4(tile + base0 + ky * geo.RS() + kx * geo.PS() + 4 * j);
+                        fma4(d, w, bf);
                     }
-                const float4 bb = cld4(bdw + h * geo.Ch() + 4 * j);
-                bf.x += bb.x; bf.y += bb.y; bf.z += bb.z; bf.w += bb.w;
+                bf = add4(bf, ld4(bdw + h * geo.Ch() + 4 * j));
             };
             // ---- contraction, then the epilogue into registers (reads x at the centre pixel), written back after the barrier
             const float hi = cb.act == ACT_RELU6 ? 6.f : INFINITY;
@@ -605,7 +595,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
 #pragma unroll
                 for (int gq = 0; gq < 4; gq++) {
                     const int ch = (SPLIT ? mt_w : m) * 32 + 8 * gq + 4 * h;
-                    if (ch < geo.C()) finish1(D[m], ch, gq, (GP::all_res || cb.has_res) ? cld4(centre + ch) : zero4, hi);
+                    if (ch < geo.C()) finish1(D[m], ch, gq, (GP::all_res || cb.has_res) ? ld4(centre + ch) : zero4, hi);
                 }
         }
         __syncthreads();  // every wave has read x (and the constants) for this block
@@ -628,7 +618,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
         for (int i = tid; i < geo.H() * rowf4; i += 512) {
             int r = i / rowf4, e = i - r * rowf4;
             int px = e / geo.C4(), c4 = e - px * geo.C4();
-            *reinterpret_cast<float4*>(out + 4 * (long)i) = cld4(tile + (r + 1) * geo.RS() + (px + 1) * geo.PS() + 4 * c4);
+            *reinterpret_cast<float4*>(out + 4 * (long)i) = ld4(tile + (r + 1) * geo.RS() + (px + 1) * geo.PS() + 4 * c4);
         }
     }
     MI_CHAIN_STAMP(10)
@@ -648,21 +638,10 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
             const int py = vo ? qo / Wo : 0, px = vo ? qo - (qo / Wo) * Wo : 0;
             // SAME on an even size: taps at image rows 2py .. 2py+2 = tile slots 2py+1 .. 2py+3 (slot H+1 is the zero border)
             const float* t0 = tile + (2 * py + 1) * geo.RS() + (2 * px + 1) * geo.PS();
-            f32x16c D1;
+            f32x16 D1;
             auto dw = [&](int j, float4& bf) {
                 const int c0 = h * geo.Ch() + 4 * j;
-                bf = cld4(bdw + c0);
-#pragma unroll
-                for (int ky = 0; ky < 3; ky++)
-#pragma unroll
-                    for (int kx = 0; kx < 3; kx++) {
-                        const float4 w = cld4(wdw + (ky * 3 + kx) * geo.Cp() + c0);
-                        const float4 d = cld4(t0 + ky * geo.RS() + kx * geo.PS() + c0);
-                        bf.x = fmaf(d.x, w.x, bf.x);
-                        bf.y = fmaf(d.y, w.y, bf.y);
-                        bf.z = fmaf(d.z, w.z, bf.z);
-                        bf.w = fmaf(d.w, w.w, bf.w);
-                    }
+                bf = dw3x3_quad<true>(wdw + c0, geo.Cp(), t0 + c0, geo.RS(), geo.PS(), bdw + c0);
             };
             if constexpr (SCHED == 1) {
                 using K = typename GP::K;
@@ -677,7 +656,7 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
                 if (ch >= Co) continue;
                 float4 sk = zero4;
                 if (cb.has_res && ch < geo.C()) {  // 2x2 max-pool of the resident frame, zero channel pad above C
-                    const float4 s0 = cld4(t0 + ch), s1 = cld4(t0 + geo.PS() + ch), s2 = cld4(t0 + geo.RS() + ch), s3 = cld4(t0 + geo.RS() + geo.PS() + ch);
+                    const float4 s0 = ld4(t0 + ch), s1 = ld4(t0 + geo.PS() + ch), s2 = ld4(t0 + geo.RS() + ch), s3 = ld4(t0 + geo.RS() + geo.PS() + ch);
                     sk = make_float4(fmaxf(fmaxf(s0.x, s1.x), fmaxf(s2.x, s3.x)), fmaxf(fmaxf(s0.y, s1.y), fmaxf(s2.y, s3.y)),
                                      fmaxf(fmaxf(s0.z, s1.z), fmaxf(s2.z, s3.z)), fmaxf(fmaxf(s0.w, s1.w), fmaxf(s2.w, s3.w)));
                 }
@@ -710,9 +689,9 @@ __global__ __launch_bounds__(512, 2) void chain_kernel(ChainArgs a, ChainGeom g)
             const float* px = from_post ? lds + g.off_t8 + qc * (Cs + 4) : tile + (qc / Wh + 1) * geo.RS() + (qc % Wh + 1) * geo.PS();
             float4 bq[4];
 #pragma unroll
-            for (int gq = 0; gq < 4; gq++) bq[gq] = H.bias ? cld4(H.bias + mt * 32 + 8 * gq + 4 * h) : zero4;  // stacked, zero padded to the tile
-            f32x16c D1;
-            contract1(H.w_pw, nchs, mt, [&](int j, float4& bf) { bf = cld4(px + h * Chs + 4 * j); }, D1);
+            for (int gq = 0; gq < 4; gq++) bq[gq] = H.bias ? ld4(H.bias + mt * 32 + 8 * gq + 4 * h) : zero4;  // stacked, zero padded to the tile
+            f32x16 D1;
+            contract1(H.w_pw, nchs, mt, [&](int j, float4& bf) { bf = ld4(px + h * Chs + 4 * j); }, D1);
             if (!vh) continue;
 #pragma unroll
             for (int gq = 0; gq < 4; gq++) {
@@ -770,8 +749,7 @@ bool make_chain_geom(const ChainArgs& a, ChainGeom* out) {
         }
     }
     g.lds_bytes = off * 4;
-    if (g.lds_bytes > 160 * 1024 - 256) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (g.lds_bytes > kLdsBudget) return false;
     if (!aligned16(a.in) || !aligned16(a.out) || (a.in_fs & 3) || (a.out_fs & 3)) return false;
     if (a.pre.on && (a.pre.Cin % 8 || a.pre.Cin < 8 || a.pre.Cin > a.C || !aligned16(a.pre.in) || (a.pre.in_fs & 3))) return false;
     if (a.post.on && ((a.H & 1) || (a.W & 1) || a.post.Co % 4 || a.post.Co < a.C || a.post.Co > g.MT * 32 || !aligned16(a.post.out) || (a.post.out_fs & 3))) return false;
@@ -790,9 +768,7 @@ bool all_relu(const ChainArgs& a) {
 
 template <int MT, bool SPLIT, class GP = GeomRun, int ACT = kActRun, int SCHED = 0>
 int launch_chain_inst(const ChainArgs& a, const ChainGeom& g, hipStream_t s) {
-    auto kern = chain_kernel<MT, SPLIT, GP, ACT, SCHED>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, dim3((unsigned)a.B), dim3(512), (size_t)g.lds_bytes, s, a, g);
+    return launch_full_lds(chain_kernel<MT, SPLIT, GP, ACT, SCHED>, dim3((unsigned)a.B), dim3(512), (size_t)g.lds_bytes, s, a, g);
 }
 
 }  // namespace

@@ -26,14 +26,12 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
+#include "wave_sync.hpp"
 
 namespace mi {
 
-typedef float df32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
-
-__device__ __forceinline__ float4 dld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 constexpr int kDbPrefetch = 12;  // float4 registers per thread for the next band's rows of x
 
@@ -49,7 +47,7 @@ struct DblockGeom {
 };
 #ifdef MI_DBLOCK_STAMPS
 unsigned long long* g_dblock_stamps = nullptr;
-#define MI_DB_STAMP(k) if (g.stamps && (threadIdx.x & 63) == 0) { __builtin_amdgcn_sched_barrier(0); g.stamps[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+#define MI_DB_STAMP(k) if (g.stamps && (threadIdx.x & 63) == 0) MI_STAMP_AT(g.stamps[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (k)])
 #else
 #define MI_DB_STAMP(k)
 #endif
@@ -70,13 +68,6 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
     const int o_bdw1 = 9 * g.Cp, o_b1 = 10 * g.Cp, o_sl1 = o_b1 + 32 * MTA, o_wdw2 = o_sl1 + 32 * MTA, o_bdw2 = o_wdw2 + 9 * g.Cmp, o_b2 = o_bdw2 + g.Cmp, o_sl2 = o_b2 + 32 * MT;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const int total = a.B * g.bands;
-    // LDS-only workgroup barrier: __syncthreads() would also wait for the next band's rows and for this band's stores
-    auto wg_barrier = [&]() {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
     // the rows of x a band needs: image rows [r0 - 2, r0 + RB + 2) clipped to the image = one contiguous piece of the frame
     auto band_rows = [&](int it, int& frame, int& r0, int& lo, int& hi) {
         frame = it / g.bands;
@@ -91,15 +82,15 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
         const int n4 = (hi - lo) * W * C4;
         const float* src = a.in + (long)frame * a.in_fs + (long)lo * W * a.C;
 #pragma unroll
-        for (int k = 0; k < kDbPrefetch; k++) xv[k] = dld4(src + 4 * (long)min(tid + 512 * k, n4 - 1));  // clamped; pieces past the end are not used
+        for (int k = 0; k < kDbPrefetch; k++) xv[k] = ld4(src + 4 * (long)min(tid + 512 * k, n4 - 1));  // clamped; pieces past the end are not used
     };
 
     // ---- once per workgroup: clear both tensors (their border columns stay zero), stage the constants and the weights
     for (int i = tid; i < ((g.RB + 4) * g.RSx) >> 2; i += 512) reinterpret_cast<float4*>(xt)[i] = zero4;
     for (int i = tid; i < ((g.RB + 2) * g.RSa) >> 2; i += 512) reinterpret_cast<float4*>(at)[i] = zero4;
     for (int i = tid; i < g.cfl; i += 512) lds[g.off_c + i] = a.consts[i];
-    for (int i = tid; i < (32 * MTA * g.Cp) >> 2; i += 512) reinterpret_cast<float4*>(lds + g.off_w1)[i] = dld4(a.w1 + 4 * i);
-    for (int i = tid; i < (32 * MT * g.Cmp) >> 2; i += 512) reinterpret_cast<float4*>(lds + g.off_w2)[i] = dld4(a.w2 + 4 * i);
+    for (int i = tid; i < (32 * MTA * g.Cp) >> 2; i += 512) reinterpret_cast<float4*>(lds + g.off_w1)[i] = ld4(a.w1 + 4 * i);
+    for (int i = tid; i < (32 * MT * g.Cmp) >> 2; i += 512) reinterpret_cast<float4*>(lds + g.off_w2)[i] = ld4(a.w2 + 4 * i);
     int item = blockIdx.x;
     prefetch(item);
 
@@ -113,26 +104,9 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
             for (int e = 0; e < 16; e++) D[m][e] = 0.f;
         for (int j = 0; j < nchk; j++) {
             const int c0 = h * Chh + 4 * j;
-            float4 bf = dld4(bdw + c0);
+            const float4 bf = dw3x3_quad<true>(wdw + c0, Cpad, t0 + c0, RS, PS, bdw + c0);
 #pragma unroll
-            for (int ky = 0; ky < 3; ky++)
-#pragma unroll
-                for (int kx = 0; kx < 3; kx++) {
-                    const float4 w = dld4(wdw + (ky * 3 + kx) * Cpad + c0);
-                    const float4 d = dld4(t0 + ky * RS + kx * PS + c0);
-                    bf.x = fmaf(d.x, w.x, bf.x);
-                    bf.y = fmaf(d.y, w.y, bf.y);
-                    bf.z = fmaf(d.z, w.z, bf.z);
-                    bf.w = fmaf(d.w, w.w, bf.w);
-                }
-#pragma unroll
-            for (int m = 0; m < NT; m++) {
-                const float4 av = dld4(wL + ((m * nchk + j) * 64 + lane) * 4);
-                D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bf.x, D[m], 0, 0, 0);
-                D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bf.y, D[m], 0, 0, 0);
-                D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bf.z, D[m], 0, 0, 0);
-                D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bf.w, D[m], 0, 0, 0);
-            }
+            for (int m = 0; m < NT; m++) mfma32_quad(ld4(wL + ((m * nchk + j) * 64 + lane) * 4), bf, D[m]);
         }
     };
 
@@ -148,7 +122,7 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
         constexpr int NT = decltype(NTc)::value;
         constexpr bool TOLDS = decltype(TOLDSc)::value;
         const int Chh = Cpad >> 1;
-        auto finish = [&](const df32x16 (&D)[NT], int la, int ox, bool valid) {
+        auto finish = [&](const f32x16 (&D)[NT], int la, int ox, bool valid) {
             const int iy = img0 + la;
             const bool inside = iy >= 0 && iy < a.H;
             const float* ks = K ? K + (la + krow) * RSk + (ox + 1) * PSk : nullptr;
@@ -160,19 +134,15 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
                 for (int gq = 0; gq < 4; gq++) {
                     const int ch = 32 * m + 8 * gq + 4 * h;
                     if (ch >= (TOLDS ? g.Cmp : Cout) || !valid) continue;
-                    const float4 bb = dld4(bias + ch), sl = dld4(slope + ch);
+                    const float4 bb = ld4(bias + ch), sl = ld4(slope + ch);
                     float4 sk = make_float4(0.f, 0.f, 0.f, 0.f);  // channels above Ck: the zero channel-pad of the skip
-                    if (ks && ch < Ck) sk = dld4(ks + ch);
-                    float4 v = make_float4(D[m][4 * gq] + bb.x + sk.x, D[m][4 * gq + 1] + bb.y + sk.y, D[m][4 * gq + 2] + bb.z + sk.z, D[m][4 * gq + 3] + bb.w + sk.w);
-                    v.x = fminf(fmaxf(v.x, 0.f) + sl.x * fminf(v.x, 0.f), hi);
-                    v.y = fminf(fmaxf(v.y, 0.f) + sl.y * fminf(v.y, 0.f), hi);
-                    v.z = fminf(fmaxf(v.z, 0.f) + sl.z * fminf(v.z, 0.f), hi);
-                    v.w = fminf(fmaxf(v.w, 0.f) + sl.w * fminf(v.w, 0.f), hi);
+                    if (ks && ch < Ck) sk = ld4(ks + ch);
+                    float4 v = bias_skip_act4(quad4(D[m], gq), bb, sk, sl, hi);
                     if (TOLDS) {
                         if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);  // rows outside the image are the next depthwise conv's zero padding
-                        *reinterpret_cast<float4*>(dl + ch) = v;
+                        st4(dl + ch, v);
                     } else {
-                        *reinterpret_cast<float4*>(dg + ch) = v;
+                        st4(dg + ch, v);
                     }
                 }
         };
@@ -183,7 +153,7 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
                 const int q = grp * 32 + pl;
                 const bool valid = q < npx;
                 const int la = valid ? q / W : 0, ox = valid ? q - (q / W) * W : 0;
-                df32x16 D[NT];
+                f32x16 D[NT];
                 contract(S + la * RSs + ox * PSs, RSs, PSs, Cpad, nchk, wdw, bdw, wL, D, NTc);
                 finish(D, la, ox, valid);
             }
@@ -194,14 +164,14 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
                 const bool vq = qq < npq;
                 const int pr = vq ? qq / W : 0, ox = vq ? qq - (qq / W) * W : 0, la0 = 2 * pr;
                 const float* t0 = S + la0 * RSs + ox * PSs;  // tap rows la0 .. la0 + 3
-                df32x16 D0[NT], D1[NT];
+                f32x16 D0[NT], D1[NT];
 #pragma unroll
                 for (int m = 0; m < NT; m++)
 #pragma unroll
                     for (int e = 0; e < 16; e++) { D0[m][e] = 0.f; D1[m][e] = 0.f; }
                 for (int j = 0; j < nchk; j++) {
                     const int c0 = h * Chh + 4 * j;
-                    const float4 bb = dld4(bdw + c0);
+                    const float4 bb = ld4(bdw + c0);
                     float4 bf0 = bb, bf1 = bb;
                     // data row r feeds tap row r of the upper pixel and tap row r - 1 of the lower one (same tap order as the one-row form)
                     float4 wprev[3];
@@ -210,20 +180,20 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
                         float4 d[3], wr[3];
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) {
-                            d[kx] = dld4(t0 + r * RSs + kx * PSs + c0);
-                            if (r < 3) wr[kx] = dld4(wdw + (r * 3 + kx) * Cpad + c0);
+                            d[kx] = ld4(t0 + r * RSs + kx * PSs + c0);
+                            if (r < 3) wr[kx] = ld4(wdw + (r * 3 + kx) * Cpad + c0);
                         }
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) {
-                            if (r < 3) { bf0.x = fmaf(d[kx].x, wr[kx].x, bf0.x); bf0.y = fmaf(d[kx].y, wr[kx].y, bf0.y); bf0.z = fmaf(d[kx].z, wr[kx].z, bf0.z); bf0.w = fmaf(d[kx].w, wr[kx].w, bf0.w); }
-                            if (r > 0) { bf1.x = fmaf(d[kx].x, wprev[kx].x, bf1.x); bf1.y = fmaf(d[kx].y, wprev[kx].y, bf1.y); bf1.z = fmaf(d[kx].z, wprev[kx].z, bf1.z); bf1.w = fmaf(d[kx].w, wprev[kx].w, bf1.w); }
+                            if (r < 3) fma4(d[kx], wr[kx], bf0);
+                            if (r > 0) fma4(d[kx], wprev[kx], bf1);
                         }
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) wprev[kx] = wr[kx];
                     }
 #pragma unroll
                     for (int m = 0; m < NT; m++) {
-                        const float4 av = dld4(wL + ((m * nchk + j) * 64 + lane) * 4);
+                        const float4 av = ld4(wL + ((m * nchk + j) * 64 + lane) * 4);  // the two rows' MFMAs alternate: not two mfma32_quad calls, which would issue quad after quad
                         D0[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bf0.x, D0[m], 0, 0, 0);
                         D1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bf1.x, D1[m], 0, 0, 0);
                         D0[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bf0.y, D0[m], 0, 0, 0);
@@ -269,13 +239,13 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
         }
         if (item + (int)gridDim.x < total) prefetch(item + gridDim.x);  // the next band's rows travel under this band's work
         MI_DB_STAMP(2)
-        wg_barrier();
+        lds_barrier();
         MI_DB_STAMP(3)
         // ---- stage 1: a on rows [r0 - 1, r0 + RB + 1) (rows outside the image: zeros)
         stage(std::integral_constant<int, MTA>{}, std::true_type{}, std::true_type{}, g.pair1 != 0, g.RB + 2, r0 - 1, xt, g.RSx, g.PSx, g.Cp, nch1, cst, cst + o_bdw1, w1L,
               cst + o_b1, cst + o_sl1, a.hi1, a.Cm, a.skip1 ? xt : nullptr, g.RSx, g.PSx, 1, a.C, at, nullptr);
         MI_DB_STAMP(4)
-        wg_barrier();
+        lds_barrier();
         MI_DB_STAMP(5)
         // ---- stage 2: y on rows [r0, r0 + RB) inside the image; its skip is x (double block) or a (a pair of BlazeBlocks)
         stage(std::integral_constant<int, MT>{}, std::false_type{}, std::integral_constant<bool, (MT <= 2)>{}, g.pair2 != 0, min(g.RB, a.H - r0), r0, at, g.RSa, g.PSa, g.Cmp, nch2, cst + o_wdw2, cst + o_bdw2, w2L,
@@ -284,7 +254,7 @@ __global__ __launch_bounds__(512, 2) void dblock_kernel(DblockArgs a, DblockGeom
         MI_DB_STAMP(6)
         item += gridDim.x;
         if (item >= total) break;
-        wg_barrier();  // the next band overwrites both tensors
+        lds_barrier();  // the next band overwrites both tensors
     }
 }
 
@@ -316,7 +286,7 @@ bool make_dblock_geom(const DblockArgs& a, DblockGeom* out) {
     for (int r = std::min(std::min(a.H, 32), cap); r >= 1; r--) {
         const long fl = (long)(r + 4) * g.RSx + (long)(r + 2) * g.RSa + g.cfl + wfl + 16;
         const long n4 = (long)(r + 4) * a.W * (a.C / 4);
-        if (fl * 4 <= 160 * 1024 - 256 && n4 <= (long)kDbPrefetch * 512) { RB = r; break; }
+        if (fl * 4 <= kLdsBudget && n4 <= (long)kDbPrefetch * 512) { RB = r; break; }
     }
     if (RB < 2) return false;
     // stage 1 with two rows per lane needs an even band height; worth it when it shortens the busiest wave's share (a pair group
@@ -342,21 +312,16 @@ bool make_dblock_geom(const DblockArgs& a, DblockGeom* out) {
     g.off_w1 = off; off += 32 * MTA * g.Cp;
     g.off_w2 = off; off += 32 * MT * g.Cmp;
     g.lds_bytes = off * 4;
-    if (g.lds_bytes > 160 * 1024 - 256) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (g.lds_bytes > kLdsBudget) return false;
     if (!aligned16(a.in) || !aligned16(a.out) || !aligned16(a.w1) || !aligned16(a.w2) || !a.consts || (a.in_fs & 3) || (a.out_fs & 3)) return false;
     *out = g;
     return true;
 }
 
-int dblock_cu_count() { return device_cu_count(); }  // launch.hpp: per device
-
 template <int MT, int MTA>
 int launch_dblock_inst(const DblockArgs& a, const DblockGeom& g, hipStream_t s) {
-    auto kern = dblock_kernel<MT, MTA>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)std::min<long>((long)a.B * g.bands, dblock_cu_count());
-    return (int)launch_kernel(kern, dim3(grid), dim3(512), (size_t)g.lds_bytes, s, a, g);
+    const unsigned grid = (unsigned)std::min<long>((long)a.B * g.bands, device_cu_count());
+    return launch_full_lds(dblock_kernel<MT, MTA>, dim3(grid), dim3(512), (size_t)g.lds_bytes, s, a, g);
 }
 
 }  // namespace

@@ -126,7 +126,6 @@ __global__ __launch_bounds__(256) void transpose_tiled_kernel(const float* __res
 }
 
 inline unsigned nblocks(long n) { return (unsigned)((n + 255) / 256); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -139,7 +138,7 @@ int launch_avgpool(const EltArgs& a, void* s) {
     const int tph = (a.Ho - 1) * a.p2 + a.p0 - a.H, tpw = (a.Wo - 1) * a.p3 + a.p1 - a.W;
     const int pt = tph > 0 ? tph / 2 : 0, pl = tpw > 0 ? tpw / 2 : 0;
     if (n >= (1L << 31) * 256) return (int)hipErrorInvalidValue;
-    if (a.C % 4 == 0 && a.a_fs % 4 == 0 && a.out_fs % 4 == 0 && al16(a.a) && al16(a.out))
+    if (a.C % 4 == 0 && a.a_fs % 4 == 0 && a.out_fs % 4 == 0 && aligned16(a.a) && aligned16(a.out))
         return (int)launch_kernel(avgpool_kernel<4>, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)s, a, pt, pl);
     return (int)launch_kernel(avgpool_kernel<1>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)s, a, pt, pl);
 }

@@ -19,6 +19,7 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
 #include "roi_dev.hpp"
 
 namespace mi {
@@ -729,9 +730,6 @@ int launch_dw(const DwArgs& a, void* stream) {
 // out[b][n] = act(bias[n] + sum_k x[b][k] * W[n][k]) on v_mfma_f32_32x32x2_f32: one wave per 32 frames x 32 outputs.  The
 // contraction index is split in two halves (lanes 0-31 take k in [0, K/2), lanes 32-63 take [K/2, K)), so every lane reads
 // its operands as float4 of four consecutive k: four MFMAs per pair of 16-byte loads, both operands straight from L2.
-typedef float hg_f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 __global__ __launch_bounds__(256) void head_gemm_kernel(HeadGemmArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n0 = (blockIdx.x * 4 + wave) * 32, b0 = blockIdx.y * 32;
@@ -739,17 +737,14 @@ __global__ __launch_bounds__(256) void head_gemm_kernel(HeadGemmArgs a) {
     const int r = lane & 31, h = lane >> 5, K2 = a.K >> 1;
     const float* xp = a.in + (long)min(b0 + r, a.B - 1) * a.in_fs + h * K2;   // rows past the batch / the outputs re-read the
     const float* wp = a.w + (long)min(n0 + r, a.N - 1) * a.K + h * K2;        // last valid one; their results are not stored
-    hg_f32x16 D;
+    f32x16 D;
 #pragma unroll
     for (int e = 0; e < 16; e++) D[e] = 0.f;
     float4 xa = ld4(xp), wa = ld4(wp);
     for (int j = 0; j < K2; j += 4) {
         const int jn = min(j + 4, K2 - 4);
         const float4 xn = ld4(xp + jn), wn = ld4(wp + jn);  // next chunk in flight under this chunk's MFMAs
-        D = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.x, wa.x, D, 0, 0, 0);
-        D = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.y, wa.y, D, 0, 0, 0);
-        D = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.z, wa.z, D, 0, 0, 0);
-        D = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.w, wa.w, D, 0, 0, 0);
+        mfma32_quad(xa, wa, D);
         xa = xn; wa = wn;
     }
     // D[v]: frame b0 + 4 * h + 8 * (v / 4) + v % 4, output n0 + r
@@ -797,7 +792,7 @@ __global__ __launch_bounds__(256) void head_dot_kernel(HeadGemmArgs a) {
 bool head_gemm_supports(int K, int N) { return K >= 16 && (K % 8) == 0 && N >= 1; }
 
 int launch_head_gemm(const HeadGemmArgs& a, void* stream) {
-    if (!head_gemm_supports(a.K, a.N) || a.B < 1 || (a.in_fs & 3) || (reinterpret_cast<uintptr_t>(a.in) & 15) || (reinterpret_cast<uintptr_t>(a.w) & 15))
+    if (!head_gemm_supports(a.K, a.N) || a.B < 1 || (a.in_fs & 3) || !aligned16(a.in) || !aligned16(a.w))
         return (int)hipErrorInvalidValue;
     if (a.B <= 4 && !a.one_form) return (int)launch_kernel(head_dot_kernel, dim3((unsigned)((a.N + 3) / 4), (unsigned)a.B), dim3(256), 0, (hipStream_t)stream, a);
     const unsigned tiles_n = (unsigned)((a.N + 31) / 32);
@@ -940,8 +935,7 @@ int launch_affine(const EltArgs& a, void* s) {
     const long n = (long)a.B * a.H * a.W * a.C;
     if (n <= 0) return 0;
     if (!a.b || !a.shift || (a.act == ACT_PRELU && !a.alpha)) return (int)hipErrorInvalidValue;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool v4 = a.C % 4 == 0 && a.a_fs % 4 == 0 && a.out_fs % 4 == 0 && al16(a.a) && al16(a.out) && al16(a.b) && al16(a.shift);
+    const bool v4 = a.C % 4 == 0 && a.a_fs % 4 == 0 && a.out_fs % 4 == 0 && aligned16(a.a) && aligned16(a.out) && aligned16(a.b) && aligned16(a.shift);
     if (a.div) {
         if (v4) return (int)launch_kernel(affine_kernel<4, true>, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)s, a);
         return (int)launch_kernel(affine_kernel<1, true>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)s, a);

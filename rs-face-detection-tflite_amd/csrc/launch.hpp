@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdint>
 #include <map>
 #include <mutex>
 #include <set>
@@ -96,6 +97,13 @@ inline int device_cu_count() {
     return v;
 }
 
+// the CU's LDS, and what the kernels' geometries plan with (256 bytes of slack)
+constexpr int kLdsBytes = 160 * 1024;
+constexpr int kLdsBudget = kLdsBytes - 256;
+
+// the 16-byte loads and stores of the kernels want their tensors and blobs on 16-byte addresses
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize = the CU's 160 KB) once per (kernel, device)
 inline hipError_t allow_full_lds(const void* func) {
     static std::mutex m;
@@ -105,9 +113,16 @@ inline hipError_t allow_full_lds(const void* func) {
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lock(m);
     if (done.count({func, dev})) return hipSuccess;
-    e = hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    e = hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     if (e == hipSuccess) done.insert({func, dev});
     return e;
+}
+
+// a launch with up to the whole LDS as dynamic shared memory: allow_full_lds, then launch_kernel.  Returns the status as the C ABI's int.
+template <typename... KArgs, typename... Args>
+inline int launch_full_lds(void (*kern)(KArgs...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, Args&&... args) {
+    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
+    return (int)launch_kernel(kern, grid, block, lds_bytes, s, std::forward<Args>(args)...);
 }
 
 inline hipError_t record_event(hipEvent_t ev, hipStream_t s) {

@@ -486,7 +486,7 @@ int mdb_launch(const DblockArgs& a, hipStream_t s) {
     // bands: enough workgroups for every CU to hold as many as its LDS takes; a band costs four priming steps
     static const int forced = getenv("MI_MDB_BAND") ? atoi(getenv("MI_MDB_BAND")) : 0;  // tuning aid
     // (the pair form on 16 channels needs ~160 registers: three waves per SIMD)
-    const int per_cu = std::max(1, std::min((K::PAIR ? 12 : 8) / K::NWV, (int)((160 * 1024) / (K::LDS_F * 4))));
+    const int per_cu = std::max(1, std::min((K::PAIR ? 12 : 8) / K::NWV, (int)(kLdsBytes / (K::LDS_F * 4))));
     long bands = std::max<long>(1, ((long)per_cu * device_cu_count() + a.B / 2) / std::max(1, a.B));
     int rows = (int)((a.H + bands - 1) / bands);
     rows = std::max(rows, std::min(a.H, 8));
@@ -550,7 +550,6 @@ bool mdblock_kernel_supports(const DblockArgs& a) {
     // the waves of a band walk it row by row: below about one workgroup per CU the launch is latency-bound and the wider kernel finishes sooner
     static const int min_b = getenv("MI_MDB_MIN_B") ? atoi(getenv("MI_MDB_MIN_B")) : 32;
     if (a.B < min_b) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (a.stem_in)   // the pair behind the first convolution, which runs inside the launch: `in` is not read
         return mdb_shape(a.W, a.C, a.Cm, a.Co, true) == 5 && a.H == 96 && a.stem_consts && aligned16(a.stem_in) && aligned16(a.stem_consts) && !(a.stem_in_fs & 3) &&
                aligned16(a.out) && aligned16(a.mconsts) && !(a.out_fs & 3);
@@ -609,7 +608,6 @@ bool mbneck_kernel_supports(const BneckArgs& a) {
     if (a.nblocks != 1 || !a.blocks[0].mconsts || !mbneck_shape_ok(a.W, a.C, a.Cm) || a.H < 2) return false;
     static const int min_b = getenv("MI_MDB_MIN_B") ? atoi(getenv("MI_MDB_MIN_B")) : 32;
     if (a.B < min_b) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     return aligned16(a.in) && aligned16(a.out) && aligned16(a.blocks[0].mconsts) && !(a.in_fs & 3) && !(a.out_fs & 3);
 }
 
@@ -622,7 +620,7 @@ int launch_mbneck(const BneckArgs& a, void* stream) {
     ma.hi1 = a.blocks[0].hi1; ma.hi2 = a.blocks[0].hi2;
     static const int forced = getenv("MI_MBN_BAND") ? atoi(getenv("MI_MBN_BAND")) : 0;  // tuning aid
     const int groups = (a.B + K::NF - 1) / K::NF;
-    const int per_cu = std::max(1, std::min(8 / (K::NF * K::NWV), (int)((160 * 1024) / (K::LDS_F * 4))));
+    const int per_cu = std::max(1, std::min(8 / (K::NF * K::NWV), (int)(kLdsBytes / (K::LDS_F * 4))));
     long bands = std::max<long>(1, ((long)per_cu * device_cu_count() + groups / 2) / std::max(1, groups));
     int rows = (int)((a.H + bands - 1) / bands);
     rows = std::max(rows, std::min(a.H, 8));

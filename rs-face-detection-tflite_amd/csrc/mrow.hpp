@@ -23,7 +23,9 @@ namespace {
 
 typedef float df32x4 __attribute__((ext_vector_type(4)));
 
-// workgroup barrier behind an LDS-only wait (__syncthreads() would also drain vmcnt: the next row's DMA and the output stores)
+// workgroup barrier behind an LDS-only wait (__syncthreads() would also drain vmcnt: the next row's DMA and the output stores).
+// Not wave_sync.hpp's lds_barrier: this one is a single asm statement, so the compiler's own wait counting does not see the wait; with
+// lds_barrier in its place mdblock_kernel<MD<4,4,1,2,3,true,8,..,PAIR,STEM>> has 183 / 185 s_waitcnt instead of 193 / 196.
 __device__ __forceinline__ void dwg_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
@@ -463,8 +465,7 @@ inline void mrow_pack_bias(float* dst_bias, float* dst_slope, int Co, int C, con
 template <class A>
 inline int mrow_launch(void (*k_relu)(A), void (*k_any)(A), bool relu, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const A& args) {
     void (*kern)(A) = relu ? k_relu : k_any;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, grid, block, lds_bytes, s, args);
+    return launch_full_lds(kern, grid, block, lds_bytes, s, args);
 }
 
 }  // namespace

@@ -272,7 +272,7 @@ int ms2_launch(const BlockArgs& a, hipStream_t s) {
     ma.hi = a.ep.act == ACT_RELU6 ? 6.f : INFINITY;
     static const int forced = getenv("MI_MS2_BAND") ? atoi(getenv("MI_MS2_BAND")) : 0;  // tuning aid (output rows per band)
     const int groups = (a.B + K::NF - 1) / K::NF;
-    const int per_cu = std::max(1, std::min(8 / (K::NF * K::NWV), (int)((160 * 1024) / (K::LDS_F * 4))));
+    const int per_cu = std::max(1, std::min(8 / (K::NF * K::NWV), (int)(kLdsBytes / (K::LDS_F * 4))));
     long bands = std::max<long>(1, ((long)per_cu * device_cu_count() + groups / 2) / std::max(1, groups));
     int rows = (int)((a.Ho + bands - 1) / bands);
     rows = std::max(rows, std::min(a.Ho, 6));
@@ -330,7 +330,6 @@ bool ms2_kernel_supports(const BlockArgs& a) {
     if (!ms2_shape(a.W, a.C, a.Co, skip)) return false;
     static const int min_b = getenv("MI_MS2_MIN_B") ? atoi(getenv("MI_MS2_MIN_B")) : 32;
     if (a.B < min_b) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     return aligned16(a.in) && aligned16(a.out) && aligned16(a.w_mwalk) && !(a.in_fs & 3) && !(a.out_fs & 3);
 }
 

@@ -296,7 +296,6 @@ bool mstrip_kernel_supports(const BlockArgs& a) {
     // latency-bound and the block kernel's wider workgroups finish sooner (B = 5: 14.3 against 11 us)
     static const int min_b = getenv("MI_MSTRIP_MIN_B") ? atoi(getenv("MI_MSTRIP_MIN_B")) : 32;
     if (a.B < min_b) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     return aligned16(a.in) && aligned16(a.out) && !(a.in_fs & 3) && !(a.out_fs & 3);
 }
 

@@ -207,7 +207,6 @@ bool mwalk_kernel_supports(const BlockArgs& a) {
     // (the 24-pixel rows fill 1.5 of their 2 tiles: 0.0211 against the block kernel's 0.0201 ms at 64 frames, 0.0233 / 0.0322 at 128)
     static const int min_b = getenv("MI_MWALK_MIN_B") ? atoi(getenv("MI_MWALK_MIN_B")) : 0;
     if (a.B < (min_b > 0 ? min_b : (mw_shape(a.W, a.C, a.Co) == 2 ? 96 : 32))) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     return aligned16(a.in) && aligned16(a.out) && aligned16(a.w_mwalk) && !(a.in_fs & 3) && !(a.out_fs & 3);
 }
 

@@ -33,27 +33,17 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
 #include "wave_sync.hpp"
 
 namespace mi {
 
 namespace {
 
-typedef float rf32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float4 rld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 rmax4(float4 a, float4 b, float4 c, float4 d) {
-    return make_float4(fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x)), fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y)),
-                       fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z)), fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w)));
-}
-__device__ __forceinline__ float* resolve(const ResBases& bs, const ResRef& r, int frame) {
-    return bs.p[r.base] + r.root_off * bs.scale[r.base] + r.inner + (long)(frame + bs.frame0[r.base]) * r.fs;
-}
-
 #ifdef MI_RES_STAMPS
 unsigned long long* g_res_stamps = nullptr;  // [workgroup][stage][8]: stage start, constants issued, units done, stage end; wave 0's first unit: start, ring issued, MFMA loop done, epilogue done (s_memtime)
 #define MI_RES_STAMP(k) if (stamps && tid == 0) stamps[((long)blockIdx.x * nstages + s) * 8 + (k)] = __builtin_amdgcn_s_memtime();
-#define MI_RES_USTAMP(k) if (ustamps && threadIdx.x == 0 && u == 0) { __builtin_amdgcn_sched_barrier(0); ustamps[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+#define MI_RES_USTAMP(k) if (ustamps && threadIdx.x == 0 && u == 0) MI_STAMP_AT(ustamps[k])
 #else
 #define MI_RES_STAMP(k)
 #define MI_RES_USTAMP(k)
@@ -97,10 +87,10 @@ __device__ __forceinline__ EpiView make_epi(const ResStage& st, const ResBases& 
     EpiView e;
     e.Ho = st.Ho; e.Wo = st.Wo; e.Co = st.Co; e.MT = (st.Co + 31) >> 5;
     e.dst_lds = st.dst_off >= 0; e.dst_off = st.dst_off; e.dst_b = st.dst_b; e.dst_row = st.Wo + 2 * st.dst_b; e.dst_PS = st.dst_PS;
-    e.dstg = st.dst_g.base >= 0 ? resolve(bs, st.dst_g, frame) : nullptr;
+    e.dstg = st.dst_g.base >= 0 ? res_resolve(bs, st.dst_g, frame) : nullptr;
     e.res_mode = st.res_mode; e.res_C = st.res_C; e.res_off = st.res_off; e.res_b = st.res_b; e.res_W = st.res_W;
     e.res_row = st.res_W + 2 * st.res_b; e.res_PS = st.res_PS;
-    e.resg = (st.res_mode != RES_NONE && st.res_off < 0) ? resolve(bs, st.res_g, frame) : nullptr;
+    e.resg = (st.res_mode != RES_NONE && st.res_off < 0) ? res_resolve(bs, st.res_g, frame) : nullptr;
     e.hi = st.act == ACT_RELU6 ? 6.f : INFINITY;
     e.wpw = bs.weights + st.w_pw;
     return e;
@@ -138,7 +128,7 @@ __device__ __forceinline__ void run_units(const EpiView& ep, const SrcView& sv, 
         const int qq = valid ? q : 0;
         const int oy = dWo.div(qq), ox = qq - oy * ep.Wo;
         MI_RES_USTAMP(4)
-        rf32x16 D;
+        f32x16 D;
 #pragma unroll
         for (int e = 0; e < 16; e++) D[e] = 0.f;
 
@@ -146,7 +136,7 @@ __device__ __forceinline__ void run_units(const EpiView& ep, const SrcView& sv, 
         // A fragments: a plain pointer walk; past the tile's last chunk it runs into the next tile / the next constant of the
         // weights blob (never used; the blob ends with slack for it)
         auto a_next = [&]() -> float4 {
-            const float4 v = rld4(wa);
+            const float4 v = ld4(wa);
             wa += 256;
             return v;
         };
@@ -158,27 +148,21 @@ __device__ __forceinline__ void run_units(const EpiView& ep, const SrcView& sv, 
         const float* bp = lds + pix_base + v_first;  // CONTIG: weights of padded channels are zero and so are the LDS pad lanes
         auto b_next = [&]() -> float4 {
             if (CONTIG) {
-                const float4 v = rld4(bp);
+                const float4 v = ld4(bp);
                 bp += 4;
                 return v;
             }
             const bool ok = bv < sv.Kv;
             const long a = pix_base + (ok ? btap + bc : 0);
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (MODE == 1) { if (ok) v = rld4(sv.g + a); }
-            else { v = rld4(lds + a); if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f); }
+            if (MODE == 1) { if (ok) v = ld4(sv.g + a); }
+            else { v = ld4(lds + a); if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f); }
             bv += 4; bc += 4;
             if (bc >= sv.C) {
                 bc = 0; bkx++; btap += sv.PS;
                 if (bkx == sv.KW) { bkx = 0; btap += (long)(sv.row - sv.KW) * sv.PS; }
             }
             return v;
-        };
-        auto mfma4 = [&](const float4& av, const float4& bf) {
-            D = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bf.x, D, 0, 0, 0);
-            D = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bf.y, D, 0, 0, 0);
-            D = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bf.z, D, 0, 0, 0);
-            D = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bf.w, D, 0, 0, 0);
         };
 
         if constexpr (MODE == 3) {
@@ -196,19 +180,19 @@ __device__ __forceinline__ void run_units(const EpiView& ep, const SrcView& sv, 
             float4 ringA3[4];
 #pragma unroll
             for (int r = 0; r < 4; r++) ringA3[r] = a_next();
-            float4 x0 = rld4(g0), x1 = rld4(g1);
+            float4 x0 = ld4(g0), x1 = ld4(g1);
             auto do_block = [&](float4& A0, float4& A1, int b) {  // A0 / A1: the ring slots of chunks 2b and 2b + 1 (static registers)
                 *reinterpret_cast<float4*>(w0) = x0;
                 *reinterpret_cast<float4*>(w0 + 16 * SP) = x1;
                 const int bn = min(b + 1, nblk - 1);  // the next block's pixels are on their way while this one is contracted
-                x0 = rld4(g0 + 16 * bn);
-                x1 = rld4(g1 + 16 * bn);
+                x0 = ld4(g0 + 16 * bn);
+                x1 = ld4(g1 + 16 * bn);
                 wave_sync();
-                const float4 b0 = rld4(rd), b1 = rld4(rd + 4);
+                const float4 b0 = ld4(rd), b1 = ld4(rd + 4);
                 wave_sync();  // the slab may be rewritten once every lane has read it (LDS executes a wave's accesses in order)
-                mfma4(A0, b0);
+                mfma32_quad(A0, b0, D);
                 A0 = a_next();
-                mfma4(A1, b1);
+                mfma32_quad(A1, b1, D);
                 A1 = a_next();
             };
             int b = 0;
@@ -232,11 +216,11 @@ __device__ __forceinline__ void run_units(const EpiView& ep, const SrcView& sv, 
 #pragma unroll
             for (int r = 0; r < PF; r++) {  // no control flow around the loads: slot r is consumed, then refilled PF chunks ahead
                 if (MODE == 1) {
-                    mfma4(ringA[r], ringB[MODE == 1 ? r : 0]);
+                    mfma32_quad(ringA[r], ringB[MODE == 1 ? r : 0], D);
                     ringB[MODE == 1 ? r : 0] = b_next();
                 } else {
                     const float4 bn = b_next();
-                    mfma4(ringA[r], bcur);
+                    mfma32_quad(ringA[r], bcur, D);
                     bcur = bn;
                 }
                 ringA[r] = a_next();
@@ -246,10 +230,10 @@ __device__ __forceinline__ void run_units(const EpiView& ep, const SrcView& sv, 
         for (int r = 0; r < PF - 1; r++)
             if (r < rem) {
                 if (MODE == 1) {
-                    mfma4(ringA[r], ringB[MODE == 1 ? r : 0]);
+                    mfma32_quad(ringA[r], ringB[MODE == 1 ? r : 0], D);
                 } else {
                     const float4 bn = b_next();
-                    mfma4(ringA[r], bcur);
+                    mfma32_quad(ringA[r], bcur, D);
                     bcur = bn;
                 }
             }
@@ -269,35 +253,31 @@ __device__ __forceinline__ void run_units(const EpiView& ep, const SrcView& sv, 
                 const int ch = mt * 32 + 8 * gq + 4 * h;
                 on[gq] = ch < ep.Co;
                 const int chc = on[gq] ? ch : 0;
-                const float4 bb = rld4(biasL + chc), al = rld4(alphaL + chc);
-                float4 v = make_float4(D[4 * gq] + bb.x, D[4 * gq + 1] + bb.y, D[4 * gq + 2] + bb.z, D[4 * gq + 3] + bb.w);
+                const float4 bb = ld4(biasL + chc), al = ld4(alphaL + chc);
+                float4 v = add4(quad4(D, gq), bb);
                 if (ep.res_mode != RES_NONE && chc < ep.res_C) {
                     float4 rv;
                     if (ep.res_off >= 0) {
-                        if (ep.res_mode == RES_DIRECT) rv = rld4(rl + chc);
-                        else rv = rmax4(rld4(rl + chc), rld4(rl + ep.res_PS + chc), rld4(rl + ep.res_row * ep.res_PS + chc), rld4(rl + (ep.res_row + 1) * ep.res_PS + chc));
+                        if (ep.res_mode == RES_DIRECT) rv = ld4(rl + chc);
+                        else rv = max4(ld4(rl + chc), ld4(rl + ep.res_PS + chc), ld4(rl + ep.res_row * ep.res_PS + chc), ld4(rl + (ep.res_row + 1) * ep.res_PS + chc));
                     } else {
-                        if (ep.res_mode == RES_DIRECT) rv = rld4(rg + chc);
-                        else rv = rmax4(rld4(rg + chc), rld4(rg + ep.res_C + chc), rld4(rg + (long)ep.res_W * ep.res_C + chc), rld4(rg + (long)(ep.res_W + 1) * ep.res_C + chc));
+                        if (ep.res_mode == RES_DIRECT) rv = ld4(rg + chc);
+                        else rv = max4(ld4(rg + chc), ld4(rg + ep.res_C + chc), ld4(rg + (long)ep.res_W * ep.res_C + chc), ld4(rg + (long)(ep.res_W + 1) * ep.res_C + chc));
                     }
-                    v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
+                    v = add4(v, rv);
                 }
-                v.x = fminf(fmaxf(v.x, 0.f) + al.x * fminf(v.x, 0.f), ep.hi);
-                v.y = fminf(fmaxf(v.y, 0.f) + al.y * fminf(v.y, 0.f), ep.hi);
-                v.z = fminf(fmaxf(v.z, 0.f) + al.z * fminf(v.z, 0.f), ep.hi);
-                v.w = fminf(fmaxf(v.w, 0.f) + al.w * fminf(v.w, 0.f), ep.hi);
-                outv[gq] = v;
+                outv[gq] = act4(v, al, ep.hi);
             }
 #pragma unroll
             for (int gq = 0; gq < 4; gq++) {  // ... then the stores
                 if (!on[gq]) continue;
                 const int ch = mt * 32 + 8 * gq + 4 * h;
                 const float4 v = outv[gq];
-                if (dl) *reinterpret_cast<float4*>(dl + ch) = v;   // Co % 4 == 0 whenever the output stays in LDS (planner)
+                if (dl) st4(dl + ch, v);   // Co % 4 == 0 whenever the output stays in LDS (planner)
                 if (dg) {
                     if ((ep.Co & 3) == 0) {
                         *reinterpret_cast<float4*>(dg + ch) = v;
-                    } else {  // ragged output heads (213, 15, 1 channels)
+                    } else {  // ragged output heads (213, 15, 1 channels); written out: as store4_ragged the kernel has 394 s_waitcnt instead of 396
                         dg[ch] = v.x;
                         if (ch + 1 < ep.Co) dg[ch + 1] = v.y;
                         if (ch + 2 < ep.Co) dg[ch + 2] = v.z;
@@ -329,7 +309,7 @@ __global__ __launch_bounds__(512, 4) void resident_kernel(const ResStage* __rest
         const ResStage& st = prog[0];
         const int n4 = const_count(st) >> 2;
         const float* cb = bs.weights + (n4 > 0 ? st.cblob : 0);
-        for (int i = tid; i < n4; i += 512) reinterpret_cast<float4*>(lds + const_off)[i] = rld4(cb + 4 * (long)i);
+        for (int i = tid; i < n4; i += 512) reinterpret_cast<float4*>(lds + const_off)[i] = ld4(cb + 4 * (long)i);
         zero_dst(st);
     }
     __syncthreads();
@@ -349,18 +329,18 @@ __global__ __launch_bounds__(512, 4) void resident_kernel(const ResStage* __rest
 #pragma unroll
         for (int k = 0; k < kNPre; k++) {
             const int i = tid + 512 * k;
-            pre[k] = rld4(cnext + 4 * (long)min(i, max(npre - 1, 0)));
+            pre[k] = ld4(cnext + 4 * (long)min(i, max(npre - 1, 0)));
         }
         MI_RES_STAMP(1)
         if (st.kind == RES_STAGE_LOAD) {
-            const float* src = resolve(bs, st.src_g, frame);
+            const float* src = res_resolve(bs, st.src_g, frame);
             const int sW = st.src_W, C4 = st.src_C >> 2, n = st.src_H * sW * C4;
             const int db = st.dst_b, drow = sW + 2 * db, dPS = st.dst_PS, doff = st.dst_off;
             const Div dC4(C4), dW(sW);
             for (int i = tid; i < n; i += 512) {
                 const int px = dC4.div(i), c4 = i - px * C4;
                 const int y = dW.div(px), x = px - y * sW;
-                *reinterpret_cast<float4*>(lds + doff + ((y + db) * drow + x + db) * dPS + 4 * c4) = rld4(src + 4 * (long)i);
+                *reinterpret_cast<float4*>(lds + doff + ((y + db) * drow + x + db) * dPS + 4 * c4) = ld4(src + 4 * (long)i);
             }
         } else if (st.kind == RES_STAGE_DW) {
             EpiView ep = make_epi(st, bs, frame);
@@ -385,17 +365,15 @@ __global__ __launch_bounds__(512, 4) void resident_kernel(const ResStage* __rest
                     const int pxl = dC4p.div(it), c0 = 4 * (it - pxl * C4p);
                     const int q = px0 + pxl, oy = dWo.div(q), ox = q - oy * Wo;
                     const float* p = lds + src0 + (oy * S * srow + ox * S) * sPS + c0;
-                    float4 acc = rld4(cst + 9 * Cp + c0);  // weights and the LDS pad lanes are zero above the real channel count
+                    // the loop stays here (fma4 only): as dw3x3_quad + st4 the kernel spills 15 VGPRs instead of 9 and merges two LDS writes
+                    float4 acc = ld4(cst + 9 * Cp + c0);  // weights and the LDS pad lanes are zero above the real channel count
 #pragma unroll
                     for (int ky = 0; ky < 3; ky++)
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) {
-                            const float4 w = rld4(cst + (ky * 3 + kx) * Cp + c0);
-                            const float4 d = rld4(p + (ky * srow + kx) * sPS);
-                            acc.x = fmaf(d.x, w.x, acc.x);
-                            acc.y = fmaf(d.y, w.y, acc.y);
-                            acc.z = fmaf(d.z, w.z, acc.z);
-                            acc.w = fmaf(d.w, w.w, acc.w);
+                            const float4 w = ld4(cst + (ky * 3 + kx) * Cp + c0);
+                            const float4 d = ld4(p + (ky * srow + kx) * sPS);
+                            fma4(d, w, acc);
                         }
                     *reinterpret_cast<float4*>(lds + dw_off + pxl * PSs + c0) = acc;
                 }
@@ -422,7 +400,7 @@ __global__ __launch_bounds__(512, 4) void resident_kernel(const ResStage* __rest
                 if (sv.KW == 1) run_units<2>(ep, sv, lds, cst, 0, PGn, ust);
                 else run_units<0>(ep, sv, lds, cst, 0, PGn, ust);
             } else {
-                sv.g = resolve(bs, st.src_g, frame) + src_rows * st.src_W * st.src_C; sv.off = 0; sv.row = st.src_W; sv.PS = st.src_C; sv.b = 0;
+                sv.g = res_resolve(bs, st.src_g, frame) + src_rows * st.src_W * st.src_C; sv.off = 0; sv.row = st.src_W; sv.PS = st.src_C; sv.b = 0;
                 sv.slab = st.dw_off;
                 if (st.kblk == 16) run_units<3>(ep, sv, lds, cst, 0, PGn, ust);
                 else run_units<1>(ep, sv, lds, cst, 0, PGn, ust);
@@ -455,14 +433,13 @@ int resident_const_floats(const ResStage& st) {
 }
 
 int launch_resident(const ResLaunch& a, void* stream) {
-    if (!a.prog || a.nstages < 1 || a.B < 1 || a.bands < 1 || a.lds_bytes > 160 * 1024 || a.const_floats > kResConstMax) return (int)hipErrorInvalidValue;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(resident_kernel)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(resident_kernel, dim3((unsigned)(a.B * a.bands)), dim3(512), (size_t)a.lds_bytes, (hipStream_t)stream, a.prog, a.nstages,
-                              a.const_off, a.const_floats, a.bands, a.bases,
+    if (!a.prog || a.nstages < 1 || a.B < 1 || a.bands < 1 || a.lds_bytes > kLdsBytes || a.const_floats > kResConstMax) return (int)hipErrorInvalidValue;
+    return launch_full_lds(resident_kernel, dim3((unsigned)(a.B * a.bands)), dim3(512), (size_t)a.lds_bytes, (hipStream_t)stream, a.prog, a.nstages,
+                           a.const_off, a.const_floats, a.bands, a.bases,
 #ifdef MI_RES_STAMPS
-                              g_res_stamps
+                           g_res_stamps
 #else
-                              nullptr
+                           nullptr
 #endif
     );
 }

@@ -1063,17 +1063,8 @@ __device__ __forceinline__ void strip_hand_row(float* lds, int image, int img_p,
         for (int q = 0; q < CQ; q++) sst4(dstl + 4 * q, lane >= npx ? z : o[q]);
     }
 }
-// workgroup barrier between steps: raw s_barrier with an LDS-only wait, so that the stores of the last block and the DMA of block 0
-// stay in flight across it
-// (MI_ABL_NOBAR, a timing ablation of the two-row forms, now also drops strip_pipe_kernel's barrier, which had no such switch of its own)
-__device__ __forceinline__ void wg_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-#ifndef MI_ABL_NOBAR
-    __builtin_amdgcn_s_barrier();
-#endif
-    asm volatile("" ::: "memory");
-}
+// (the workgroup barrier between steps is wave_sync.hpp's lds_barrier: the stores of the last block and the DMA of block 0 stay in flight
+// across it; MI_ABL_NOBAR, a timing ablation of the two-row forms, also drops strip_pipe_kernel's barrier)
 // stride-2 tail: one wave serves both strips (W > 64: lane = output column) or both units (W <= 64: 32 lanes each); this lane's first
 // tap column in the full-width row image `img`
 template <int PXS>
@@ -1268,7 +1259,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
             if (tail) tail_step(t, tacc, tmx);
         }
         if (hand_over) strip_hand_row<CQ, C>(lds, role * SLOTS + (t & 1), img_p, lane, a.H, full, npx, e, o);
-        wg_barrier();
+        lds_barrier();
     };
     const int T = NH2 ? a.band_rows + 3 * S + 1 : a.band_rows + 3 * S - 1;
     for (int t = 0; t < T; t += 2) {
@@ -1611,7 +1602,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
             if (tail) tail_step(t, tacc, tmx);
         }
         MI_PSTAMP(0)
-        wg_barrier();  // every reader of the previous pair is done
+        lds_barrier();  // every reader of the previous pair is done
         MI_PSTAMP(1)
         if (hand_over) {
             hand_row(c0 - 1, 0, o0);
@@ -1621,7 +1612,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
             store_row(c0, o1);
         }
         MI_PSTAMP(2)
-        wg_barrier();
+        lds_barrier();
         MI_PSTAMP(3)
     };
     const int T = NH2 ? 2 * S + a.band_rows / 2 + 1 : 2 * S - 1 + a.band_rows / 2;
@@ -1864,7 +1855,7 @@ __global__ __launch_bounds__(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB, 2) void
         MI_PSTAMP(1)
         MI_PSTAMP(2)
 #else
-        wg_barrier();  // every reader of the previous pair is done
+        lds_barrier();  // every reader of the previous pair is done
         MI_PSTAMP(1)
         if (hand_over) {
             hand_row(c0 - 1, 0, o0);
@@ -1898,9 +1889,8 @@ int launch_pipe_inst(const PipeArgs& pa, hipStream_t s) {
               : (rps == 3 ? strip_pipe2m_kernel<CQ, KB, RELU, NH2> : (two ? strip_pipe2_kernel<CQ, KB, RELU, NH2> : strip_pipe_kernel<CQ, KB, RELU, NH2>));
     // rings + per strip / unit the DMA row buffers of block 0 + one transposition buffer for the waves that store
     const size_t lds_bytes = (size_t)((KB - 1) * 2 * 132 * (mf ? K::C + 4 : K::C) + (two ? 10 : 6) * K::BUF_F) * 4;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
     const int wgs = pa.strips == 2 ? pa.units : (pa.units + 1) / 2;
-    return (int)launch_kernel(kern, dim3((unsigned)wgs), dim3(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB), lds_bytes, s, pa);
+    return launch_full_lds(kern, dim3((unsigned)wgs), dim3(NH2 ? 128 * (KB - 1) + 64 * NH2 : 128 * KB), lds_bytes, s, pa);
 }
 
 unsigned long long* g_strip_stamps = nullptr;  // set by the development harness (MI_STRIP_STAMPS builds)
@@ -1937,8 +1927,7 @@ int launch_strip_inst(const BlockArgs& a, hipStream_t s) {
     sa.stamps = g_strip_stamps;
     const long waves = (long)a.B * sa.strips * sa.bands;
     const size_t lds_bytes = (size_t)4 * K::WAVE_F * 4;  // 4 waves x 2 row buffers
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), lds_bytes, s, sa);
+    return launch_full_lds(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), lds_bytes, s, sa);
 }
 
 }  // namespace
@@ -1953,7 +1942,6 @@ bool strip_kernel_supports(const BlockArgs& a) {
         if (a.ep.res_after) return false;  // skip behind the activation: block / generic kernels only
         if (a.ep.res_mode != RES_DIRECT || a.ep.res != a.in || a.ep.res_fs != a.in_fs || a.ep.res_C != a.C) return false;
     }
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!aligned16(a.in) || !aligned16(a.out) || (a.in_fs & 3) || (a.out_fs & 3)) return false;
     return true;
 }
@@ -2041,7 +2029,6 @@ static bool strip_tail_supports(const BlockArgs& t, const BlockArgs& first) {
     if (t.C != first.C || t.H != first.H || t.W != first.W || (t.H & 1) || (t.W & 1) || t.Ho * 2 != t.H || t.Wo * 2 != t.W) return false;
     if (t.Co != t.C && t.Co != 2 * t.C) return false;
     if (t.ep.res_mode != RES_NONE && (t.ep.res_mode != RES_MAXPOOL || t.ep.res_C != t.C || t.ep.res_H != t.H || t.ep.res_W != t.W)) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     return aligned16(t.out) && !(t.out_fs & 3);
 }
 

@@ -36,24 +36,13 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
 
 namespace mi {
 
 namespace {
 
 typedef float tf32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 tld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void tst4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 tmax4(float4 a, float4 b, float4 c, float4 d) {
-    return make_float4(fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x)), fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y)),
-                       fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z)), fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w)));
-}
-__device__ __forceinline__ float* tresolve(const ResBases& bs, const ResRef& r, int frame) {
-    return bs.p[r.base] + r.root_off * bs.scale[r.base] + r.inner + (long)(frame + bs.frame0[r.base]) * r.fs;
-}
-// n / d for n * d < 2^32 with m = ceil(2^32 / d) (host: tail_magic; m = 0 stands for d = 1)
-__device__ __forceinline__ int tdiv(int n, unsigned m) { return m ? (int)__umulhi((unsigned)n, m) : n; }
 
 // What the waves need to know about a stage, read from the descriptor once (scalar registers).
 struct TailView {
@@ -93,15 +82,15 @@ __device__ __forceinline__ void tail_prefetch(const TailStage& st, const float* 
     const int ct = nct >= 8 ? wave : wave % nct;
     const float* wa = weights + st.w_a + ((long)ct * n4 * 64 + lane) * 4;
 #pragma unroll
-    for (int i = 0; i < kTailPreA; i++) pf.A[i] = tld4(wa + 256 * i);   // (a tile of fewer steps: the loads run into the next tile / constant of the blob, which ends with slack)
+    for (int i = 0; i < kTailPreA; i++) pf.A[i] = ld4(wa + 256 * i);   // (a tile of fewer steps: the loads run into the next tile / constant of the blob, which ends with slack)
     const float* wc = weights + st.w_c + 16 * ct + 4 * kq;
-    pf.bias = tld4(wc);
-    pf.slope = tld4(wc + 16 * nct);
+    pf.bias = ld4(wc);
+    pf.slope = ld4(wc + 16 * nct);
 }
 
 #ifdef MI_TAIL_STAMPS
 unsigned long long* g_tail_stamps = nullptr;  // [workgroup][stage][4]: stage start, depthwise phase done, units done, closing barrier passed (s_memtime)
-#define MI_TAIL_STAMP(k) if (stamps && threadIdx.x == 0) { __builtin_amdgcn_sched_barrier(0); stamps[((long)blockIdx.x * nstages + s) * 4 + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+#define MI_TAIL_STAMP(k) if (stamps && threadIdx.x == 0) MI_STAMP_AT(stamps[((long)blockIdx.x * nstages + s) * 4 + (k)])
 #else
 #define MI_TAIL_STAMP(k)
 #endif
@@ -122,7 +111,7 @@ __device__ __forceinline__ void tail_group(const TailView& v, float4 (&A)[8], bo
     for (int u = 0; u < NPT; u++) {
         const int pc = min((tb + u < t1 ? tb + u : tb) * 16 + n, v.P - 1);
         if (v.gather2) {
-            const int f = tdiv(pc, v.mHW), q = pc - f * v.HW, oy = tdiv(q, v.mW), ox = q - oy * v.Wo;
+            const int f = magic_div(pc, v.mHW), q = pc - f * v.HW, oy = magic_div(q, v.mW), ox = q - oy * v.Wo;
             bp[u] = v.bsrc + (long)((f * v.sH + 2 * oy + (kq >> 1)) * v.sW + 2 * ox + (kq & 1)) * v.bPS;
         } else {
             bp[u] = v.bsrc + (long)pc * v.bPS + kq * K4;
@@ -136,16 +125,16 @@ __device__ __forceinline__ void tail_group(const TailView& v, float4 (&A)[8], bo
     for (int kb = 0; kb < nkb; kb++) {
         if (kb > 0 || !a0) {
 #pragma unroll
-            for (int i = 0; i < N4; i++) A[i] = tld4(wa + 256 * (kb * N4 + i));
+            for (int i = 0; i < N4; i++) A[i] = ld4(wa + 256 * (kb * N4 + i));
         }
         float4 b[NPT][2];   // the B operands of step i + 1 are on their way while step i's MFMAs run
 #pragma unroll
-        for (int u = 0; u < NPT; u++) b[u][0] = tld4(bp[u] + 4 * N4 * kb);
+        for (int u = 0; u < NPT; u++) b[u][0] = ld4(bp[u] + 4 * N4 * kb);
 #pragma unroll
         for (int i = 0; i < N4; i++) {
             if (i + 1 < N4) {
 #pragma unroll
-                for (int u = 0; u < NPT; u++) b[u][(i + 1) & 1] = tld4(bp[u] + 4 * (N4 * kb + i + 1));
+                for (int u = 0; u < NPT; u++) b[u][(i + 1) & 1] = ld4(bp[u] + 4 * (N4 * kb + i + 1));
             }
 #pragma unroll
             for (int u = 0; u < NPT; u++) D[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[i].x, b[u][i & 1].x, D[u], 0, 0, 0);
@@ -162,42 +151,33 @@ __device__ __forceinline__ void tail_group(const TailView& v, float4 (&A)[8], bo
     for (int u = 0; u < NPT; u++) {
         const int pu = (tb + u) * 16 + n;
         if (tb + u >= t1 || pu >= v.P || ch >= v.Co) continue;
-        const int f = tdiv(pu, v.mHW), q = pu - f * v.HW;
+        const int f = magic_div(pu, v.mHW), q = pu - f * v.HW;
         float4 r = make_float4(D[u][0] + bias.x, D[u][1] + bias.y, D[u][2] + bias.z, D[u][3] + bias.w);
         if (v.res_mode != RES_NONE && ch < v.res_C) {
             float4 sk;
             if (v.rl) {
                 if (v.res_mode == RES_DIRECT) {
-                    sk = tld4(v.rl + (long)pu * v.rPS + ch);
+                    sk = ld4(v.rl + (long)pu * v.rPS + ch);
                 } else {  // 2x2 max-pool of a (2 Ho x 2 Wo) source
-                    const int oy = tdiv(q, v.mW), ox = q - oy * v.Wo;
+                    const int oy = magic_div(q, v.mW), ox = q - oy * v.Wo;
                     const float* s0 = v.rl + (long)((f * 2 * v.Ho + 2 * oy) * v.rW + 2 * ox) * v.rPS + ch;
-                    sk = tmax4(tld4(s0), tld4(s0 + v.rPS), tld4(s0 + (long)v.rW * v.rPS), tld4(s0 + (long)(v.rW + 1) * v.rPS));
+                    sk = max4(ld4(s0), ld4(s0 + v.rPS), ld4(s0 + (long)v.rW * v.rPS), ld4(s0 + (long)(v.rW + 1) * v.rPS));
                 }
             } else if (v.res_mode == RES_DIRECT) {
-                sk = tld4(v.rg + f * v.rfs + (long)q * v.res_C + ch);
+                sk = ld4(v.rg + f * v.rfs + (long)q * v.res_C + ch);
             } else {
-                const int oy = tdiv(q, v.mW), ox = q - oy * v.Wo;
+                const int oy = magic_div(q, v.mW), ox = q - oy * v.Wo;
                 const float* s0 = v.rg + f * v.rfs + ((long)(2 * oy) * v.rW + 2 * ox) * v.res_C + ch;
-                sk = tmax4(tld4(s0), tld4(s0 + v.res_C), tld4(s0 + (long)v.rW * v.res_C), tld4(s0 + (long)(v.rW + 1) * v.res_C));
+                sk = max4(ld4(s0), ld4(s0 + v.res_C), ld4(s0 + (long)v.rW * v.res_C), ld4(s0 + (long)(v.rW + 1) * v.res_C));
             }
-            r.x += sk.x; r.y += sk.y; r.z += sk.z; r.w += sk.w;
+            r = add4(r, sk);
         }
-        r.x = fminf(fmaxf(r.x, 0.f) + slope.x * fminf(r.x, 0.f), v.hi);
-        r.y = fminf(fmaxf(r.y, 0.f) + slope.y * fminf(r.y, 0.f), v.hi);
-        r.z = fminf(fmaxf(r.z, 0.f) + slope.z * fminf(r.z, 0.f), v.hi);
-        r.w = fminf(fmaxf(r.w, 0.f) + slope.w * fminf(r.w, 0.f), v.hi);
-        if (v.dl) tst4(v.dl + (long)pu * v.dPS + ch, r);
+        r = act4(r, slope, v.hi);
+        if (v.dl) st4(v.dl + (long)pu * v.dPS + ch, r);
         if (v.dg) {
             float* o = v.dg + f * v.dfs + (long)q * v.Co + ch;
-            if ((v.Co & 3) == 0) {
-                tst4(o, r);
-            } else {
-                o[0] = r.x;
-                if (ch + 1 < v.Co) o[1] = r.y;
-                if (ch + 2 < v.Co) o[2] = r.z;
-                if (ch + 3 < v.Co) o[3] = r.w;
-            }
+            if ((v.Co & 3) == 0) st4(o, r);
+            else store4_ragged(o, ch, v.Co, r);
         }
     }
 }
@@ -232,7 +212,7 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
     const int frame0 = blockIdx.x * G, nf = min(G, B - frame0);
     TailPre pf;
     if (PRE) tail_prefetch(prog[0], bs.weights, pf);
-    if (tid < 64) tst4(lds + zero_off + 4 * tid, make_float4(0.f, 0.f, 0.f, 0.f));   // the pixel out-of-frame depthwise taps read (<= 256 channels)
+    if (tid < 64) st4(lds + zero_off + 4 * tid, make_float4(0.f, 0.f, 0.f, 0.f));   // the pixel out-of-frame depthwise taps read (<= 256 channels)
     __syncthreads();
     for (int s = 0; s < nstages; s++) {
         const TailStage& st = prog[s];
@@ -244,13 +224,13 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
             if (PRE && more) tail_prefetch(prog[s + 1], bs.weights, pf);
             const int C4 = st.src_C >> 2, per = st.src_H * st.src_W * C4, PS = st.src_C + 4;
             const unsigned mper = st.mHW, mC4 = st.mW;
-            const float* src = tresolve(bs, st.src_g, frame0);
+            const float* src = res_resolve(bs, st.src_g, frame0);
             const long fs = st.src_g.fs;
             float* dst = lds + (long)st.dst_off * G;
             const int HW = st.src_H * st.src_W;
             for (int i = tid; i < nf * per; i += 512) {
-                const int f = tdiv(i, mper), e = i - f * per, px = tdiv(e, mC4), c4 = e - px * C4;
-                tst4(dst + (long)(f * HW + px) * PS + 4 * c4, tld4(src + f * fs + 4 * (long)e));
+                const int f = magic_div(i, mper), e = i - f * per, px = magic_div(e, mC4), c4 = e - px * C4;
+                st4(dst + (long)(f * HW + px) * PS + 4 * c4, ld4(src + f * fs + 4 * (long)e));
             }
             MI_TAIL_STAMP(1)
             MI_TAIL_STAMP(2)
@@ -276,14 +256,14 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
             const float* cw = bs.weights + st.w_c + 32 * nct + 4 * c4;    // [9][Kv] taps, [Kv] bias
             float4 w[9];
 #pragma unroll
-            for (int t = 0; t < 9; t++) w[t] = tld4(cw + t * Kv);
-            const float4 bdw = tld4(cw + 9 * Kv);
+            for (int t = 0; t < 9; t++) w[t] = ld4(cw + t * Kv);
+            const float4 bdw = ld4(cw + 9 * Kv);
             const int PSk = Kv + 4, S = st.S, sH = st.src_H, sW = st.src_W, sC = st.src_C;
             float* scr = lds + (long)st.scr_off * G + 4 * c4;
             const bool from_lds = st.src_off >= 0;
             const int sPS = sC + 4;
             const float* sl = lds + (long)(from_lds ? st.src_off : 0) * G + 4 * c4;
-            const float* sg = from_lds ? nullptr : tresolve(bs, st.src_g, frame0) + 4 * c4;
+            const float* sg = from_lds ? nullptr : res_resolve(bs, st.src_g, frame0) + 4 * c4;
             const long sfs = st.src_g.fs;
             const float* zl = lds + zero_off + 4 * c4;
             float* pool = st.pool_off >= 0 ? lds + (long)st.pool_off * G + 4 * c4 : nullptr;   // 2x2 max-pool of the source = taps (0..1, 0..1): the skip, for the epilogue
@@ -292,7 +272,7 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
             // pair costs 12 / 15 reads instead of 18, and the reads of a pair are in flight together
             const int Wp = (Wo + 1) >> 1, per = Ho * Wp, nitems = nf * per;
             for (int it = prow; it < nitems; it += PP) {
-                const int f = tdiv(it, st.mHWp), r = it - f * per, oy = tdiv(r, st.mWp), ox = 2 * (r - oy * Wp);
+                const int f = magic_div(it, st.mHWp), r = it - f * per, oy = magic_div(r, st.mWp), ox = 2 * (r - oy * Wp);
                 const int iy0 = oy * S - st.pt, ix0 = ox * S - st.pl;
                 const int b0 = (f * sH + iy0) * sW + ix0;   // source pixel of tap (0, 0) of the first pixel, counted over the workgroup's frames (may lie outside: unused then)
                 const int p0 = f * HW + oy * Wo + ox;
@@ -310,9 +290,9 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
                         if (kx == 4 && S == 1) continue;   // (uniform)
                         const bool ok = rok[ky] && cok[kx];
                         if (from_lds) {
-                            d[ky][kx] = tld4(ok ? sl + (long)(b0 + ky * sW + kx) * sPS : zl);
+                            d[ky][kx] = ld4(ok ? sl + (long)(b0 + ky * sW + kx) * sPS : zl);
                         } else {
-                            const float4 x = tld4(sg + f * sfs + (long)(ok ? (iy0 + ky) * sW + ix0 + kx : 0) * sC);
+                            const float4 x = ld4(sg + f * sfs + (long)(ok ? (iy0 + ky) * sW + ix0 + kx : 0) * sC);
                             d[ky][kx] = ok ? x : make_float4(0.f, 0.f, 0.f, 0.f);
                         }
                     }
@@ -322,7 +302,7 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
 #pragma unroll
                     for (int kx = 0; kx < 3; kx++) {   // (the taps of a pixel in the order of the single-pixel form: ky, kx ascending)
                         const float4 wt = w[ky * 3 + kx], x0 = d[ky][kx];
-                        acc0.x = fmaf(x0.x, wt.x, acc0.x); acc0.y = fmaf(x0.y, wt.y, acc0.y); acc0.z = fmaf(x0.z, wt.z, acc0.z); acc0.w = fmaf(x0.w, wt.w, acc0.w);
+                        fma4(x0, wt, acc0);
                     }
                 if (S == 1) {
 #pragma unroll
@@ -330,7 +310,7 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) {
                             const float4 wt = w[ky * 3 + kx], x1 = d[ky][kx + 1];
-                            acc1.x = fmaf(x1.x, wt.x, acc1.x); acc1.y = fmaf(x1.y, wt.y, acc1.y); acc1.z = fmaf(x1.z, wt.z, acc1.z); acc1.w = fmaf(x1.w, wt.w, acc1.w);
+                            fma4(x1, wt, acc1);
                         }
                 } else {
 #pragma unroll
@@ -338,19 +318,19 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
 #pragma unroll
                         for (int kx = 0; kx < 3; kx++) {
                             const float4 wt = w[ky * 3 + kx], x1 = d[ky][kx + 2];
-                            acc1.x = fmaf(x1.x, wt.x, acc1.x); acc1.y = fmaf(x1.y, wt.y, acc1.y); acc1.z = fmaf(x1.z, wt.z, acc1.z); acc1.w = fmaf(x1.w, wt.w, acc1.w);
+                            fma4(x1, wt, acc1);
                         }
                 }
-                tst4(scr + (long)p0 * PSk, acc0);
-                if (two) tst4(scr + (long)(p0 + 1) * PSk, acc1);
+                st4(scr + (long)p0 * PSk, acc0);
+                if (two) st4(scr + (long)(p0 + 1) * PSk, acc1);
                 if (pool) {   // (stride 2, pads 0: the 2x2 windows are columns 0..1 and 2..3 of rows 0..1)
-                    tst4(pool + (long)p0 * PSk, tmax4(d[0][0], d[0][1], d[1][0], d[1][1]));
-                    if (two) tst4(pool + (long)(p0 + 1) * PSk, tmax4(d[0][2], d[0][3], d[1][2], d[1][3]));
+                    st4(pool + (long)p0 * PSk, max4(d[0][0], d[0][1], d[1][0], d[1][1]));
+                    if (two) st4(pool + (long)(p0 + 1) * PSk, max4(d[0][2], d[0][3], d[1][2], d[1][3]));
                 }
             }
             } else {   // (128 registers: one pixel per item)
             for (int p = prow; p < P; p += PP) {
-                const int f = tdiv(p, st.mHW), q = p - f * HW, oy = tdiv(q, st.mW), ox = q - oy * Wo;
+                const int f = magic_div(p, st.mHW), q = p - f * HW, oy = magic_div(q, st.mW), ox = q - oy * Wo;
                 const int iy0 = oy * S - st.pt, ix0 = ox * S - st.pl;
                 const int b0 = (f * sH + iy0) * sW + ix0;   // source pixel of tap (0, 0), counted over the workgroup's frames (may lie outside: unused then)
                 bool rok[3], cok[3];
@@ -363,22 +343,19 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
                     for (int kx = 0; kx < 3; kx++) {
                         const bool ok = rok[ky] && cok[kx];
                         if (from_lds) {
-                            d[ky * 3 + kx] = tld4(ok ? sl + (long)(b0 + ky * sW + kx) * sPS : zl);
+                            d[ky * 3 + kx] = ld4(ok ? sl + (long)(b0 + ky * sW + kx) * sPS : zl);
                         } else {
-                            const float4 x = tld4(sg + f * sfs + (long)(ok ? (iy0 + ky) * sW + ix0 + kx : 0) * sC);
+                            const float4 x = ld4(sg + f * sfs + (long)(ok ? (iy0 + ky) * sW + ix0 + kx : 0) * sC);
                             d[ky * 3 + kx] = ok ? x : make_float4(0.f, 0.f, 0.f, 0.f);
                         }
                     }
                 float4 acc = bdw;
 #pragma unroll
                 for (int t = 0; t < 9; t++) {
-                    acc.x = fmaf(d[t].x, w[t].x, acc.x);
-                    acc.y = fmaf(d[t].y, w[t].y, acc.y);
-                    acc.z = fmaf(d[t].z, w[t].z, acc.z);
-                    acc.w = fmaf(d[t].w, w[t].w, acc.w);
+                    fma4(d[t], w[t], acc);
                 }
-                tst4(scr + (long)p * PSk, acc);
-                if (pool) tst4(pool + (long)p * PSk, tmax4(d[0], d[1], d[3], d[4]));
+                st4(scr + (long)p * PSk, acc);
+                if (pool) st4(pool + (long)p * PSk, max4(d[0], d[1], d[3], d[4]));
             }
             }
             __syncthreads();
@@ -390,8 +367,8 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
         MI_TAIL_STAMP(1)
         if (!PRE) {   // (two workgroups per CU: the other one computes while these travel)
 #pragma unroll
-            for (int i = 0; i < 8; i++) A[i] = tld4(wa0 + 256 * i);
-            bias = tld4(wc0); slope = tld4(wc0 + 16 * nct);
+            for (int i = 0; i < 8; i++) A[i] = ld4(wa0 + 256 * i);
+            bias = ld4(wc0); slope = ld4(wc0 + 16 * nct);
         } else {
             // this stage's constants leave the prefetch registers (the second half of A is asked for now and arrives behind the first
             // half's MFMAs), the next stage's start their trip
@@ -399,16 +376,16 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
             for (int i = 0; i < kTailPreA; i++) A[i] = pf.A[i];
             if (n4b > kTailPreA) {
 #pragma unroll
-                for (int i = kTailPreA; i < 8; i++) A[i] = tld4(wa0 + 256 * i);
+                for (int i = kTailPreA; i < 8; i++) A[i] = ld4(wa0 + 256 * i);
             }
             bias = pf.bias; slope = pf.slope;
             if (more) tail_prefetch(prog[s + 1], bs.weights, pf);
         }
         v.dl = st.dst_off >= 0 ? lds + (long)st.dst_off * G : nullptr; v.dPS = st.Co + 4;
-        v.dg = st.dst_g.base >= 0 ? tresolve(bs, st.dst_g, frame0) : nullptr; v.dfs = st.dst_g.fs;
+        v.dg = st.dst_g.base >= 0 ? res_resolve(bs, st.dst_g, frame0) : nullptr; v.dfs = st.dst_g.fs;
         v.res_mode = st.res_mode; v.res_C = st.res_C; v.rPS = st.res_C + 4; v.rW = st.res_W;
         v.rl = (st.res_mode != RES_NONE && st.res_off >= 0) ? lds + (long)st.res_off * G : nullptr;
-        v.rg = (st.res_mode != RES_NONE && st.res_off < 0) ? tresolve(bs, st.res_g, frame0) : nullptr; v.rfs = st.res_g.fs;
+        v.rg = (st.res_mode != RES_NONE && st.res_off < 0) ? res_resolve(bs, st.res_g, frame0) : nullptr; v.rfs = st.res_g.fs;
         if (kind == TAIL_DW && st.pool_off >= 0) { v.res_mode = RES_DIRECT; v.rl = lds + (long)st.pool_off * G; v.rg = nullptr; }   // the pooled skip, one pixel per output pixel
         v.hi = st.act == ACT_RELU6 ? 6.f : INFINITY;
         v.wa = bs.weights + st.w_a; v.wc = bs.weights + st.w_c;
@@ -421,9 +398,9 @@ __global__ __launch_bounds__(512, PRE ? 2 : 4) void tail_kernel(const TailStage*
             for (int ct = ct0 + 8; ct < nct; ct += 8) {   // stages of more than 128 output channels: the further tiles fetch their constants themselves
                 const float* wa = v.wa + ((long)ct * n4 * 64 + lane) * 4;
 #pragma unroll
-                for (int i = 0; i < 8; i++) A[i] = tld4(wa + 256 * i);
-                bias = tld4(v.wc + 16 * ct + 4 * kq);
-                slope = tld4(v.wc + 16 * nct + 16 * ct + 4 * kq);
+                for (int i = 0; i < 8; i++) A[i] = ld4(wa + 256 * i);
+                bias = ld4(v.wc + 16 * ct + 4 * kq);
+                slope = ld4(v.wc + 16 * nct + 16 * ct + 4 * kq);
                 tail_tile(v, A, bias, slope, ct, t0, t1, n4b, nkb);
             }
         }
@@ -455,7 +432,7 @@ int launch_tail(const TailLaunch& a, void* stream) {
     if (!a.prog || a.nstages < 1 || a.B < 1 || a.G < 1 || a.frame_floats < 1) return (int)hipErrorInvalidValue;
     const long zero_off = (long)a.frame_floats * a.G;
     const long lds_bytes = (zero_off + 256) * 4;
-    if (lds_bytes > 160 * 1024) return (int)hipErrorInvalidValue;
+    if (lds_bytes > kLdsBytes) return (int)hipErrorInvalidValue;
     unsigned long long* stamps = nullptr;
 #ifdef MI_TAIL_STAMPS
     stamps = g_tail_stamps;
@@ -472,8 +449,7 @@ int launch_tail(const TailLaunch& a, void* stream) {
     bool pre = a.variant == 1 || (a.variant == 0 && lds_bytes > 80 * 1024);
     if (a.variant == 0 && rule == 0) pre = lds_bytes > 80 * 1024 || nwg <= (unsigned)device_cu_count();
     auto kern = pre ? tail_kernel<true> : tail_kernel<false>;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return (int)e;
-    return (int)launch_kernel(kern, dim3(nwg), dim3(512), (size_t)lds_bytes, (hipStream_t)stream, a.prog, a.nstages, a.G, a.B, (int)zero_off, a.bases, stamps);
+    return launch_full_lds(kern, dim3(nwg), dim3(512), (size_t)lds_bytes, (hipStream_t)stream, a.prog, a.nstages, a.G, a.B, (int)zero_off, a.bases, stamps);
 }
 
 }  // namespace mi

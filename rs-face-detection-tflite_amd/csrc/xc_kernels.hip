@@ -26,18 +26,11 @@
 
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "mfma32.hpp"
 
 namespace mi {
 
-typedef float xf32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
-
-__device__ __forceinline__ float4 xld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 xmax4(float4 a, float4 b, float4 c, float4 d) {
-    return make_float4(fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x)), fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y)),
-                       fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z)), fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w)));
-}
 
 struct XcGeom {
     int PSn, PSw;          // pixel strides (floats) of the narrow / wide LDS tensor
@@ -47,7 +40,7 @@ struct XcGeom {
     unsigned long long* stamps;  // diagnostic builds only (MI_XC_STAMPS): s_memtime stamps of workgroup 0, wave 0
 };
 #ifdef MI_XC_STAMPS
-#define XC_STAMP(k) if (g.stamps && blockIdx.x == 0 && threadIdx.x == 0) { __builtin_amdgcn_sched_barrier(0); g.stamps[(k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+#define XC_STAMP(k) if (g.stamps && blockIdx.x == 0 && threadIdx.x == 0) MI_STAMP_AT(g.stamps[(k)])
 #else
 #define XC_STAMP(k)
 #endif
@@ -72,7 +65,7 @@ __device__ __forceinline__ void xc_unit(const XcStage& st, const XcArgs& a, int 
     const bool valid = q < npix;
     const int qq = valid ? q : 0, oy = qq / W, ox = qq - oy * W;
     const float* t0 = src + (oy * row + ox) * PSs + h * Ch;   // tap (0, 0) of this pixel (bordered tensor: pixel (y, x) sits at (y + 1, x + 1)), this lane's k-half
-    xf32x16 D[MTG];
+    f32x16 D[MTG];
 #pragma unroll
     for (int m = 0; m < MTG; m++)
 #pragma unroll
@@ -84,7 +77,7 @@ __device__ __forceinline__ void xc_unit(const XcStage& st, const XcArgs& a, int 
     for (int m = 0; m < MTG; m++) {
         wa[m] = st.w_pw + ((long)min(mt0 + m, MT - 1) * nch * 64 + lane) * 4;
 #pragma unroll
-        for (int r = 0; r < kXcRing; r++) ring[r][m] = xld4(wa[m] + (long)min((KSPLIT ? share * (nch / nsh) : 0) + r, nch - 1) * 256);
+        for (int r = 0; r < kXcRing; r++) ring[r][m] = ld4(wa[m] + (long)min((KSPLIT ? share * (nch / nsh) : 0) + r, nch - 1) * 256);
     }
     const int jb = KSPLIT ? share * (nch / nsh) : 0, je = KSPLIT ? jb + nch / nsh : nch;
     // one k-chunk: depthwise 3x3 (+ bias) of 4 channels of this lane's k-half (or the pixel itself: pointwise stage), then the MFMAs
@@ -92,28 +85,21 @@ __device__ __forceinline__ void xc_unit(const XcStage& st, const XcArgs& a, int 
         const int c0 = 4 * j;
         float4 bf;
         if (st.has_dw) {   // wave-uniform
-            bf = xld4(bdw + h * Ch + c0);
+            // the loop stays here (fma4 only): as dw3x3_quad the kernel spills 22 VGPRs instead of 20 and has 870 s_waitcnt instead of 861
+            bf = ld4(bdw + h * Ch + c0);
 #pragma unroll
             for (int ky = 0; ky < 3; ky++)
 #pragma unroll
                 for (int kx = 0; kx < 3; kx++) {
-                    const float4 w = xld4(wdw + (ky * 3 + kx) * Cp + h * Ch + c0);
-                    const float4 d = xld4(t0 + (ky * row + kx) * PSs + c0);
-                    bf.x = fmaf(d.x, w.x, bf.x);
-                    bf.y = fmaf(d.y, w.y, bf.y);
-                    bf.z = fmaf(d.z, w.z, bf.z);
-                    bf.w = fmaf(d.w, w.w, bf.w);
+                    const float4 w = ld4(wdw + (ky * 3 + kx) * Cp + h * Ch + c0);
+                    const float4 d = ld4(t0 + (ky * row + kx) * PSs + c0);
+                    fma4(d, w, bf);
                 }
         } else {
-            bf = xld4(t0 + (row + 1) * PSs + c0);   // pointwise stage: the pixel itself
+            bf = ld4(t0 + (row + 1) * PSs + c0);   // pointwise stage: the pixel itself
         }
 #pragma unroll
-        for (int m = 0; m < MTG; m++) {
-            D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].x, bf.x, D[m], 0, 0, 0);
-            D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].y, bf.y, D[m], 0, 0, 0);
-            D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].z, bf.z, D[m], 0, 0, 0);
-            D[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m].w, bf.w, D[m], 0, 0, 0);
-        }
+        for (int m = 0; m < MTG; m++) mfma32_quad(av[m], bf, D[m]);
     };
     // whole ring rounds: no control flow around the loads (a branch per chunk makes every wait a full one — each chunk then paid an L2
     // round trip for the fragments asked for a moment before: 3.9 k cycles per chunk); slot r is consumed, then refilled kXcRing chunks ahead
@@ -126,7 +112,7 @@ __device__ __forceinline__ void xc_unit(const XcStage& st, const XcArgs& a, int 
 #pragma unroll
             for (int m = 0; m < MTG; m++) {
                 av[m] = ring[r][m];
-                ring[r][m] = xld4(wa[m] + (long)min(j0 + r + kXcRing, nch - 1) * 256);
+                ring[r][m] = ld4(wa[m] + (long)min(j0 + r + kXcRing, nch - 1) * 256);
             }
             chunk(j0 + r, av);
         }
@@ -134,7 +120,7 @@ __device__ __forceinline__ void xc_unit(const XcStage& st, const XcArgs& a, int 
     for (int j = jb + nfull * kXcRing; j < je; j++) {   // the rest (k-chunk counts that are no multiple of the ring): plain loads
         float4 av[MTG];
 #pragma unroll
-        for (int m = 0; m < MTG; m++) av[m] = xld4(wa[m] + (long)j * 256);
+        for (int m = 0; m < MTG; m++) av[m] = ld4(wa[m] + (long)j * 256);
         chunk(j, av);
     }
     if constexpr (KSPLIT) {
@@ -173,22 +159,17 @@ __device__ __forceinline__ void xc_unit(const XcStage& st, const XcArgs& a, int 
         for (int gq = 0; gq < 4; gq++) {
             const int ch = (mt0 + m) * 32 + 8 * gq + 4 * h;
             if (ch >= st.Co) continue;
-            const float4 bb = xld4(biasL + ch);
-            float4 v = make_float4(D[m][4 * gq] + bb.x, D[m][4 * gq + 1] + bb.y, D[m][4 * gq + 2] + bb.z, D[m][4 * gq + 3] + bb.w);
+            const float4 bb = ld4(biasL + ch);
             float4 sk = make_float4(0.f, 0.f, 0.f, 0.f);
             if (st.skip == 2 && ch < st.res_C) {   // 2x2 max-pool of the previous resolution's tensor (the run's first stage only: read here, once)
                 const float* r = st.res + (long)frame * st.res_fs + ((long)(2 * oy) * st.res_W + 2 * ox) * st.res_C + ch;
-                sk = xmax4(xld4(r), xld4(r + st.res_C), xld4(r + (long)st.res_W * st.res_C), xld4(r + (long)(st.res_W + 1) * st.res_C));
+                sk = max4(ld4(r), ld4(r + st.res_C), ld4(r + (long)st.res_W * st.res_C), ld4(r + (long)(st.res_W + 1) * st.res_C));
             }
-            if (st.skip == 1 && ch < st.C) sk = xld4(own + ch);   // channels >= C: the zero channel-pad of the skip
-            if (st.skip == 3) sk = xld4(dl + ch);                 // the wide tensor of the pair before: this pixel's old content, replaced in place
-            v.x += sk.x; v.y += sk.y; v.z += sk.z; v.w += sk.w;
-            v.x = fminf(fmaxf(v.x, 0.f) + lo_slope * fminf(v.x, 0.f), hi);
-            v.y = fminf(fmaxf(v.y, 0.f) + lo_slope * fminf(v.y, 0.f), hi);
-            v.z = fminf(fmaxf(v.z, 0.f) + lo_slope * fminf(v.z, 0.f), hi);
-            v.w = fminf(fmaxf(v.w, 0.f) + lo_slope * fminf(v.w, 0.f), hi);
-            if (dl) *reinterpret_cast<float4*>(dl + ch) = v;
-            if (dg) *reinterpret_cast<float4*>(dg + ch) = v;
+            if (st.skip == 1 && ch < st.C) sk = ld4(own + ch);   // channels >= C: the zero channel-pad of the skip
+            if (st.skip == 3) sk = ld4(dl + ch);                 // the wide tensor of the pair before: this pixel's old content, replaced in place
+            const float4 v = bias_skip_act4(quad4(D[m], gq), bb, sk, make_float4(lo_slope, lo_slope, lo_slope, lo_slope), hi);
+            if (dl) st4(dl + ch, v);
+            if (dg) st4(dg + ch, v);
         }
     }
     (void)Cop;
@@ -213,7 +194,7 @@ __global__ __launch_bounds__(512) void xc_kernel(XcArgs a, XcGeom g) {
         const float* in = a.in + (long)frame * a.in_fs;
         for (int i = tid; i < npix * C4; i += 512) {
             const int px = i / C4, c4 = i - px * C4, y = px / W, x = px - y * W;
-            *reinterpret_cast<float4*>(nar + ((y + 1) * row + x + 1) * g.PSn + 4 * c4) = xld4(in + 4 * (long)i);
+            *reinterpret_cast<float4*>(nar + ((y + 1) * row + x + 1) * g.PSn + 4 * c4) = ld4(in + 4 * (long)i);
         }
     }
     XC_STAMP(1)
@@ -230,7 +211,7 @@ __global__ __launch_bounds__(512) void xc_kernel(XcArgs a, XcGeom g) {
         // ---- this stage's small constants (depthwise taps [9][Cp], depthwise bias [Cp], pointwise bias [Cop]: one packed blob, copied as it is)
         {
             const int n4 = (10 * Cp + Cop) >> 2;
-            for (int i = tid; i < n4; i += 512) reinterpret_cast<float4*>(cst)[i] = xld4(st.cblob + 4 * (long)i);
+            for (int i = tid; i < n4; i += 512) reinterpret_cast<float4*>(cst)[i] = ld4(st.cblob + 4 * (long)i);
         }
         XC_STAMP(2 + 4 * s)
         __syncthreads();
@@ -286,7 +267,6 @@ bool make_xc_geom(const XcArgs& a, XcGeom* out) {
         if (side && side != st.C) return false;
         side = st.C;
         cmax = std::max(cmax, 10 * ((st.C + 7) & ~7) + MT * 32);
-        auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
         if (!aligned16(st.w_pw) || !st.cblob || !aligned16(st.cblob) || (st.skip == 2 && (!aligned16(st.res) || (st.res_fs & 3)))) return false;
     }
     if (a.st[a.nstages - 1].Co != Cn) return false;   // the run ends on the narrow side
@@ -299,8 +279,7 @@ bool make_xc_geom(const XcArgs& a, XcGeom* out) {
     g.off_c = off; off += (cmax + 3) & ~3;
     g.cst_floats = cmax;
     g.lds_bytes = off * 4;
-    if (g.lds_bytes > 160 * 1024 - 256) return false;
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (g.lds_bytes > kLdsBudget) return false;
     if (!aligned16(a.in) || !aligned16(a.out) || (a.in_fs & 3) || (a.out_fs & 3)) return false;
     *out = g;
     return true;
@@ -318,10 +297,10 @@ bool xc_kernel_supports(const XcArgs& a) {
 int launch_xc(const XcArgs& a, void* stream) {
     XcGeom g;
     if (!make_xc_geom(a, &g)) return (int)hipErrorInvalidValue;
-    if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(xc_kernel)); e != hipSuccess) return (int)e;
     g.stamps = nullptr;
 #ifdef MI_XC_STAMPS
     if (getenv("MI_XC_STAMPS")) {   // stamps build: run the launch eagerly and print where workgroup 0's first wave spent it
+        if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(xc_kernel)); e != hipSuccess) return (int)e;
         static unsigned long long* d = nullptr;
         if (!d) (void)hipMalloc(&d, 64 * 8);
         g.stamps = d;
@@ -335,7 +314,7 @@ int launch_xc(const XcArgs& a, void* stream) {
         return 0;
     }
 #endif
-    return (int)launch_kernel(xc_kernel, dim3((unsigned)a.B), dim3(512), (size_t)g.lds_bytes, (hipStream_t)stream, a, g);
+    return launch_full_lds(xc_kernel, dim3((unsigned)a.B), dim3(512), (size_t)g.lds_bytes, (hipStream_t)stream, a, g);
 }
 
 }  // namespace mi
