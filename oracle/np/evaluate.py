@@ -85,10 +85,15 @@ def densify(t: tfl3.Tensor) -> np.ndarray:
     return dense
 
 
-def run(g: tfl3.Graph, x: np.ndarray, keep_all=False, num_threads=None):
-    """x: float32 [B,H,W,C] NHWC. Returns list of output arrays (graph output order) or dict of all tensors."""
+def run(g: tfl3.Graph, x: np.ndarray, keep_all=False, num_threads=None, dtype=np.float32):
+    """x: [B,H,W,C] NHWC. Returns list of output arrays (graph output order) or dict of all tensors.
+    dtype: np.float32 (the cross-check of the C oracle) or np.float64 (the yardstick of tests/test_slices_cpu.py: activations and
+    the constants after dequantisation are float64; the constants themselves stay the f32 / f16 values of the file)."""
     if num_threads:
         torch.set_num_threads(num_threads)
+    dtype = np.dtype(dtype)
+    assert dtype in (np.dtype(np.float32), np.dtype(np.float64))
+    tdt = torch.float32 if dtype == np.float32 else torch.float64
     vals = {}
 
     def const(i):
@@ -103,13 +108,13 @@ def run(g: tfl3.Graph, x: np.ndarray, keep_all=False, num_threads=None):
         if t.data is None:
             raise KeyError("tensor %d has no value" % i)
         a = const(i)
-        if a.dtype == np.float16:
-            a = a.astype(np.float32)
+        if a.dtype in (np.float16, np.float32):
+            a = a.astype(dtype)
         v = torch.from_numpy(np.ascontiguousarray(a))
         vals[i] = v
         return v
 
-    vals[g.inputs[0]] = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    vals[g.inputs[0]] = torch.from_numpy(np.ascontiguousarray(x, dtype=dtype))
     B = x.shape[0]
     with torch.no_grad():
         for op in g.ops:
@@ -117,13 +122,13 @@ def run(g: tfl3.Graph, x: np.ndarray, keep_all=False, num_threads=None):
             o = op.outputs[0]
             if c == tfl3.DEQUANTIZE:
                 src = vals[op.inputs[0]].numpy() if op.inputs[0] in vals else const(op.inputs[0])
-                vals[o] = torch.from_numpy(np.ascontiguousarray(src).astype(np.float32))
+                vals[o] = torch.from_numpy(np.ascontiguousarray(src).astype(dtype))
             elif c == tfl3.DENSIFY:
-                vals[o] = torch.from_numpy(densify(g.tensors[op.inputs[0]]))
+                vals[o] = torch.from_numpy(densify(g.tensors[op.inputs[0]]).astype(dtype))
             elif c in (tfl3.CONV_2D, tfl3.DEPTHWISE_CONV_2D):
                 a = get(op.inputs[0]).permute(0, 3, 1, 2)
-                w = get(op.inputs[1]).to(torch.float32)
-                bias = get(op.inputs[2]).to(torch.float32) if len(op.inputs) > 2 and op.inputs[2] >= 0 else None
+                w = get(op.inputs[1]).to(tdt)
+                bias = get(op.inputs[2]).to(tdt) if len(op.inputs) > 2 and op.inputs[2] >= 0 else None
                 sh, sw = op.opts["stride_h"], op.opts["stride_w"]
                 if c == tfl3.CONV_2D:
                     kh, kw = w.shape[1], w.shape[2]

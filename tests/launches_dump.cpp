@@ -4,6 +4,7 @@
 //   shipped: the option rows {defaults, strip=0, pair_fuse=0, stem_fuse=0, mchain=0, small_chain=0, stem_mfma=0, fork=0, heads=4, lanes=2,
 //            fuse=2} at F in {1, 4, 5, 16, 17, 31, 32}; band=2 at F in {1, 4}; the u8 input form (where the graph has one) at F in {1, 32}
 //   synth:   defaults and fuse=2 at F in {1, 32}
+//   tensors: defaults at F in {1, 3, 32, 33}, in a form of its own (below): per launch `k "label" in=[tensors] out=[tensors]`
 // Per configuration a header line `== model row F=n`, then one line per launch: launcher tag, label, the plan nodes it stands for (first-last
 // and how many), stream slot, wait node, record flag, and a 64-bit FNV-1a hash of the argument struct taken field by field (pointers as the
 // numbers they are).  The device addresses are fake, 256-byte aligned and 2^40 bytes apart (graph outputs 2^36); nothing dereferences them:
@@ -11,6 +12,7 @@
 //   small-batch scratch 0x050000000000  stage programs 0x060000000000  tail programs 0x070000000000
 //   band program 0x080000000000, constants 0x090000000000, workspace 0x0a0000000000, sync 0x0b0000000000, fail 0x0c0000000000
 //   u8 frames 0x0d0000000000, u8 table 0x0e0000000000
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -150,7 +152,34 @@ void print_lowered(const Plan& plan, const Lowered& low) {
     std::printf("nodes=%zu views=%zu\n", plan.nodes.size(), views);
 }
 
-void run_config(const char* model, const std::vector<unsigned char>& blob, const Row& row, int F) {
+// `tensors` mode: per launch its label and the graph tensors it reads from / writes to memory (what a slice of the graph that holds exactly this
+// launch is cut at, tests/tfl_slice.py); the views (nodes without a launch) behind them, by their output tensor
+void print_tensors(const Plan& plan, const Lowered& low) {
+    auto list = [](const std::vector<int>& v) {
+        std::string s;
+        for (int t : v) s += (s.empty() ? "" : ",") + std::to_string(t);
+        return s;
+    };
+    for (size_t k = 0; k < low.launches.size(); k++) {
+        std::vector<int> in, out;
+        for (size_t i = 0; i < plan.nodes.size(); i++) {
+            if (low.launch_of_node[i] != static_cast<int>(k)) continue;
+            const Node& n = plan.nodes[i];
+            for (int t : n.in) in.push_back(t);
+            out.push_back(n.out);
+            for (int t : n.extra_out) out.push_back(t);
+            for (const Node& h : n.head_nodes) out.push_back(h.out);
+        }
+        std::vector<int> ext;
+        for (int t : in)
+            if (std::find(out.begin(), out.end(), t) == out.end() && std::find(ext.begin(), ext.end(), t) == ext.end()) ext.push_back(t);
+        std::printf("%zu \"%s\" in=[%s] out=[%s]\n", k, low.launches[k].label.c_str(), list(ext).c_str(), list(out).c_str());
+    }
+    for (size_t i = 0; i < plan.nodes.size(); i++)
+        if (low.launch_of_node[i] < 0) std::printf("view in=[%s] out=[%d]\n", list(plan.nodes[i].in).c_str(), plan.nodes[i].out);
+}
+
+void run_config(const char* model, const std::vector<unsigned char>& blob, const Row& row, int F, bool tensors = false) {
     std::printf("== %s %s F=%d\n", model, row.name, F);
     try {
         const Plan plan = build_plan(parse_tflite(blob.data(), blob.size()), row.fuse, 4, 156 * 1024, true);
@@ -185,7 +214,9 @@ void run_config(const char* model, const std::vector<unsigned char>& blob, const
         if (fmax && c.small_chain > 0) { c.small = fake<float>(0x050000000000ull); c.small_floats = 2 * static_cast<size_t>(c.small_chain) * fmax; }
         c.band = row.band && bp.ready && c.lanes == 1 && F <= bp.max_frames;
         if (row.band) std::printf("band=%d\n", c.band ? 1 : 0);
-        print_lowered(plan, lower_chunk(plan, consts, bp, sched, c, true));
+        const Lowered low = lower_chunk(plan, consts, bp, sched, c, true);
+        if (tensors) print_tensors(plan, low);
+        else print_lowered(plan, low);
     } catch (const std::exception& e) {
         std::printf("threw: %s\n", e.what());
     }
@@ -194,8 +225,8 @@ void run_config(const char* model, const std::vector<unsigned char>& blob, const
 
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
-    const bool shipped = !std::strcmp(argv[1], "shipped");
-    if (!shipped && std::strcmp(argv[1], "synth")) return 2;
+    const bool shipped = !std::strcmp(argv[1], "shipped"), tensors = !std::strcmp(argv[1], "tensors");
+    if (!shipped && !tensors && std::strcmp(argv[1], "synth")) return 2;
     Row defaults{"defaults"}, fuse2{"fuse=2"}, heads4{"heads=4"}, band2{"band=2"}, u8{"u8"};
     fuse2.fuse = 2; heads4.heads = 4; band2.band = 2; u8.u8 = true;
     const std::vector<Row> rows = {defaults,
@@ -213,7 +244,9 @@ int main(int argc, char** argv) {
         std::ifstream f(argv[i], std::ios::binary);
         const std::vector<unsigned char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
         const char* base = std::strrchr(argv[i], '/') ? std::strrchr(argv[i], '/') + 1 : argv[i];
-        if (shipped) {
+        if (tensors) {
+            for (int F : {1, 3, 32, 33}) run_config(base, b, defaults, F, true);
+        } else if (shipped) {
             for (const Row& r : rows)
                 for (int F : {1, 4, 5, 16, 17, 31, 32}) run_config(base, b, r, F);
             for (int F : {1, 4}) run_config(base, b, band2, F);
