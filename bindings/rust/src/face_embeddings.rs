@@ -2,7 +2,7 @@
 //! tells users to download one), none is shipped here, and the reference's own model has never been run on this engine.  Any graph of
 //! the operators the engine lowers that maps `[1,112,112,3]` to one output of `D` values per frame loads.
 use crate::pipeline::FacesResults;
-use crate::types::{BBox, Detection, Image};
+use crate::types::{BBox, Detection, Image, Rect};
 use crate::{check, ffi};
 use anyhow::Error;
 use std::ffi::CString;
@@ -144,6 +144,90 @@ impl FaceEmbeddings {
         })?;
         Ok(out)
     }
+
+    /// NOT the reference's chip (that is `infer`, which crops the box): the least-squares similarity fit of `points` — pixel coordinates in
+    /// the order of `face_align_template(source)`, five of them, four for `AlignSource::Detection` — the warp of the WHOLE image by it to
+    /// 112 x 112, the network, `l2_norm` (`mi_fe_infer_image_aligned`).  Returns the embedding and the fitted ROI; points without a fit
+    /// (a coordinate that is not finite, all points equal) are an `Err`.
+    pub fn infer_aligned<'a, I>(&self, image: I, points: &[[f32; 2]], source: AlignSource) -> Result<(Vec<f32>, Rect), Error>
+    where
+        I: TryInto<Image<'a>>,
+        I::Error: Into<Error>,
+    {
+        let image: Image<'a> = image.try_into().map_err(Into::into)?;
+        let mut out = vec![0f32; self.features];
+        let mut roi = Rect::new(0.5, 0.5, 1.0, 1.0, 0.0, true).to_mi();
+        check(unsafe {
+            ffi::mi_fe_infer_image_aligned(self.handle, image.data.as_ptr(), image.width, image.height, image.stride, points.as_ptr() as *const f32,
+                                           points.len() as i32, source.to_mi(), out.as_mut_ptr(), out.len() as i32, &mut roi)
+        })?;
+        Ok((out, Rect::from_mi(&roi)))
+    }
+
+    /// `infer_aligned` for every item of what `Pipeline::run_faces` returned for these frames (`mi_fe_infer_aligned_items`): the points of
+    /// an item come from its mesh (`AlignSource::Mesh`: landmarks and `present`), from its detection's key points (`AlignSource::Detection`)
+    /// or from the caller (`AlignSource::Points`: `points` holds `[max_items][5]` pixel points).  `rois` holds the fitted ROI of every item.
+    pub fn infer_items_aligned(&self, frames: &[u8], batch: usize, width: i32, height: i32, stride: i32, faces: &FacesResults,
+                               source: AlignSource, points: Option<&[[f32; 2]]>, want_raw: bool, want_chips: bool)
+                               -> Result<(ItemEmbeddings, Vec<Rect>), Error> {
+        let m = faces.item_frame.len();
+        let max_faces = faces.faces.iter().map(|f| f.len()).max().unwrap_or(0).max(1);
+        if batch == 0 || m == 0 || m > 32767 || faces.item_face.len() != m || faces.faces.len() != batch || max_faces > 16 {
+            return Err(Error::msg("the result of run_faces on these frames is expected (max_faces 1..16, max_items 1..32767)"));
+        }
+        if width <= 0 || height <= 0 || stride <= 0 || (stride as i64) < 3 * width as i64 {
+            return Err(Error::msg("frames must hold batch frames of height rows of stride bytes"));
+        }
+        let (w, h, s) = (width as usize, height as usize, stride as usize);
+        let need = s.checked_mul(h).and_then(|f| f.checked_mul(batch - 1)).and_then(|x| x.checked_add(s * (h - 1))).and_then(|x| x.checked_add(3 * w));
+        if need.map_or(true, |x| frames.len() < x) {
+            return Err(Error::msg("frames must hold batch frames of height rows of stride bytes"));
+        }
+        // the operand the source reads, as the C entry wants it, and its gate
+        let mut dets: Vec<ffi::mi_detection> = Vec::new();
+        let present: Vec<i32> = faces.present.iter().map(|&p| p as i32).collect();
+        let (src, gate): (*const std::ffi::c_void, *const i32) = match source {
+            AlignSource::Mesh => {
+                if faces.landmarks.len() != m * 468 * 3 || present.len() != m {
+                    return Err(Error::msg("landmarks must be [max_items][468][3] and present [max_items]"));
+                }
+                (faces.landmarks.as_ptr() as *const std::ffi::c_void, present.as_ptr())
+            }
+            AlignSource::Detection => {
+                dets = vec![ffi::mi_detection { data: [0.0; 16], score: 0.0 }; batch * max_faces];
+                for (b, frame) in faces.faces.iter().enumerate() {
+                    for (k, det) in frame.iter().enumerate() {
+                        dets[b * max_faces + k] = det.to_mi();
+                    }
+                }
+                (dets.as_ptr() as *const std::ffi::c_void, std::ptr::null())
+            }
+            AlignSource::Points => match points {
+                Some(p) if p.len() == m * 5 => (p.as_ptr() as *const std::ffi::c_void, std::ptr::null()),
+                _ => return Err(Error::msg("AlignSource::Points needs [max_items][5] pixel points")),
+            },
+        };
+        let d = self.features;
+        let chip = 3 * (IMG_SIZE as usize) * (IMG_SIZE as usize);
+        let mut out = ItemEmbeddings {
+            features: d,
+            embeddings: vec![0f32; m * d],
+            valid: vec![0i32; m],
+            raw: vec![0f32; if want_raw { m * d } else { 0 }],
+            chips: vec![0f32; if want_chips { m * chip } else { 0 }],
+        };
+        let mut rois = vec![Rect::new(0.5, 0.5, 1.0, 1.0, 0.0, true).to_mi(); m];
+        check(unsafe {
+            ffi::mi_fe_infer_aligned_items(self.handle, frames.as_ptr(), batch as i32, width, height, stride, source.to_mi(), src, gate,
+                                           max_faces as i32, faces.item_frame.as_ptr(), faces.item_face.as_ptr(), m as i32,
+                                           out.embeddings.as_mut_ptr(), out.valid.as_mut_ptr(),
+                                           if want_raw { out.raw.as_mut_ptr() } else { std::ptr::null_mut() },
+                                           if want_chips { out.chips.as_mut_ptr() } else { std::ptr::null_mut() }, rois.as_mut_ptr(),
+                                           ffi::MI_MEM_HOST, std::ptr::null_mut())
+        })?;
+        drop(dets);
+        Ok((out, rois.iter().map(Rect::from_mi).collect()))
+    }
 }
 
 impl Drop for FaceEmbeddings {
@@ -160,6 +244,61 @@ pub fn face_chip_rect(detection: &Detection, image_size: (i32, i32)) -> Result<(
     let mut valid: i32 = 0;
     check(unsafe { ffi::mi_face_chip_rect(&det, image_size.0, image_size.1, rect.as_mut_ptr(), &mut valid) })?;
     Ok(((rect[0], rect[1], rect[2], rect[3]), valid != 0))
+}
+
+/// Where the points of an aligned chip come from (`MI_ALIGN_*`).  Aligned chips are NOT the reference's behaviour: it crops the box.
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub enum AlignSource {
+    /// five pixel points: image-left eye, image-right eye, nose tip, image-left and image-right mouth corner
+    Points,
+    /// the 468 mesh landmarks: eyes = midpoints of 33 / 133 and 362 / 263, nose tip = 1, mouth corners = 61 and 291
+    Mesh,
+    /// the detection's key points 0..3 (eyes, nose tip, mouth centre) against the four-point template
+    Detection,
+}
+
+impl AlignSource {
+    pub(crate) fn to_mi(self) -> i32 {
+        match self {
+            AlignSource::Points => ffi::MI_ALIGN_POINTS,
+            AlignSource::Mesh => ffi::MI_ALIGN_MESH,
+            AlignSource::Detection => ffi::MI_ALIGN_DETECTION,
+        }
+    }
+}
+
+/// The destination points of the aligned chip in chip pixels (`mi_face_align_template`, host only): five, or four for `Detection`.
+pub fn face_align_template(source: AlignSource) -> Result<Vec<[f64; 2]>, Error> {
+    let mut xy = [[0f64; 2]; 5];
+    let mut n: i32 = 0;
+    check(unsafe { ffi::mi_face_align_template(source.to_mi(), xy.as_mut_ptr() as *mut f64, &mut n) })?;
+    Ok(xy[..n.clamp(0, 5) as usize].to_vec())
+}
+
+/// The pixel points of one face by the gather rule (`mi_face_align_points`, host only): `src` is `[468][3]` normalised landmarks for
+/// `Mesh`, a detection's 17 floats for `Detection`, `[5][2]` points for `Points`.
+pub fn face_align_points(source: AlignSource, src: &[f32], image_size: (i32, i32)) -> Result<Vec<[f32; 2]>, Error> {
+    let need = match source {
+        AlignSource::Points => 10,
+        AlignSource::Mesh => 468 * 3,
+        AlignSource::Detection => 17,
+    };
+    if src.len() != need {
+        return Err(Error::msg("the source's operand has another length"));
+    }
+    let mut pts = [[0f32; 2]; 5];
+    let mut n: i32 = 0;
+    check(unsafe { ffi::mi_face_align_points(source.to_mi(), src.as_ptr(), image_size.0, image_size.1, pts.as_mut_ptr() as *mut f32, &mut n) })?;
+    Ok(pts[..n.clamp(0, 5) as usize].to_vec())
+}
+
+/// The least-squares similarity fit of pixel `points` to the template of `source` as the rotated square ROI whose warp to 112 x 112 is the
+/// aligned chip, and whether the fit is valid (`mi_face_align_roi`, host only).
+pub fn face_align_roi(points: &[[f32; 2]], source: AlignSource) -> Result<(Rect, bool), Error> {
+    let mut roi = Rect::new(0.5, 0.5, 1.0, 1.0, 0.0, true).to_mi();
+    let mut valid: i32 = 0;
+    check(unsafe { ffi::mi_face_align_roi(points.as_ptr() as *const f32, points.len() as i32, source.to_mi(), &mut roi, &mut valid) })?;
+    Ok((Rect::from_mi(&roi), valid != 0))
 }
 
 /// What `topk_select` and `Gallery::topk` return, `k` slots per query row: slots beyond the eligible rows hold -1 / -inf / -1.

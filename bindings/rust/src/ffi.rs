@@ -6,6 +6,9 @@ use std::os::raw::{c_char, c_double, c_float, c_int, c_long, c_void};
 pub const MI_OK: c_int = 0;
 pub const MI_MEM_HOST: c_int = 0;
 pub const MI_MEM_DEVICE: c_int = 1;
+pub const MI_ALIGN_POINTS: c_int = 0;
+pub const MI_ALIGN_MESH: c_int = 1;
+pub const MI_ALIGN_DETECTION: c_int = 2;
 pub const MI_NUM_FACE_LANDMARKS: usize = 468;
 pub const MI_NUM_EYE_LANDMARKS: usize = 71;
 pub const MI_NUM_IRIS_LANDMARKS: usize = 5;
@@ -220,6 +223,17 @@ extern "C" {
                                   faces: *const mi_detection, max_faces: c_int, item_frame: *const c_int, item_face: *const c_int,
                                   max_items: c_int, embeddings: *mut c_float, valid: *mut c_int, raw: *mut c_float, chips: *mut c_float,
                                   mem: c_int, stream: *mut c_void) -> c_int;
+    // aligned face chips (not the reference's behaviour: it crops the box); `source` is one of MI_ALIGN_*
+    pub fn mi_face_align_template(source: c_int, xy: *mut c_double, n: *mut c_int) -> c_int;
+    pub fn mi_face_align_roi(points_xy: *const c_float, n: c_int, source: c_int, roi: *mut mi_rect, valid: *mut c_int) -> c_int;
+    pub fn mi_face_align_points(source: c_int, landmarks_or_detection: *const c_float, width: c_int, height: c_int, points_xy: *mut c_float,
+                                n: *mut c_int) -> c_int;
+    pub fn mi_fe_infer_image_aligned(h: *mut mi_fe, rgb: *const u8, width: c_int, height: c_int, stride: c_int, points_xy: *const c_float,
+                                     n: c_int, source: c_int, embedding: *mut c_float, cap: c_int, roi: *mut mi_rect) -> c_int;
+    pub fn mi_fe_infer_aligned_items(h: *mut mi_fe, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int, source: c_int,
+                                     src: *const c_void, gate: *const c_int, max_faces: c_int, item_frame: *const c_int,
+                                     item_face: *const c_int, max_items: c_int, embeddings: *mut c_float, valid: *mut c_int,
+                                     raw: *mut c_float, chips: *mut c_float, rois: *mut mi_rect, mem: c_int, stream: *mut c_void) -> c_int;
     pub fn mi_l2_norm(input: *const c_float, n: c_int, out: *mut c_float) -> c_int;
     pub fn mi_similarity_score(a: *const c_float, b: *const c_float, n: c_int, out: *mut c_float) -> c_int;
     pub fn mi_similarity_matrix(device: c_int, a: *const c_float, n: c_int, b: *const c_float, m: c_int, features: c_int, out: *mut c_float,

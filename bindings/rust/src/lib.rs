@@ -25,7 +25,8 @@ pub mod render;
 pub mod utils;
 
 pub use face_detection::{FaceDetection, FaceDetectionModel};
-pub use face_embeddings::{face_chip_rect, topk_select, FaceEmbeddings, Gallery, ItemEmbeddings, TopK};
+pub use face_embeddings::{face_align_points, face_align_roi, face_align_template, face_chip_rect, topk_select, AlignSource, FaceEmbeddings, Gallery,
+                          ItemEmbeddings, TopK};
 pub use face_landmark::{face_detection_to_roi, FaceLandmark};
 pub use render::{
     detections_to_render_data, iris_landmarks_to_render_data, landmarks_to_render_data, render_face_items, render_to_image, Annotation,

@@ -427,6 +427,60 @@ int mi_fe_infer_face_items(mi_fe *h, const uint8_t *frames, int batch, int width
                            int max_faces, const int *item_frame, const int *item_face, int max_items, float *embeddings, int *valid,
                            float *raw, float *chips, int mem, void *stream);
 
+/* ---- Aligned face chips.  NOT the reference's behaviour: the reference crops the detector's box and resizes it (the two entries above,
+ * which keep every bit).  ArcFace-style networks are trained on chips in which the eyes, the nose tip and the mouth corners sit at five fixed
+ * positions of the 112 x 112 picture; these entries fit, per face, the least-squares similarity transform (rotation, uniform scale,
+ * translation) of the face's points to that template and warp the WHOLE frame by it: the transform is the rotated square ROI
+ * {x_center, y_center, side, side, rotation, normalized = 0} and the chip is image_to_tensor(frame, Some(roi), (112,112), false, (0,1), false)
+ * (transform.rs:188-234), BORDER_CONSTANT 0 outside the frame.
+ * Template (chip pixels), in the order image-left eye, image-right eye, nose tip, image-left mouth corner, image-right mouth corner:
+ *   (38.2946, 51.6963) (73.5318, 51.5014) (56.0252, 71.7366) (41.5493, 92.3655) (70.7299, 92.2041)
+ * `source` says where an item's points come from; every source ends in n f32 pixel points, which the fit widens to f64:
+ *   MI_ALIGN_POINTS     f32 [5][2] pixel coordinates in the template's order, as they are
+ *   MI_ALIGN_MESH       the item's 468 mesh landmarks (normalised; x * width, y * height in f64): the eyes are the midpoints of landmarks
+ *                       33 / 133 and 362 / 263, the nose tip is landmark 1, the mouth corners are 61 and 291
+ *   MI_ALIGN_DETECTION  the detection's key points 0..3 (eyes, nose tip, mouth CENTRE; data[4 + 2i] * width, data[5 + 2i] * height in f64)
+ *                       against the four-point template: the first three rows and the mean of the last two
+ * The fit (f64, sequential sums, no fused multiply-add; m = mean of the points, mq = mean of the template, d* = the differences to them):
+ *   A = sum(dx du + dy dv), B = sum(dx dv - dy du), S = sum(dx dx + dy dy), N = A A + B B, c = A S / N, d = -(B S / N),
+ *   side = 112 S / sqrt(N), rotation = atan2(-B, A), centre = m + (c + i d)((56, 56) - mq).
+ * It is invalid — and the ROI is then the whole image, {0.5, 0.5, 1, 1, 0, normalized = 1} — when a coordinate is not finite, when S or N is
+ * not a positive finite number (all points equal), or when side or the centre is not finite. */
+#define MI_ALIGN_POINTS 0
+#define MI_ALIGN_MESH 1
+#define MI_ALIGN_DETECTION 2
+
+/* Host only: the template of `source` -> xy (the rows behind *n are zeros), *n = 5, or 4 for MI_ALIGN_DETECTION. */
+int mi_face_align_template(int source, double xy[5][2], int *n);
+/* Host only, no GPU: the fit of n f32 pixel points against the template of `source` — the specification of the device code; both go through
+ * the same arithmetic.  n must be the template's n (5; 4 for MI_ALIGN_DETECTION), anything else is MI_EINVAL.  *valid = 0 for an invalid fit. */
+int mi_face_align_roi(const float *points_xy, int n, int source, mi_rect *roi, int *valid);
+/* Host only: the points of ONE item by the gather rule above — landmarks_or_detection = f32 [468][3] (MI_ALIGN_MESH), a detection's 17 floats
+ * (MI_ALIGN_DETECTION) or f32 [5][2] (MI_ALIGN_POINTS: copied) -> points_xy (rows behind *n are zeros), *n. */
+int mi_face_align_points(int source, const float *landmarks_or_detection, int width, int height, float points_xy[5][2], int *n);
+
+/* One picture in host memory: the fit of points_xy (n pixel points for the template of `source`, as mi_face_align_roi takes them), the
+ * aligned chip of the whole picture (all of it is uploaded), the network, l2_norm.  embedding = D floats, host memory; roi may be NULL.
+ * MI_ERANGE for an invalid fit; MI_EINVAL for cap < D or an n that is not the template's. */
+int mi_fe_infer_image_aligned(mi_fe *h, const uint8_t *rgb, int width, int height, int stride, const float *points_xy, int n, int source,
+                              float *embedding, int cap, mi_rect *roi);
+
+/* The aligned chips of EVERY item of what mi_pipeline_run_faces left in memory, as it lies there.  frames, item_frame, max_items, embeddings,
+ * valid, raw, chips, mem and stream are those of mi_fe_infer_face_items; src and gate depend on `source`:
+ *   MI_ALIGN_POINTS     src = f32 [max_items][5][2], gate = point_valid [max_items] or NULL
+ *   MI_ALIGN_MESH       src = landmarks f32 [max_items][468][3], gate = present [max_items]
+ *   MI_ALIGN_DETECTION  src = faces [batch][max_faces] (mi_detection), gate = NULL; item_face [max_items] and max_faces (1..16) are read
+ *                       for this source only
+ *   rois        mi_rect [max_items], may be NULL: the fitted ROI (the whole-image ROI for an invalid item)
+ * An item is invalid when its item_frame is outside 0..batch-1, its gate is 0, its item_face is outside 0..max_faces-1 or its fit is invalid:
+ * valid = 0, its rows of embeddings, raw and chips are zeros, and neither its frame nor its points, landmarks or detection is dereferenced.
+ * A valid ROI may lie wholly outside the frame: its chip is zeros and it has an embedding.  Two launches in front of the network, as the box
+ * path has; launch shapes depend on the arguments alone and nothing is read back.  max_items beyond 32767 is MI_EINVAL before anything is
+ * queued.  All pointers follow `mem`. */
+int mi_fe_infer_aligned_items(mi_fe *h, const uint8_t *frames, int batch, int width, int height, int stride, int source, const void *src,
+                              const int *gate, int max_faces, const int *item_frame, const int *item_face, int max_items, float *embeddings,
+                              int *valid, float *raw, float *chips, mi_rect *rois, int mem, void *stream);
+
 /* utils::l2_norm(arr) — utils.rs:30-33: out = in / sqrt(sum in^2), the sum in f32, in index order, the square and the add rounded
  * separately (iter().map().sum::<f32>()).  Host only, bit-identical to the reference's order of operations; out may alias in. */
 int mi_l2_norm(const float *in, int n, float *out);

@@ -402,7 +402,10 @@ struct FaceItemEmbeddings {       // mi_fe_infer_face_items, results in host mem
     std::vector<int> valid;          // [max_items]
     std::vector<float> raw;          // [max_items][D] when asked for: the network's output before l2_norm
     std::vector<float> chips;        // [max_items][112][112][3] when asked for: the network's input
+    std::vector<Rect> rois;          // [max_items], infer_items_aligned only: the fitted ROI (the whole image where the fit is invalid)
 };
+// where the points of an aligned chip come from (MI_ALIGN_*; mi_face.h states the gather rule and the fit)
+enum class AlignSource { Points = MI_ALIGN_POINTS, Mesh = MI_ALIGN_MESH, Detection = MI_ALIGN_DETECTION };
 class FaceEmbeddings {
    public:
     // FaceEmbeddings::new(model_path): a FILE path, default "./models/face_embeddings.tflite" (face_embeddings.rs:30-37)
@@ -453,10 +456,86 @@ class FaceEmbeddings {
         return o;
     }
 
+    // Aligned chips — NOT the reference's behaviour (it crops the box: infer / infer_items).  points: pixel coordinates in the template's
+    // order, five of them (four for AlignSource::Detection); the least-squares similarity fit to the template, the warp of the WHOLE image
+    // by it, the network, l2_norm.  Throws Error (MI_ERANGE) for points without a fit.  roi: the fitted ROI, when asked for.
+    std::vector<float> infer_aligned(const Image& image, const std::vector<std::array<float, 2>>& points, AlignSource source = AlignSource::Points,
+                                     Rect* roi = nullptr) const {
+        std::vector<float> out(static_cast<std::size_t>(features_));
+        mi_rect r = Rect{}.c();
+        const int rc = mi_fe_infer_image_aligned(h_, image.rgb, image.width, image.height, image.stride, points.empty() ? nullptr : points[0].data(),
+                                                 static_cast<int>(points.size()), static_cast<int>(source), out.data(), features_, &r);
+        if (roi) *roi = Rect::from(r);
+        detail::check(rc);
+        return out;
+    }
+    // ... for every item of what Pipeline::run_faces returned, frames in host memory: the points of an item from its mesh (landmarks, present),
+    // from its detection's key points, or from `points` ([max_items][5] pixel points, AlignSource::Points)
+    FaceItemEmbeddings infer_items_aligned(const std::uint8_t* frames, int batch, int width, int height, int stride, const FacesResults& r,
+                                           AlignSource source = AlignSource::Mesh, const std::vector<std::array<float, 2>>* points = nullptr,
+                                           bool want_raw = false, bool want_chips = false) const {
+        const std::size_t M = r.item_frame.size(), D = static_cast<std::size_t>(features_);
+        if (batch < 1 || M < 1 || M > 32767 || r.item_face.size() != M || r.faces.size() % static_cast<std::size_t>(batch) != 0)
+            throw std::invalid_argument("infer_items_aligned: the result of run_faces on these frames is expected (max_items 1..32767)");
+        const void* src = nullptr;
+        const int* gate = nullptr;
+        if (source == AlignSource::Mesh) {
+            if (r.landmarks.size() != M * MI_NUM_FACE_LANDMARKS * 3 || r.present.size() != M)
+                throw std::invalid_argument("infer_items_aligned: landmarks [max_items][468][3] and present [max_items] are expected");
+            src = r.landmarks.data();
+            gate = r.present.data();
+        } else if (source == AlignSource::Detection) {
+            src = r.faces.data();
+        } else {
+            if (!points || points->size() != M * 5) throw std::invalid_argument("infer_items_aligned: [max_items][5] pixel points are expected");
+            src = points->data();
+        }
+        FaceItemEmbeddings o;
+        o.features = features_;
+        o.embeddings.resize(M * D);
+        o.valid.resize(M);
+        if (want_raw) o.raw.resize(M * D);
+        if (want_chips) o.chips.resize(M * 3 * MI_FE_CHIP_SIZE * MI_FE_CHIP_SIZE);
+        std::vector<mi_rect> rois(M, Rect{}.c());
+        detail::check(mi_fe_infer_aligned_items(h_, frames, batch, width, height, stride, static_cast<int>(source), src, gate,
+                                                static_cast<int>(r.faces.size() / batch), r.item_frame.data(), r.item_face.data(), static_cast<int>(M),
+                                                o.embeddings.data(), o.valid.data(), want_raw ? o.raw.data() : nullptr,
+                                                want_chips ? o.chips.data() : nullptr, rois.data(), MI_MEM_HOST, nullptr));
+        for (const mi_rect& q : rois) o.rois.push_back(Rect::from(q));
+        return o;
+    }
+
    private:
     mi_fe* h_ = nullptr;
     int features_ = 0;
 };
+
+// Aligned chips, host only (mi_face.h): the template of a source in chip pixels; the pixel points of one face by the gather rule (src:
+// [468][3] normalised landmarks, a detection's 17 floats, or [5][2] points); the fit of such points as the ROI of the chip, and its validity
+inline std::vector<std::array<double, 2>> face_align_template(AlignSource source) {
+    double xy[5][2];
+    int n = 0;
+    detail::check(mi_face_align_template(static_cast<int>(source), xy, &n));
+    std::vector<std::array<double, 2>> out;
+    for (int i = 0; i < n; i++) out.push_back({xy[i][0], xy[i][1]});
+    return out;
+}
+inline std::vector<std::array<float, 2>> face_align_points(AlignSource source, const std::vector<float>& src, std::pair<int, int> image_size) {
+    const std::size_t need = source == AlignSource::Mesh ? MI_NUM_FACE_LANDMARKS * 3 : source == AlignSource::Detection ? 17 : 10;
+    if (src.size() != need) throw std::invalid_argument("face_align_points: the source's operand has another length");
+    float pts[5][2];
+    int n = 0;
+    detail::check(mi_face_align_points(static_cast<int>(source), src.data(), image_size.first, image_size.second, pts, &n));
+    std::vector<std::array<float, 2>> out;
+    for (int i = 0; i < n; i++) out.push_back({pts[i][0], pts[i][1]});
+    return out;
+}
+inline std::pair<Rect, bool> face_align_roi(const std::vector<std::array<float, 2>>& points, AlignSource source = AlignSource::Points) {
+    mi_rect r = Rect{}.c();
+    int valid = 0;
+    detail::check(mi_face_align_roi(points.empty() ? nullptr : points[0].data(), static_cast<int>(points.size()), static_cast<int>(source), &r, &valid));
+    return {Rect::from(r), valid != 0};
+}
 
 // crop_image_to_bbox's rectangle for a detection (face_embeddings.rs:101-109 on bbox().scale(size)); host only.  -> {x, y, w, h}, valid
 inline std::pair<std::array<int, 4>, bool> face_chip_rect(const Detection& d, std::pair<int, int> image_size) {

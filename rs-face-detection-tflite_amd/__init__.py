@@ -12,5 +12,6 @@ from .api import (  # noqa: F401
     ANN_FILLED_RECTS, ANN_LINES, ANN_POINTS, ANN_RECTS, Annotation, Color, Colors, RenderStyle, render_annotations, render_faces,
     RenderItemsStyle, render_face_items,
     FE_CHIP_SIZE, FaceEmbeddings, face_chip_rect, l2_norm, similarity_score, similarity_matrix,
+    ALIGN_SOURCES, RECT_DTYPE, face_align_points, face_align_roi, face_align_template,
     TOPK_MAX_K, Gallery, topk_select,
 )

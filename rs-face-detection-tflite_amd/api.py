@@ -43,7 +43,8 @@ EXPORTS = [
     "mi_bbox_to_roi", "mi_bbox_from_landmarks", "mi_face_detection_to_roi", "mi_iris_roi_from_face_landmarks", "mi_update_face_landmarks_with_iris_results", "mi_image_to_tensor", "mi_jpeg_info", "mi_jpeg_decode_rgb",
     "mi_render_annotations", "mi_render_faces", "mi_render_face_items",
     "mi_fe_create", "mi_fe_create_from_bytes", "mi_fe_free", "mi_fe_model", "mi_fe_features", "mi_face_chip_rect", "mi_fe_infer_image",
-    "mi_fe_infer_face_items", "mi_l2_norm", "mi_similarity_score", "mi_similarity_matrix",
+    "mi_fe_infer_face_items", "mi_face_align_template", "mi_face_align_roi", "mi_face_align_points", "mi_fe_infer_image_aligned",
+    "mi_fe_infer_aligned_items", "mi_l2_norm", "mi_similarity_score", "mi_similarity_matrix",
     "mi_topk_select", "mi_gallery_create", "mi_gallery_free", "mi_gallery_dims", "mi_gallery_set_option", "mi_gallery_get_option", "mi_gallery_topk",
 ]
 
@@ -336,6 +337,12 @@ def lib():
     L.mi_face_chip_rect.argtypes = [C.POINTER(CDetection), C.c_int, C.c_int, ip, ip]
     L.mi_fe_infer_image.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dp, vp, C.c_int]
     L.mi_fe_infer_face_items.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp]
+    L.mi_face_align_template.argtypes = [C.c_int, vp, ip]
+    L.mi_face_align_roi.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Rect), ip]
+    L.mi_face_align_points.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, ip]
+    L.mi_fe_infer_image_aligned.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(Rect)]
+    L.mi_fe_infer_aligned_items.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp,
+                                            C.c_int, vp]
     L.mi_l2_norm.argtypes = [vp, C.c_int, vp]
     L.mi_similarity_score.argtypes = [vp, vp, C.c_int, fp]
     L.mi_similarity_matrix.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]
@@ -1284,6 +1291,124 @@ class FaceEmbeddings:
         _check(self.L.mi_fe_infer_face_items(self.h, p, B, W, H, stride, pf, F, pi, pk, M, _ptr(out["embeddings"])[0], _ptr(out["valid"])[0],
                                              opt("raw"), opt("chips"), mem, C.c_void_p(stream or 0)))
         return out
+
+    def infer_aligned(self, image, points, source="points", cap=None, want_roi=False):
+        """mi_fe_infer_image_aligned — NOT the reference's chip (the reference crops the box: infer()).  `points`: pixel coordinates [5,2] in the
+        template's order (face_align_template), or [4,2] with source="detection" (eyes, nose tip, mouth centre); face_align_points gathers them
+        from a mesh or a detection.  The least-squares similarity fit to the template, the warp of the WHOLE image by it, the network, l2_norm
+        -> float32 [1, D] (with want_roi: (embedding, Rect)).  MiError (MI_ERANGE) for points without a fit."""
+        image, w, h, stride = _image_args(image)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        cap = self.features if cap is None else int(cap)
+        out = np.zeros((1, max(cap, 1)), np.float32)
+        roi = Rect()
+        _check(self.L.mi_fe_infer_image_aligned(self.h, C.c_void_p(image.ctypes.data), w, h, stride, C.c_void_p(pts.ctypes.data), int(pts.shape[0]),
+                                                _align_source(source), C.c_void_p(out.ctypes.data), cap, C.byref(roi)))
+        return (out[:, :self.features], roi) if want_roi else out[:, :self.features]
+
+    def infer_items_aligned(self, frames, result, source="mesh", points=None, point_valid=None, want_raw=False, want_chips=False, want_rois=False,
+                            stream=None):
+        """mi_fe_infer_aligned_items on what Pipeline.run_faces returned, as it lies in memory — NOT the reference's chips (infer_items is the
+        box path).  source "mesh": result's landmarks [M,468,3], present [M] and item_frame [M] are read; "detection": faces [B,F,17], item_frame
+        and item_face; "points": `points` float32 [M,5,2] pixel coordinates, `point_valid` int32 [M] or None, and result's item_frame.  Returns
+        dict(embeddings [M,D], valid [M]) plus raw [M,D], chips [M,112,112,3] and rois when asked for: a numpy array of RECT_DTYPE [M] for host
+        frames, a uint8 CUDA tensor [M,48] holding the same bytes for device frames.  Rows of invalid items are zeros."""
+        p, mem, B, H, W, stride = _picture(frames, 3, "frames")
+        if mem == MI_MEM_DEVICE:
+            _device_ready(frames, self.device, None, "uint8")
+        src_id = _align_source(source)
+        shape = lambda x: tuple(int(v) for v in x.shape)
+        item_frame = result["item_frame"]
+        if item_frame.ndim != 1:
+            raise ValueError("item_frame must be [M]")
+        M, F = shape(item_frame)[0], 1
+        pk = pg = None
+        if source == "mesh":
+            src, gate = result["landmarks"], result["present"]
+            if shape(src) != (M, NUM_FACE_LANDMARKS, 3) or shape(gate) != (M,):
+                raise ValueError("landmarks must be [M,468,3] and present [M]")
+        elif source == "detection":
+            src, gate = result["faces"], None
+            if src.ndim != 3 or shape(src)[0] != B or shape(src)[2] != 17 or shape(result["item_face"]) != (M,):
+                raise ValueError("faces must be [B,F,17] and item_face [M]")
+            F = shape(src)[1]
+        else:
+            src, gate = points, point_valid
+            if src is None or shape(src) != (M, 5, 2) or (gate is not None and shape(gate) != (M,)):
+                raise ValueError("points must be [M,5,2] and point_valid [M] or None")
+        if not (1 <= F <= 16 and 1 <= M <= 32767):   # (before the outputs are sized by them; the C entry checks again)
+            raise MiError(-1, "max_faces must be 1..16 and max_items 1..32767")   # MI_EINVAL
+        ps, src = _render_operand(src, mem, self.device, "float32", "the source's points")
+        pg, gate = _render_operand(gate, mem, self.device, "int32", "the source's gate")
+        pi, item_frame = _render_operand(item_frame, mem, self.device, "int32", "item_frame")
+        if source == "detection":
+            pk, item_face = _render_operand(result["item_face"], mem, self.device, "int32", "item_face")
+        D = self.features
+        shapes = dict(embeddings=((M, D), "float32"), valid=((M,), "int32"))
+        if want_raw:
+            shapes["raw"] = ((M, D), "float32")
+        if want_chips:
+            shapes["chips"] = ((M, FE_CHIP_SIZE, FE_CHIP_SIZE, 3), "float32")
+        if want_rois:
+            shapes["rois"] = ((M, RECT_DTYPE.itemsize), "uint8")
+        if mem == MI_MEM_DEVICE:
+            import torch
+            out = {k: torch.zeros(sh, dtype=getattr(torch, dt), device=frames.device) for k, (sh, dt) in shapes.items()}
+            torch.cuda.current_stream(frames.device).synchronize()   # (the zero fills above were queued on torch's stream)
+        else:
+            out = {k: np.zeros(sh, getattr(np, dt)) for k, (sh, dt) in shapes.items()}
+        opt = lambda k: _ptr(out[k])[0] if k in out else None
+        _check(self.L.mi_fe_infer_aligned_items(self.h, p, B, W, H, stride, src_id, ps, pg, F, pi, pk, M, _ptr(out["embeddings"])[0],
+                                                _ptr(out["valid"])[0], opt("raw"), opt("chips"), opt("rois"), mem, C.c_void_p(stream or 0)))
+        if want_rois and mem == MI_MEM_HOST:
+            out["rois"] = out["rois"].view(RECT_DTYPE).reshape(M)
+        return out
+
+
+ALIGN_SOURCES = {"points": 0, "mesh": 1, "detection": 2}   # MI_ALIGN_POINTS / MI_ALIGN_MESH / MI_ALIGN_DETECTION
+# mi_rect as it lies in memory (the rois of FaceEmbeddings.infer_items_aligned)
+RECT_DTYPE = np.dtype([("x_center", "<f8"), ("y_center", "<f8"), ("width", "<f8"), ("height", "<f8"), ("rotation", "<f8"), ("normalized", "<i4"),
+                       ("pad", "<i4")])
+
+
+def _align_source(source):
+    if source not in ALIGN_SOURCES:
+        raise ValueError("source must be one of %s, not %r" % (sorted(ALIGN_SOURCES), source))
+    return ALIGN_SOURCES[source]
+
+
+def face_align_template(source="points"):
+    """mi_face_align_template (host only): the destination points of the aligned chip, float64 [5,2] in chip pixels (image-left eye,
+    image-right eye, nose tip, image-left and image-right mouth corner), or [4,2] for source="detection" (the mouth's centre instead)."""
+    xy, n = np.zeros((5, 2), np.float64), C.c_int()
+    _check(lib().mi_face_align_template(_align_source(source), C.c_void_p(xy.ctypes.data), C.byref(n)))
+    return xy[:n.value].copy()
+
+
+def face_align_points(source, landmarks_or_detection, image_size):
+    """mi_face_align_points (host only): the pixel points of one face, float32 [5,2] from its mesh (source="mesh": landmarks [468,3],
+    normalised) or [4,2] from its detection (source="detection": a Detection or 17 floats); image_size = (width, height)."""
+    x = landmarks_or_detection
+    if isinstance(x, Detection):
+        x = np.concatenate([np.asarray(x.data, np.float32).reshape(-1), [np.float32(x.score)]])
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    need = (10, 3 * NUM_FACE_LANDMARKS, 17)[_align_source(source)]
+    if x.size != need:
+        raise ValueError("source %r takes %d floats, not %d" % (source, need, x.size))
+    pts, n = np.zeros((5, 2), np.float32), C.c_int()
+    _check(lib().mi_face_align_points(_align_source(source), C.c_void_p(x.ctypes.data), int(image_size[0]), int(image_size[1]),
+                                      C.c_void_p(pts.ctypes.data), C.byref(n)))
+    return pts[:n.value].copy()
+
+
+def face_align_roi(points, source="points"):
+    """mi_face_align_roi (host only, no GPU): the least-squares similarity fit of pixel `points` ([5,2]; [4,2] for source="detection") to the
+    template, as the rotated square Rect whose warp to 112 x 112 is the aligned chip -> (Rect, valid).  An invalid fit (a coordinate that is
+    not finite, all points equal) gives the whole-image Rect and valid = False; a wrong number of points is MiError (MI_EINVAL)."""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+    roi, valid = Rect(), C.c_int()
+    _check(lib().mi_face_align_roi(C.c_void_p(pts.ctypes.data), int(pts.shape[0]), _align_source(source), C.byref(roi), C.byref(valid)))
+    return roi, bool(valid.value)
 
 
 def face_chip_rect(detection, image_size):

@@ -1,5 +1,6 @@
 // capi_embed.cpp — FaceEmbeddings, similarity and top-k, and the gallery.
 #include "capi_internal.hpp"
+#include "face_align.hpp"
 
 using namespace mi::capi;
 
@@ -8,6 +9,7 @@ struct mi_fe {
     mi_model model;
     int features = 0;   // D
     DeviceBuf d_in, d_geom, d_valid, d_img, d_frames, d_faces, d_item_frame, d_item_face, d_emb, d_raw;
+    DeviceBuf d_gate, d_rois;   // the aligned entries: point_valid / present, the fitted ROIs
 };
 
 // A gallery of enrolled embeddings (mi_gallery_topk): the rows and labels in device memory, uploaded once, and the scratch of a call —
@@ -132,6 +134,125 @@ int mi_fe_infer_face_items(mi_fe* h, const uint8_t* frames, int batch, int width
         hand_back(embeddings, d_emb, n_emb, mem, s, "D2H embeddings");
         hand_back(raw, d_raw, n_emb, mem, s, "D2H raw");
         hand_back(valid, d_valid, M, mem, s, "D2H valid");
+        c.finish(mem);
+    });
+}
+
+// ---- aligned chips (face_align.hpp): not the reference's chips; the entries above keep every bit and every launch they have
+static int align_template_n(int source) {
+    double u[mi::kAlignMaxPoints], v[mi::kAlignMaxPoints];
+    const int n = mi::face_align_template(source, u, v);
+    require(n > 0, "source must be MI_ALIGN_POINTS, MI_ALIGN_MESH or MI_ALIGN_DETECTION");
+    return n;
+}
+
+int mi_face_align_template(int source, double xy[5][2], int* n) {
+    return guarded([&] {
+        require(xy && n, "null argument");
+        align_template_n(source);
+        double u[mi::kAlignMaxPoints], v[mi::kAlignMaxPoints];
+        *n = mi::face_align_template(source, u, v);
+        for (int i = 0; i < mi::kAlignMaxPoints; i++) { xy[i][0] = i < *n ? u[i] : 0.0; xy[i][1] = i < *n ? v[i] : 0.0; }
+    });
+}
+
+int mi_face_align_roi(const float* points_xy, int n, int source, mi_rect* roi, int* valid) {
+    return guarded([&] {
+        require(points_xy && roi && valid, "null argument");
+        require(n == align_template_n(source), "n must be the template's point count (5; 4 for MI_ALIGN_DETECTION)");
+        static_assert(sizeof(mi_rect) == sizeof(mi::RectD), "mi_rect layout");
+        mi::RectD r;
+        *valid = mi::face_align_roi_points(reinterpret_cast<const float(*)[2]>(points_xy), n, source, &r);
+        std::memcpy(roi, &r, sizeof r);
+    });
+}
+
+int mi_face_align_points(int source, const float* landmarks_or_detection, int width, int height, float points_xy[5][2], int* n) {
+    return guarded([&] {
+        require(landmarks_or_detection && points_xy && n, "null argument");
+        require(width > 0 && height > 0, "bad image geometry");
+        align_template_n(source);
+        *n = mi::face_align_gather(source, landmarks_or_detection, width, height, points_xy);
+    });
+}
+
+int mi_fe_infer_image_aligned(mi_fe* h, const uint8_t* rgb, int width, int height, int stride, const float* points_xy, int n, int source,
+                              float* embedding, int cap, mi_rect* roi) {
+    return guarded([&] {
+        require(h && rgb && points_xy && embedding, "null argument");
+        require(width > 0 && height > 0 && stride >= 3 * static_cast<long>(width), "bad image geometry");
+        require(n == align_template_n(source), "n must be the template's point count (5; 4 for MI_ALIGN_DETECTION)");
+        require(cap >= h->features, "output capacity is smaller than the model's feature count");
+        mi::RectD r;
+        const int ok = mi::face_align_roi_points(reinterpret_cast<const float(*)[2]>(points_xy), n, source, &r);
+        if (roi) std::memcpy(roi, &r, sizeof r);
+        if (!ok) throw ApiError(MI_ERANGE, "the points have no similarity fit (a coordinate is not finite, or all points are equal)");
+        Call c(h->model);
+        mi::Model& m = c.m;
+        const hipStream_t s = c.s;
+        const int D = h->features;
+        // the WHOLE picture travels: a crop with a shifted ROI would round the ROI's corners to other floats; the last row owns 3 * width bytes
+        const size_t bytes = static_cast<size_t>(stride) * (height - 1) + static_cast<size_t>(3) * width;
+        float* d_in = h->d_in.as<float>(m.input_elems());
+        float* d_emb = h->d_emb.as<float>(D);
+        const uint8_t* d_img = stage(h->d_img, rgb, bytes, MI_MEM_HOST, s, "H2D image");
+        mi::aligned_chip_enqueue_one(d_img, width, height, stride, r, d_in, s);
+        m.run_device(d_in, 1, s);
+        mi::launch_l2_norm(m.output_device(0), nullptr, 1, D, d_emb, nullptr, s);
+        hand_back(embedding, d_emb, D, MI_MEM_HOST, s, "D2H embedding");
+        c.sync();
+    });
+}
+
+int mi_fe_infer_aligned_items(mi_fe* h, const uint8_t* frames, int batch, int width, int height, int stride, int source, const void* src,
+                              const int* gate, int max_faces, const int* item_frame, const int* item_face, int max_items, float* embeddings,
+                              int* valid, float* raw, float* chips, mi_rect* rois, int mem, void* stream) {
+    return guarded([&] {
+        // (a budget the launches cannot take is refused here, before anything is queued)
+        align_template_n(source);
+        const bool det = source == MI_ALIGN_DETECTION;
+        require_face_items(batch, det ? max_faces : 1, max_items, mi::kFaceItemsMaxRunItems, "max_items must be 1..32767 (one grid row of a launch per item)");
+        require(h && frames && src && item_frame && embeddings && valid, "null argument");
+        require(!det || item_face, "MI_ALIGN_DETECTION needs item_face");
+        require(source != MI_ALIGN_MESH || gate, "MI_ALIGN_MESH needs `present` as its gate");
+        require(width > 0 && height > 0 && stride >= 3 * static_cast<long>(width), "bad frame geometry");
+        require_mem(mem);
+        static_assert(sizeof(mi_detection) == 17 * sizeof(float), "mi_detection layout");
+        static_assert(sizeof(mi_rect) == sizeof(mi::RectD), "mi_rect layout");
+        Call c(h->model, stream);
+        mi::Model& m = c.m;
+        const hipStream_t s = c.s;
+        const int B = batch, M = max_items, D = h->features;
+        const size_t chip_floats = m.input_elems(), n_emb = static_cast<size_t>(D) * M;
+        const char* what = "H2D operands";
+        const size_t src_floats = source == MI_ALIGN_POINTS ? static_cast<size_t>(M) * 2 * mi::kAlignMaxPoints
+                                  : source == MI_ALIGN_MESH ? static_cast<size_t>(M) * 3 * mi::kAlignMeshLandmarks
+                                                            : static_cast<size_t>(B) * max_faces * 17;
+        mi::AlignItems it{};
+        it.frames = stage_frames(h->d_frames, frames, B, width, height, stride, mem, s);
+        it.frame_bytes = static_cast<long>(stride) * height; it.batch = B; it.width = width; it.height = height; it.stride = stride;
+        it.source = source;
+        it.src = stage(h->d_faces, static_cast<const float*>(src), src_floats, mem, s, what);
+        it.gate = det ? nullptr : stage(h->d_gate, gate, M, mem, s, what);
+        it.max_faces = det ? max_faces : 0; it.N = M;
+        it.item_frame = stage(h->d_item_frame, item_frame, M, mem, s, what);
+        it.item_face = det ? stage(h->d_item_face, item_face, M, mem, s, what) : nullptr;
+        float* d_emb = result_target(h->d_emb, embeddings, n_emb, mem);
+        float* d_raw = raw ? result_target(h->d_raw, raw, n_emb, mem) : nullptr;
+        int* d_valid = result_target(h->d_valid, valid, M, mem);
+        auto* d_rois = rois ? reinterpret_cast<mi::RectD*>(result_target(h->d_rois, rois, M, mem)) : nullptr;
+        // the network's input is the handle's own buffer whatever `chips` is: the engine keys its captured graphs by that address
+        auto* d_geom = h->d_geom.as<mi::PreGeom>(M);
+        float* d_in = h->d_in.as<float>(chip_floats * M);
+        mi::launch_align_geom(it, d_geom, d_rois, d_valid, s);
+        mi::launch_aligned_chips(it, d_geom, d_in, s);
+        m.run_device(d_in, M, s);
+        mi::launch_l2_norm(m.output_device(0), d_valid, M, D, d_emb, d_raw, s);
+        if (chips) mi::hip_check(hipMemcpyAsync(chips, d_in, chip_floats * sizeof(float) * M, mem == MI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s), "chips copy");
+        hand_back(embeddings, d_emb, n_emb, mem, s, "D2H embeddings");
+        hand_back(raw, d_raw, n_emb, mem, s, "D2H raw");
+        hand_back(valid, d_valid, M, mem, s, "D2H valid");
+        hand_back(rois, reinterpret_cast<const mi_rect*>(d_rois), M, mem, s, "D2H rois");
         c.finish(mem);
     });
 }

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "face_align.hpp"
 #include "face_chip.hpp"
 #include "face_items.hpp"
 #include "roi_dev.hpp"
@@ -459,9 +460,92 @@ __global__ __launch_bounds__(256) void chip_tensor_one_kernel(ChipGeom c, const 
     chip_px(c, crop, stride, idx, out + (long)idx * 3);
 }
 
+// ---------------------------------------------------------------------------------------------- aligned face chips (face_align.hpp)
+// Eight lanes per item, as chip_geom_kernel: the item's points by source, the fit, then compute_geom of the fitted ROI on the whole frame.
+// An item that is gated off reads neither its points, its landmarks nor its detection; its lanes still run the elimination (on the default
+// ROI, which is what a failed fit leaves as well) so that the shuffles stay convergent.
+__global__ __launch_bounds__(64) void align_geom_kernel(AlignItems it, PreGeom* geom, RectD* rois, int* valid) {
+    const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 3, sub = threadIdx.x & 7;
+    if (i >= it.N) return;   // whole groups of 8 lanes
+    const int b = it.item_frame[i];
+    RectD roi;
+    face_align_default_roi(&roi);
+    int ok = 0;
+    if (b >= 0 && b < it.batch) {
+        const float* src = nullptr;
+        if (it.source == kAlignPoints) {
+            if (!it.gate || it.gate[i]) src = it.src + (long)i * (2 * kAlignMaxPoints);
+        } else if (it.source == kAlignMesh) {
+            if (!it.gate || it.gate[i]) src = it.src + (long)i * (3 * kAlignMeshLandmarks);
+        } else {
+            const int k = it.item_face[i];
+            if (k >= 0 && k < it.max_faces) src = it.src + ((long)b * it.max_faces + k) * 17;
+        }
+        if (src) {
+            float pts[kAlignMaxPoints][2];
+            const int n = face_align_gather(it.source, src, it.width, it.height, pts);
+            ok = face_align_roi_points(pts, n, it.source, &roi);
+        }
+    }
+    PreGeom g = compute_geom(it.width, it.height, &roi, kChipSize, kChipSize, false, nullptr, 1, sub);
+    if (!g.valid) ok = 0;
+    g.valid = ok;
+    if (sub) return;
+    geom[i] = g;
+    if (rois) rois[i] = roi;
+    valid[i] = ok;
+}
+
+// the warped pixel of the whole frame, then chip_px's conversion `(pixel as f64 * (1 - 0) / 255.0 + 0) as f32`
+__device__ __forceinline__ void aligned_px(const PreGeom& g, const uint8_t* frame, int width, int height, int stride, int idx, float* __restrict__ o) {
+    if (!g.valid) { o[0] = o[1] = o[2] = 0.f; return; }
+    const int y = idx / kChipSize, x = idx - y * kChipSize;
+    const Px p = warp_px(g, frame, width, height, stride, y, x);
+    const double k = 1.0 - 0.0;
+    o[0] = (float)((double)p.r * k / 255.0 + 0.0);
+    o[1] = (float)((double)p.g * k / 255.0 + 0.0);
+    o[2] = (float)((double)p.b * k / 255.0 + 0.0);
+}
+
+__global__ __launch_bounds__(256) void aligned_chip_kernel(AlignItems it, const PreGeom* __restrict__ geom, float* __restrict__ out) {
+    const int i = blockIdx.y;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= kChipSize * kChipSize) return;
+    const PreGeom g = geom[i];
+    // (behind g.valid: the frame of an unused slot is -1)
+    const uint8_t* frame = g.valid ? it.frames + (long)it.item_frame[i] * it.frame_bytes : nullptr;
+    aligned_px(g, frame, it.width, it.height, it.stride, idx, out + ((long)i * kChipSize * kChipSize + idx) * 3);
+}
+
+__global__ __launch_bounds__(256) void aligned_chip_one_kernel(PreGeom g, const uint8_t* __restrict__ frame, int width, int height, int stride, float* __restrict__ out) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= kChipSize * kChipSize) return;
+    aligned_px(g, frame, width, height, stride, idx, out + (long)idx * 3);
+}
+
 size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 }  // namespace
+
+void launch_align_geom(const AlignItems& it, PreGeom* d_geom, RectD* d_rois, int* d_valid, hipStream_t s) {
+    if (it.N <= 0) return;
+    hipLaunchKernelGGL(align_geom_kernel, dim3((it.N + 7) / 8), dim3(64), 0, s, it, d_geom, d_rois, d_valid);
+    hip_check(hipGetLastError(), "align_geom kernel launch");
+}
+
+void launch_aligned_chips(const AlignItems& it, const PreGeom* d_geom, float* d_out, hipStream_t s) {
+    if (it.N <= 0) return;
+    dim3 grid((kChipSize * kChipSize + 255) / 256, it.N);
+    hipLaunchKernelGGL(aligned_chip_kernel, grid, dim3(256), 0, s, it, d_geom, d_out);
+    hip_check(hipGetLastError(), "aligned_chip kernel launch");
+}
+
+void aligned_chip_enqueue_one(const uint8_t* d_img, int width, int height, int stride, const RectD& roi, float* d_out, hipStream_t s) {
+    const PreGeom g = compute_geom(width, height, &roi, kChipSize, kChipSize, false);   // same code as the device path
+    if (!g.valid) throw std::runtime_error("aligned ROI is degenerate (singular perspective transform)");
+    hipLaunchKernelGGL(aligned_chip_one_kernel, dim3((kChipSize * kChipSize + 255) / 256), dim3(256), 0, s, g, d_img, width, height, stride, d_out);
+    hip_check(hipGetLastError(), "aligned_chip kernel launch");
+}
 
 void launch_chip_geom(const ChipItems& it, ChipGeom* d_geom, int* d_valid, hipStream_t s) {
     if (it.N <= 0) return;

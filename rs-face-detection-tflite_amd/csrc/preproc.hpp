@@ -108,4 +108,27 @@ void launch_chip_tensor(const ChipItems& it, const ChipGeom* d_geom, float* d_ou
 // the crop's first pixel, rows `stride` bytes apart.
 void chip_tensor_enqueue_one(const uint8_t* d_crop, int w, int h, int stride, float* d_out, hipStream_t s);
 
+// Aligned face chips (face_align.hpp; NOT the reference's chips): per item a least-squares similarity fit of its points to the five-point
+// template, as a rotated square ROI of the WHOLE frame warped to 112 x 112 — image_to_tensor(frame, Some(roi), (112,112), false, (0,1), false),
+// so BORDER_CONSTANT 0 applies at the frame's edge.
+struct AlignItems {             // device pointers
+    const uint8_t* frames;      // [batch][height][stride] RGB u8
+    long frame_bytes;
+    int batch, width, height, stride;
+    int source;                 // kAlignPoints / kAlignMesh / kAlignDetection
+    const float* src;           // points [N][5][2] / landmarks [N][468][3] / faces [batch][max_faces][17]
+    const int* gate;            // point_valid [N] or null / present [N] / unused
+    int max_faces;              // kAlignDetection only
+    const int* item_frame;      // [N]: -1 = unused slot
+    const int* item_face;       // [N], kAlignDetection only
+    int N;
+};
+// one geometry step per item (eight lanes each): gather, fit and the ROI's homography; d_rois may be null.  valid[i] = 0 for an unused slot,
+// an index outside the arrays, a gate of 0 or a fit that fails — neither the frame nor any operand row of such an item is read
+void launch_align_geom(const AlignItems& it, PreGeom* d_geom, RectD* d_rois, int* d_valid, hipStream_t s);
+// one thread per output pixel; out f32 [N][112][112][3], zeros for an invalid item
+void launch_aligned_chips(const AlignItems& it, const PreGeom* d_geom, float* d_out, hipStream_t s);
+// The same for ONE picture in device memory whose ROI the host has fitted: the geometry (same code, on the host) travels as a kernel argument.
+void aligned_chip_enqueue_one(const uint8_t* d_img, int width, int height, int stride, const RectD& roi, float* d_out, hipStream_t s);
+
 }  // namespace mi
