@@ -105,6 +105,7 @@ pub struct mi_render_items_style {
 #[repr(C)] pub struct mi_fl { _private: [u8; 0] }
 #[repr(C)] pub struct mi_iris { _private: [u8; 0] }
 #[repr(C)] pub struct mi_pipeline { _private: [u8; 0] }
+#[repr(C)] pub struct mi_tracker { _private: [u8; 0] }
 #[repr(C)] pub struct mi_fe { _private: [u8; 0] }
 #[repr(C)] pub struct mi_gallery { _private: [u8; 0] }
 #[repr(C)] pub struct mi_model { _private: [u8; 0] }
@@ -192,6 +193,21 @@ extern "C" {
                                  present: *mut c_int, eyes: *mut c_float, mem: c_int, stream: *mut c_void) -> c_int;
     pub fn mi_face_items_layout(face_counts: *const c_int, batch: c_int, max_faces: c_int, max_items: c_int, item_frame: *mut c_int,
                                 item_face: *mut c_int, n_items: *mut c_int) -> c_int;
+
+    // landmark-to-ROI face tracking for video streams (NOT the reference's behaviour: MediaPipe's video loop; include/mi_face.h)
+    pub fn mi_track_roi_from_landmarks(landmarks: *const c_float, width: c_int, height: c_int, roi: *mut mi_rect, valid: *mut c_int) -> c_int;
+    pub fn mi_track_detect_layout(tracked: *const c_int, streams: c_int, max_detect: c_int, start: c_int, det_stream: *mut c_int,
+                                  n_detect: *mut c_int) -> c_int;
+    pub fn mi_tracker_create(fd_kind: c_int, model_dir: *const c_char, device: c_int, streams: c_int, out: *mut *mut mi_tracker) -> c_int;
+    pub fn mi_tracker_free(t: *mut mi_tracker);
+    pub fn mi_tracker_set_option(t: *mut mi_tracker, key: *const c_char, value: c_int) -> c_int;
+    pub fn mi_tracker_step(t: *mut mi_tracker, frames: *const u8, width: c_int, height: c_int, stride: c_int, max_detect: c_int,
+                           faces: *mut mi_detection, face_counts: *mut c_int, source: *mut c_int, rois: *mut mi_rect, landmarks: *mut c_float,
+                           present: *mut c_int, eyes: *mut c_float, det_stream: *mut c_int, n_detect: *mut c_int, mem: c_int,
+                           stream: *mut c_void) -> c_int;
+    pub fn mi_tracker_reset(t: *mut mi_tracker, stream_index: c_int) -> c_int;
+    pub fn mi_tracker_get_state(t: *mut mi_tracker, rois: *mut mi_rect, tracked: *mut c_int) -> c_int;
+    pub fn mi_tracker_set_state(t: *mut mi_tracker, first: c_int, n: c_int, rois: *const mi_rect, tracked: *const c_int) -> c_int;
 
     // render.rs:262-479 on the device
     pub fn mi_render_annotations(device: c_int, frames: *const u8, batch: c_int, width: c_int, height: c_int, stride: c_int,

@@ -22,6 +22,7 @@ pub mod face_landmark;
 pub mod iris_landmark;
 pub mod pipeline;
 pub mod render;
+pub mod tracker;
 pub mod utils;
 
 pub use face_detection::{FaceDetection, FaceDetectionModel};
@@ -34,6 +35,7 @@ pub use render::{
 };
 pub use iris_landmark::{iris_roi_from_face_landmarks, update_face_landmarks_with_iris_results, IrisLandmark};
 pub use pipeline::{face_items_layout, FacesResults, Pipeline};
+pub use tracker::{track_detect_layout, track_roi_from_landmarks, TrackStep, Tracker};
 pub use types::{BBox, Detection, Image, IrisResults, Landmark, Rect};
 pub use utils::{l2_norm, similarity_matrix, similarity_score};
 

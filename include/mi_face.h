@@ -365,6 +365,76 @@ int mi_pipeline_collect_jpeg(mi_pipeline *p, int slot, mi_detection *face, int *
                              int *width, int *height);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * mi_tracker — landmark-to-ROI face tracking for `streams` video streams, one face per stream (MediaPipe's num_faces = 1).
+ * NOT the reference's behaviour: the reference has no video loop.  This is MediaPipe's: the ROI of frame t+1 comes from the landmarks of
+ * frame t, and the detector runs only for a stream that has no face yet or has lost it — composed from the reference's own
+ * bbox_from_landmarks (transform.rs:146-165) and bbox_to_roi (transform.rs:44-109), the way iris_roi_from_face_landmarks composes them
+ * for the eyes (iris_landmark.rs:268-292).  The per-stream state {ROI, tracked} lives in device memory; a step reads nothing back.
+ *
+ * TRACKED ROI of landmarks f32 [468][3] (normalised to the frame, as the pipeline writes them): bbox = min / max of x and of y over all 468
+ * landmarks (f64); rotation key points = landmarks 33 and 263 (the outer eye corners) in PIXELS, (x * width, y * height);
+ * roi = bbox_to_roi(bbox, (width, height), key points, scale (1.5, 1.5), SquareLong).  Valid iff all 936 x / y values are finite, the box
+ * is normalised (BBox::normalized), width > 0 and height > 0.
+ * DETECT PLAN: the streams with tracked == 0 get the `max_detect` detector slots in cyclic stream order beginning at stream `start`; slot j
+ * is the j-th lost stream met from `start` on; det_stream[max_detect] holds -1 in unused slots; n_detect = {slots used, lost streams left
+ * without a slot}.  A handle starts at 0 and advances start by max_detect modulo streams after every step, so a stream that stays lost gets
+ * a slot at least once in any ceil(streams / max_detect) consecutive steps, however many streams never show a face.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct mi_tracker mi_tracker;
+
+/* Host only, no GPU: the two rules (the specification of the device kernels; both sides go through the same arithmetic).
+ * mi_track_roi_from_landmarks: *valid = 0 and a zeroed *roi for an invalid set.  MI_EINVAL for a null pointer or a size below 1.
+ * mi_track_detect_layout: tracked [streams], streams 1..2^20, max_detect 1..streams, start 0..streams-1; anything else is MI_EINVAL. */
+int mi_track_roi_from_landmarks(const float *landmarks, int width, int height, mi_rect *roi, int *valid);
+int mi_track_detect_layout(const int *tracked, int streams, int max_detect, int start, int *det_stream, int *n_detect);
+
+/* A tracker owns its three networks (as mi_pipeline_create / mi_pipeline_create_from_bytes load them) and every buffer it uses: calls on
+ * other handles neither see nor pay for it.  streams 1..32767 (the iris stage has 2 * streams items, one per grid row of a launch).
+ * Every stream starts lost. */
+int mi_tracker_create(int fd_kind, const char *model_dir, int device, int streams, mi_tracker **out);
+int mi_tracker_create_from_bytes(int fd_kind, const uint8_t *fd_tflite, size_t fd_nbytes, const uint8_t *fl_tflite, size_t fl_nbytes,
+                                 const uint8_t *iris_tflite, size_t iris_nbytes, int device, int streams, mi_tracker **out);
+void mi_tracker_free(mi_tracker *t);
+/* mi_pipeline_set_option on the tracker's three networks (e.g. "test_poison").  One key is the tracker's own, a measurement aid:
+ * "track_launches_only" = 1 makes every later step queue its three own launches (plan, select, update) alone, on what the last full step
+ * left in the handle's buffers; tools/track_probe.py times the launches that way.  Such a step is MI_EINVAL, before anything is queued,
+ * unless the handle's last full step had the same max_detect, width and height.  Its outputs and the state it leaves mean nothing, so
+ * setting the key back to 0 drops the state as mi_tracker_reset(t, -1) does (and synchronises). */
+int mi_tracker_set_option(mi_tracker *t, const char *key, int value);
+/* One step: `frames` holds `streams` equally sized RGB frames (as mi_pipeline_run's), frame s the next picture of stream s.
+ *   1. plan: det_stream / n_detect from the state (one launch)
+ *   2. the detector on exactly max_detect (1..streams) items: item j reads frame det_stream[j], an unused slot gets a zero tensor and its
+ *      answer is ignored; top-1 detection and its face_detection_to_roi
+ *   3. per stream: tracked -> the state's ROI, source 2; else a slot whose detector count is > 0 and whose ROI is valid -> that ROI,
+ *      source 1; else source 0
+ *   4. face mesh and both eyes of every stream with source != 0, as mi_pipeline_run
+ *   5. where present[s] holds and the tracked ROI of its landmarks is valid that ROI becomes the state and tracked = 1; else tracked = 0
+ * Outputs (all follow `mem`; streams without a result hold zeros):
+ *   faces       [streams] the detection a stream was acquired from (zeros unless source = 1)
+ *   face_counts [streams] the detector's count for a stream that held a slot, else 0        source [streams]
+ *   rois        [streams] the mi_rect the mesh ran on (zeros for source 0)
+ *   landmarks   f32 [streams][468][3]      present [streams]      eyes f32 [streams][2][76][3]
+ *   det_stream  [max_detect]               n_detect [2]
+ * The first seven lie as mi_pipeline_run's, so mi_render_faces takes them.  COST: the detector always runs on max_detect items, the mesh on
+ * `streams` and the iris network on 2 * streams: launch shapes depend on streams and max_detect alone, so with MI_MEM_DEVICE and a
+ * caller's stream the step does not synchronise but for the one-off upload when (streams, width, height, max_detect) changes.  Always the
+ * batched plan, never a single-launch plan.  A handle's steps are ORDERED: each reads the state the previous one wrote, so steps of one
+ * handle on two streams must be ordered by the caller.  MI_EINVAL before anything is queued for a null pointer, max_detect outside
+ * 1..streams or a frame geometry the other entries refuse; the state is then untouched.  MI_ERANGE (host memory only, where the counts are
+ * read back: a letterbox scale the reference asserts on, as mi_pipeline_run's) is found AFTER the step has run: the outputs are written,
+ * the state is the step's and the plan's start has advanced, so the next step goes on from there; mi_tracker_reset starts over. */
+int mi_tracker_step(mi_tracker *t, const uint8_t *frames, int width, int height, int stride, int max_detect, mi_detection *faces,
+                    int *face_counts, int *source, mi_rect *rois, float *landmarks, int *present, float *eyes, int *det_stream,
+                    int *n_detect, int mem, void *stream);
+/* Drops the state of stream `stream_index` (it is lost: the detector looks for it again); -1: of every stream, and the plan starts at
+ * stream 0 again.  Synchronises. */
+int mi_tracker_reset(mi_tracker *t, int stream_index);
+/* The state, host memory, synchronising: rois [streams] (zeros for a lost stream), tracked [streams].  set_state writes streams
+ * first .. first + n - 1 from rois [n] and tracked [n]. */
+int mi_tracker_get_state(mi_tracker *t, mi_rect *rois, int *tracked);
+int mi_tracker_set_state(mi_tracker *t, int first, int n, const mi_rect *rois, const int *tracked);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * L1 — FaceEmbeddings (face_embeddings.rs:22-109) with l2_norm / similarity_score (utils.rs:30-50)
  *
  * The MODEL IS THE CALLER'S: the reference does not ship face_embeddings.tflite (its README tells users to download one), so none is

@@ -392,6 +392,103 @@ class Pipeline {
     mi_pipeline* h_ = nullptr;
 };
 
+// Landmark-to-ROI face tracking for video streams (mi_tracker_*), results in host memory.  NOT the reference's behaviour (it has no video
+// loop): MediaPipe's — the ROI of a stream's next frame comes from the landmarks of its last one, the detector runs only for streams that
+// have no face yet or have lost it.  include/mi_face.h states the two rules.
+struct TrackRoi {
+    mi_rect roi{};
+    bool valid = false;
+};
+// mi_track_roi_from_landmarks (host only, no GPU): landmarks f32 [468][3], normalised to a frame of width x height
+inline TrackRoi track_roi_from_landmarks(const float* landmarks, int width, int height) {
+    TrackRoi o;
+    int valid = 0;
+    detail::check(mi_track_roi_from_landmarks(landmarks, width, height, &o.roi, &valid));
+    o.valid = valid != 0;
+    return o;
+}
+struct TrackDetectLayout {
+    std::vector<int> det_stream;   // [max_detect], -1 in unused slots
+    int used = 0, waiting = 0;     // slots used; lost streams left without a slot
+};
+// mi_track_detect_layout (host only, no GPU)
+inline TrackDetectLayout track_detect_layout(const std::vector<int>& tracked, int max_detect, int start = 0) {
+    TrackDetectLayout o;
+    // (the C side refuses max_detect outside 1..streams before it writes, so this allocation stops there too)
+    o.det_stream.resize(static_cast<std::size_t>(std::min<long long>(std::max(max_detect, 0), static_cast<long long>(tracked.size()))));
+    int n[2] = {0, 0};
+    detail::check(mi_track_detect_layout(tracked.data(), static_cast<int>(tracked.size()), max_detect, start, o.det_stream.data(), n));
+    o.used = n[0];
+    o.waiting = n[1];
+    return o;
+}
+struct TrackStep {                 // mi_tracker_step: one entry per stream, zeros where a stream has no result
+    std::vector<mi_detection> faces;   // [streams] the detection a stream was acquired from (source 1)
+    std::vector<int> face_counts;      // [streams]
+    std::vector<int> source;           // [streams] 2: the state's ROI, 1: the detector's, 0: none
+    std::vector<mi_rect> rois;         // [streams] the ROI the mesh ran on
+    std::vector<float> landmarks;      // [streams][468][3]
+    std::vector<int> present;          // [streams]
+    std::vector<float> eyes;           // [streams][2][76][3]
+    std::vector<int> det_stream;       // [max_detect]
+    int used = 0, waiting = 0;
+};
+struct TrackState {
+    std::vector<mi_rect> rois;         // [streams], zeros for a lost stream
+    std::vector<int> tracked;          // [streams]
+};
+class Tracker {
+   public:
+    Tracker(FaceDetectionModel model_type, int streams, std::optional<std::string> model_dir = std::nullopt, int device = 0) : streams_(streams) {
+        detail::check(mi_tracker_create(static_cast<int>(model_type), model_dir ? model_dir->c_str() : nullptr, device, streams, &h_));
+    }
+    ~Tracker() { mi_tracker_free(h_); }
+    Tracker(const Tracker&) = delete;
+    Tracker& operator=(const Tracker&) = delete;
+
+    int streams() const { return streams_; }
+    void set_option(const std::string& key, int value) { detail::check(mi_tracker_set_option(h_, key.c_str(), value)); }
+    // frames: one RGB frame per stream, frame s the next picture of stream s; the detector runs on exactly max_detect (0: streams) items.
+    // A handle's steps are ordered: each reads the state the previous one wrote.
+    TrackStep step(const std::uint8_t* frames, int width, int height, int stride, int max_detect = 0) {
+        if (max_detect <= 0) max_detect = streams_;
+        if (max_detect > streams_) throw std::invalid_argument("step: max_detect 1..streams (0: streams)");
+        const std::size_t S = static_cast<std::size_t>(streams_);
+        TrackStep r;
+        r.faces.resize(S);
+        r.face_counts.resize(S);
+        r.source.resize(S);
+        r.rois.resize(S);
+        r.landmarks.resize(S * 3 * MI_NUM_FACE_LANDMARKS);
+        r.present.resize(S);
+        r.eyes.resize(S * 2 * 3 * (MI_NUM_EYE_LANDMARKS + MI_NUM_IRIS_LANDMARKS));
+        r.det_stream.resize(static_cast<std::size_t>(max_detect));
+        int n[2] = {0, 0};
+        detail::check(mi_tracker_step(h_, frames, width, height, stride, max_detect, r.faces.data(), r.face_counts.data(), r.source.data(),
+                                      r.rois.data(), r.landmarks.data(), r.present.data(), r.eyes.data(), r.det_stream.data(), n, MI_MEM_HOST,
+                                      nullptr));
+        r.used = n[0];
+        r.waiting = n[1];
+        return r;
+    }
+    void reset(int stream_index = -1) { detail::check(mi_tracker_reset(h_, stream_index)); }
+    TrackState state() const {
+        TrackState s;
+        s.rois.resize(static_cast<std::size_t>(streams_));
+        s.tracked.resize(static_cast<std::size_t>(streams_));
+        detail::check(mi_tracker_get_state(h_, s.rois.data(), s.tracked.data()));
+        return s;
+    }
+    void set_state(int first, const std::vector<mi_rect>& rois, const std::vector<int>& tracked) {
+        if (rois.size() != tracked.size()) throw std::invalid_argument("set_state: one ROI and one flag per stream written");
+        detail::check(mi_tracker_set_state(h_, first, static_cast<int>(tracked.size()), rois.data(), tracked.data()));
+    }
+
+   private:
+    mi_tracker* h_ = nullptr;
+    int streams_ = 0;
+};
+
 // FaceEmbeddings (face_embeddings.rs:22-109).  The model is the CALLER'S: the reference ships no face_embeddings.tflite, none is shipped here,
 // and the reference's own model has never been run on this engine; any graph of the operators the engine lowers that maps [1,112,112,3] to
 // one output of D values per frame loads.  Those include the family of a ResNet-style (ArcFace) float graph: dense 3x3 CONV_2D (on the matrix

@@ -14,4 +14,5 @@ from .api import (  # noqa: F401
     FE_CHIP_SIZE, FaceEmbeddings, face_chip_rect, l2_norm, similarity_score, similarity_matrix,
     ALIGN_SOURCES, RECT_DTYPE, face_align_points, face_align_roi, face_align_template,
     TOPK_MAX_K, Gallery, topk_select,
+    Tracker, track_detect_layout, track_roi_from_landmarks,
 )

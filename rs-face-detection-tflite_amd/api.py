@@ -40,6 +40,8 @@ EXPORTS = [
     "mi_iris_infer_image",
     "mi_pipeline_create", "mi_pipeline_create_from_bytes", "mi_pipeline_model", "mi_pipeline_free", "mi_pipeline_set_option", "mi_pipeline_run",
     "mi_pipeline_run_faces", "mi_face_items_layout",
+    "mi_tracker_create", "mi_tracker_create_from_bytes", "mi_tracker_free", "mi_tracker_set_option", "mi_tracker_step", "mi_tracker_reset",
+    "mi_tracker_get_state", "mi_tracker_set_state", "mi_track_roi_from_landmarks", "mi_track_detect_layout",
     "mi_bbox_to_roi", "mi_bbox_from_landmarks", "mi_face_detection_to_roi", "mi_iris_roi_from_face_landmarks", "mi_update_face_landmarks_with_iris_results", "mi_image_to_tensor", "mi_jpeg_info", "mi_jpeg_decode_rgb",
     "mi_render_annotations", "mi_render_faces", "mi_render_face_items",
     "mi_fe_create", "mi_fe_create_from_bytes", "mi_fe_free", "mi_fe_model", "mi_fe_features", "mi_face_chip_rect", "mi_fe_infer_image",
@@ -312,6 +314,17 @@ def lib():
     L.mi_pipeline_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
     L.mi_pipeline_run_faces.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
     L.mi_face_items_layout.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.mi_tracker_create.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
+    L.mi_tracker_create_from_bytes.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(vp)]
+    L.mi_tracker_free.argtypes = [vp]
+    L.mi_tracker_free.restype = None
+    L.mi_tracker_set_option.argtypes = [vp, C.c_char_p, C.c_int]
+    L.mi_tracker_step.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
+    L.mi_tracker_reset.argtypes = [vp, C.c_int]
+    L.mi_tracker_get_state.argtypes = [vp, vp, vp]
+    L.mi_tracker_set_state.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.mi_track_roi_from_landmarks.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Rect), ip]
+    L.mi_track_detect_layout.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mi_face_detection_to_roi.argtypes = [C.POINTER(CDetection), C.c_int, C.c_int, C.POINTER(Rect)]
     L.mi_iris_roi_from_face_landmarks.argtypes = [C.POINTER(CLandmark), C.c_int, C.c_int, C.POINTER(Rect), C.POINTER(Rect)]
     L.mi_update_face_landmarks_with_iris_results.argtypes = [C.POINTER(CLandmark)] * 4
@@ -1044,6 +1057,116 @@ def face_items_layout(face_counts, max_faces, max_items):
     _check(lib().mi_face_items_layout(C.c_void_p(counts.ctypes.data), int(counts.size), int(max_faces), M, C.c_void_p(item_frame.ctypes.data),
                                       C.c_void_p(item_face.ctypes.data), C.c_void_p(n.ctypes.data)))
     return item_frame, item_face, int(n[0]), int(n[1])
+
+
+def track_roi_from_landmarks(landmarks, image_size):
+    """mi_track_roi_from_landmarks (host only, no GPU): the ROI Tracker derives for the next frame from one face's landmarks [468,3] (float32,
+    normalised to the frame) on a frame of image_size = (width, height).  NOT the reference's behaviour: MediaPipe's landmarks-to-ROI step.
+    -> (Rect, valid)."""
+    lm = np.ascontiguousarray(landmarks, np.float32)
+    if lm.shape != (468, 3):
+        raise ValueError("landmarks must be [468, 3]")
+    r, ok = Rect(), C.c_int(0)
+    _check(lib().mi_track_roi_from_landmarks(C.c_void_p(lm.ctypes.data), int(image_size[0]), int(image_size[1]), C.byref(r), C.byref(ok)))
+    return r, bool(ok.value)
+
+
+def track_detect_layout(tracked, max_detect, start=0):
+    """mi_track_detect_layout (host only, no GPU): which lost streams get the detector slots of a Tracker step.
+    -> (det_stream int32 [max_detect] (-1 in unused slots), slots used, lost streams left without a slot)."""
+    tr = np.ascontiguousarray(tracked, np.int32).reshape(-1)
+    D = int(max_detect)
+    det, n = np.zeros((max(min(D, 1 << 20), 1),), np.int32), np.zeros((2,), np.int32)
+    _check(lib().mi_track_detect_layout(C.c_void_p(tr.ctypes.data), int(tr.size), D, int(start), C.c_void_p(det.ctypes.data), C.c_void_p(n.ctypes.data)))
+    return det, int(n[0]), int(n[1])
+
+
+class Tracker:
+    """mi_tracker: landmark-to-ROI face tracking for `streams` video streams, one face per stream.  The ROI of a stream's next frame comes
+    from the landmarks of its last one; the detector runs only for streams that have no face yet or have lost it, on `max_detect` items per
+    step.  NOT the reference's behaviour (it has no video loop): MediaPipe's, composed from the reference's own functions."""
+
+    def __init__(self, model=FaceDetectionModel.BackCamera, streams=1, model_dir=None, device=0, model_bytes=None):
+        self.L = lib()
+        self.h = C.c_void_p()
+        self.device = device
+        self.streams = int(streams)
+        d = model_dir if model_dir is not None else DEFAULT_MODEL_DIR
+        if model_bytes is not None:   # (detector, face_landmark, iris_landmark) .tflite blobs
+            fd_b, fl_b, ir_b = model_bytes
+            _check(self.L.mi_tracker_create_from_bytes(int(model), fd_b, len(fd_b), fl_b, len(fl_b), ir_b, len(ir_b), device, self.streams, C.byref(self.h)))
+        else:
+            _check(self.L.mi_tracker_create(int(model), os.fsencode(d), device, self.streams, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mi_tracker_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_option(self, key, value):
+        _check(self.L.mi_tracker_set_option(self.h, key.encode(), int(value)))
+
+    def step(self, frames, max_detect=None, stream=None):
+        """frames: uint8 [streams,H,W,3] RGB (numpy, or a torch CUDA tensor), frame s the next picture of stream s.  max_detect: detector
+        items of this step (1..streams; None: streams).  Returns dict(faces [S,17], face_counts [S], source [S] (2 tracked, 1 detected,
+        0 none), rois (a numpy array of RECT_DTYPE [S] for host frames; a uint8 tensor [S,48], mi_rect as it lies in memory, for device frames),
+        landmarks [S,468,3], present [S], eyes [S,2,76,3], det_stream [max_detect], n_detect [2])."""
+        if len(frames.shape) != 4 or frames.shape[3] != 3:
+            raise ValueError("frames must be [S,H,W,3]")
+        S, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        D = S if max_detect is None else int(max_detect)
+        if S != self.streams:
+            raise MiError(-1, "frames must hold one frame per stream (%d), got %d" % (self.streams, S))   # MI_EINVAL
+        if not 1 <= D <= S:   # (before the outputs are sized by it; the C entry checks again)
+            raise MiError(-1, "max_detect must be 1..streams")
+        shapes = dict(faces=((S, 17), "float32"), face_counts=((S,), "int32"), source=((S,), "int32"), rois=((S, 48), "uint8"),
+                      landmarks=((S, 468, 3), "float32"), present=((S,), "int32"), eyes=((S, 2, 76, 3), "float32"), det_stream=((D,), "int32"),
+                      n_detect=((2,), "int32"))
+        if _is_torch(frames) and frames.is_cuda:
+            import torch
+            mem = MI_MEM_DEVICE
+            out = {k: torch.zeros(sh, dtype=getattr(torch, dt), device=frames.device) for k, (sh, dt) in shapes.items()}
+            p = C.c_void_p(frames.data_ptr())
+            stride = int(frames.stride(1))
+            if frames.stride(2) != 3 or frames.stride(3) != 1 or frames.stride(0) != stride * H:
+                raise ValueError("frames must be [S,H,W,3] with dense pixels and frames stride*H bytes apart")
+            _device_ready(frames, self.device, None, "uint8")
+        else:
+            frames = np.ascontiguousarray(frames, np.uint8)
+            mem = MI_MEM_HOST
+            out = {k: np.zeros(sh, getattr(np, dt)) for k, (sh, dt) in shapes.items()}
+            p = C.c_void_p(frames.ctypes.data)
+            stride = int(frames.strides[1])
+        _check(self.L.mi_tracker_step(self.h, p, W, H, stride, D, *[_ptr(out[k])[0] for k in ("faces", "face_counts", "source", "rois", "landmarks",
+                                                                                               "present", "eyes", "det_stream", "n_detect")],
+                                      mem, C.c_void_p(stream or 0)))
+        if mem == MI_MEM_HOST:
+            out["rois"] = out["rois"].view(RECT_DTYPE).reshape(S)
+        return out
+
+    def reset(self, stream_index=-1):
+        """Drops the state of one stream, or of all (-1; the detect plan then starts at stream 0 again)."""
+        _check(self.L.mi_tracker_reset(self.h, int(stream_index)))
+
+    def state(self):
+        """-> dict(rois: numpy records of RECT_DTYPE [streams] (zeros for a lost stream), tracked int32 [streams]).  Synchronises."""
+        rois, tracked = np.zeros((self.streams,), RECT_DTYPE), np.zeros((self.streams,), np.int32)
+        _check(self.L.mi_tracker_get_state(self.h, C.c_void_p(rois.ctypes.data), C.c_void_p(tracked.ctypes.data)))
+        return dict(rois=rois, tracked=tracked)
+
+    def set_state(self, rois, tracked, first=0):
+        """Writes the state of streams first .. first + n - 1: rois (records of RECT_DTYPE [n]), tracked [n].  Synchronises."""
+        rois = np.ascontiguousarray(rois, RECT_DTYPE).reshape(-1)
+        tracked = np.ascontiguousarray(tracked, np.int32).reshape(-1)
+        if rois.size != tracked.size:
+            raise ValueError("rois and tracked must have one entry per stream written")
+        _check(self.L.mi_tracker_set_state(self.h, int(first), int(tracked.size), C.c_void_p(rois.ctypes.data), C.c_void_p(tracked.ctypes.data)))
 
 
 def _picture(x, channels, what):

@@ -25,7 +25,7 @@
 #include "topk.hpp"
 
 // Layout: capi_core.cpp (last error, L0 model, host helpers), capi_fd.cpp (detector + its JPEG stream), capi_landmarks.cpp (mesh, iris),
-// capi_pipeline.cpp, capi_render.cpp, capi_embed.cpp (embeddings, similarity, top-k, gallery), capi_dist.cpp (RCCL broadcast, stream probing).
+// capi_pipeline.cpp, capi_tracker.cpp (mi_tracker around a private pipeline: capi_pipeline.hpp), capi_render.cpp, capi_embed.cpp (embeddings, similarity, top-k, gallery), capi_dist.cpp (RCCL broadcast, stream probing).
 // Everything here that is not a handle struct of the C header lives in mi::capi, which is hidden: libmiface.so exports the mi_* entries only.
 #define MI_CAPI_BEGIN namespace mi { namespace capi __attribute__((visibility("hidden"))) {
 #define MI_CAPI_END } }

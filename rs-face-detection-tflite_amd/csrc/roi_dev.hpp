@@ -8,8 +8,9 @@
 
 namespace mi {
 
-// bbox_to_roi + select_roi_size(SquareLong) (transform.rs:44-109), f64 like the reference
-__device__ inline bool bbox_to_roi_dev(const double bbox[4], int image_w, int image_h, const double kp[4], double scale, RectD* out) {
+// bbox_to_roi + select_roi_size(SquareLong) (transform.rs:44-109), f64 like the reference (host-callable as well: track.hpp states the
+// tracker's ROI rule once for both sides)
+__host__ __device__ inline bool bbox_to_roi_dev(const double bbox[4], int image_w, int image_h, const double kp[4], double scale, RectD* out) {
     const double xmin = bbox[0], ymin = bbox[1], xmax = bbox[2], ymax = bbox[3];
     if (!(xmin >= -1.0 && xmax < 2.0 && ymin >= -1.0)) return false;  // BBox::normalized (types.rs:133-135)
     const double iw = image_w, ih = image_h;
