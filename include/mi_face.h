@@ -615,6 +615,9 @@ int mi_iris_roi_from_face_landmarks(const mi_landmark *landmarks468, int image_w
  * entropy decoding on the host, dequantisation / IDCT / chroma upsampling / colour conversion on the GPU (the arithmetic
  * of libjpeg-turbo's default decoder, bit for bit).  Baseline and extended-sequential Huffman JPEG, 8 bit, grey or YCbCr with
  * h1v1 / h2v1 / h2v2 sampling; progressive (SOF2) streams included; anything else (arithmetic coding, 12-bit, CMYK, other containers) is MI_EINVAL with a message.
+ * Also MI_EINVAL, because imdecode gives other pixels than a plain decode would: "RGB-coded JPEG" (libjpeg's rule: no JFIF APP0 and an Adobe APP14
+ * with transform 0, or component ids R G B) and "EXIF orientation N" for N = 2..8 (imdecode turns the picture); mi_jpeg_info refuses these too when
+ * the segment precedes the frame header.
  * rgb = [height][width][3] u8, at least cap_bytes >= 3*width*height (ask mi_jpeg_info first); follows `mem`. */
 int mi_jpeg_info(const uint8_t *bytes, size_t nbytes, int *width, int *height);
 int mi_jpeg_decode_rgb(int device, const uint8_t *bytes, size_t nbytes, uint8_t *rgb, size_t cap_bytes, int *width,

@@ -70,9 +70,14 @@ static int get_bit(bitreader *br) {
             br->fake = 0;
             byte = *br->p++;
             if (byte == 0xFF) {
-                int nx = br->p < br->end ? *br->p : 0xD9;
-                if (nx == 0x00) br->p++;             /* stuffed zero */
-                else { br->marker = nx; byte = 0; br->p--; br->fake = 1; } /* marker: feed zeros from here on (libjpeg does the same) */
+                /* T.81 B.1.1.2: a marker may be preceded by any number of fill bytes FF; jdhuff.c discards the run before it looks at
+                 * the byte behind it, which is 00 for a data byte FF and a marker's code otherwise */
+                size_t fills = 0;
+                while (br->p + fills < br->end && br->p[fills] == 0xFF) fills++;
+                int nx = br->p + fills < br->end ? br->p[fills] : 0xD9;
+                if (nx == 0x00) br->p += fills + 1;   /* stuffed zero */
+                else { br->marker = nx; byte = 0; br->p += fills; br->p--; br->fake = 1; } /* marker: feed zeros from here on (libjpeg does the
+                                                                                             * same); p stays on the FF in front of its code */
             }
         }
         br->bitbuf = (uint32_t)byte;
@@ -94,6 +99,15 @@ static int decode_symbol(bitreader *br, const hufftab *h) {
         if (h->maxcode[l] >= 0 && code <= h->maxcode[l] && code >= h->mincode[l]) return h->symbols[h->valptr[l] + code - h->mincode[l]];
     }
     return 0; /* corrupt data: libjpeg warns and uses 0 */
+}
+/* RSTn: byte-align and step over the marker, which the bit reader has met already (p is on its FF) or not looked at yet (then fill
+ * bytes may still lie in front of it). */
+static void restart_marker(bitreader *br) {
+    br->bits = 0;
+    if (br->marker == 0)
+        while (br->p + 2 < br->end && br->p[0] == 0xFF && br->p[1] == 0xFF) br->p++;
+    if (br->marker >= 0xD0 && br->marker <= 0xD7) { br->p += 2; br->marker = 0; br->insufficient = 0; }
+    else if (br->marker == 0 && br->p + 1 < br->end && br->p[0] == 0xFF && br->p[1] >= 0xD0 && br->p[1] <= 0xD7) { br->p += 2; br->insufficient = 0; }
 }
 static int extend(int v, int t) { return t == 0 ? 0 : (v < (1 << (t - 1)) ? v - (1 << t) + 1 : v); } /* F.2.2.1 */
 
@@ -157,6 +171,7 @@ static int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 int orc_jpeg_info(const uint8_t *data, size_t n, int *width, int *height) {
     for (size_t i = 2; i + 8 < n;) {
         if (data[i] != 0xFF) return -1;
+        if (data[i + 1] == 0xFF) { i++; continue; } /* fill byte */
         int m = data[i + 1];
         size_t len = ((size_t)data[i + 2] << 8) | data[i + 3];
         if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
@@ -223,12 +238,6 @@ static void reconstruct(component *comp, int ncomp, int W, int H, int hmax, int 
  * _AC_refine).  One scan adds a band [Ss, Se] of coefficients, or one more bit (Al) of a band, of one component (AC) or of several
  * interleaved ones (DC).  eobrun: blocks still covered by an end-of-band run. */
 typedef struct { int nc, ci[3], Ss, Se, Ah, Al; } scan_hdr;
-
-static void restart_marker(bitreader *br) {
-    br->bits = 0;
-    if (br->marker >= 0xD0 && br->marker <= 0xD7) { br->p += 2; br->marker = 0; br->insufficient = 0; }
-    else if (br->marker == 0 && br->p + 1 < br->end && br->p[0] == 0xFF && br->p[1] >= 0xD0 && br->p[1] <= 0xD7) { br->p += 2; br->insufficient = 0; }
-}
 
 static void prog_block(bitreader *br, const scan_hdr *sh, component *cp, const hufftab *dct, const hufftab *act, int16_t *blk, int *eobrun) {
     const int Al = sh->Al;
@@ -331,7 +340,43 @@ static size_t prog_scan(const uint8_t *data, size_t n, size_t ecs, const scan_hd
     return pos;
 }
 
-/* imdecode(IMREAD_COLOR) + BGR2RGB (utils.rs:8-21): rgb = [H][W][3]. Returns 0, or a negative code (-2 = unsupported). */
+/* The Orientation tag (0x0112, SHORT, count 1) of IFD0 in the TIFF block of an Exif APP1 segment; 0 = absent or malformed.
+ * imdecode(IMREAD_COLOR) turns the picture by it (OpenCV's documentation of IMREAD_IGNORE_ORIENTATION; not run against OpenCV). */
+static unsigned tiff_get(const uint8_t *t, size_t at, int bytes, int little) {
+    unsigned v = 0;
+    for (int k = 0; k < bytes; k++) v |= (unsigned)t[at + k] << 8 * (little ? k : bytes - 1 - k);
+    return v;
+}
+static int exif_orientation(const uint8_t *tiff, size_t n) {
+    if (n < 8) return 0;
+    int little;
+    if (tiff[0] == 0x49 && tiff[1] == 0x49) little = 1;
+    else if (tiff[0] == 0x4D && tiff[1] == 0x4D) little = 0;
+    else return 0;
+    if (tiff_get(tiff, 2, 2, little) != 42) return 0;
+    size_t ifd = tiff_get(tiff, 4, 4, little);
+    if (ifd + 2 > n) return 0;
+    size_t entries = tiff_get(tiff, ifd, 2, little);
+    for (size_t e = 0; e < entries; e++) {
+        size_t at = ifd + 2 + 12 * e;
+        if (at + 12 > n) break;
+        if (tiff_get(tiff, at, 2, little) != 0x0112) continue;
+        if (tiff_get(tiff, at + 2, 2, little) != 3 || tiff_get(tiff, at + 4, 4, little) != 1) return 0;
+        return (int)tiff_get(tiff, at + 8, 2, little);
+    }
+    return 0;
+}
+
+/* libjpeg's guess of a three-component file's colour space (jdapimin.c default_decompress_parms) from what came before the first scan:
+ * a JFIF APP0 -> YCbCr; else an Adobe APP14 -> its transform byte (0 = RGB); else the component ids 'R' 'G' 'B' -> RGB; else YCbCr. */
+static int coded_as_rgb(int jfif, int adobe, int transform, const component *comp) {
+    if (jfif) return 0;
+    if (adobe) return transform == 0;
+    return comp[0].id == 82 && comp[1].id == 71 && comp[2].id == 66;
+}
+
+/* imdecode(IMREAD_COLOR) + BGR2RGB (utils.rs:8-21): rgb = [H][W][3]. Returns 0, or a negative code (-2 = unsupported,
+ * -3 = incomplete progressive stream, -4 = RGB-coded: libjpeg skips the colour conversion, -5 = EXIF orientation 2..8: imdecode turns the picture). */
 int orc_jpeg_decode_rgb(const uint8_t *data, size_t n, uint8_t *rgb, int cap_w, int cap_h) {
     if (n < 4 || data[0] != 0xFF || data[1] != 0xD8) return -1;
     uint16_t qt[4][64];
@@ -343,6 +388,7 @@ int orc_jpeg_decode_rgb(const uint8_t *data, size_t n, uint8_t *rgb, int cap_w, 
     int ncomp = 0, W = 0, H = 0, hmax = 1, vmax = 1, restart = 0, rc = -1, progressive = 0, scans = 0;
     int coef_bits[3][64];
     memset(coef_bits, 0xff, sizeof coef_bits); /* -1: never sent */
+    int jfif = 0, adobe = 0, transform = 0, exif = 0, first_scan = 1; /* application segments in front of the first scan */
     size_t i = 2;
     while (i + 4 <= n) {
         if (data[i] != 0xFF) { i++; continue; }
@@ -352,7 +398,16 @@ int orc_jpeg_decode_rgb(const uint8_t *data, size_t n, uint8_t *rgb, int cap_w, 
         size_t len = ((size_t)data[i + 2] << 8) | data[i + 3];
         const uint8_t *seg = data + i + 4;
         if (i + 2 + len > n) goto done;
-        if (m == 0xDB) { /* DQT */
+        if (m >= 0xE0 && m <= 0xEF && first_scan && len >= 2) {
+            size_t body = len - 2;
+            if (m == 0xE0 && body >= 14 && memcmp(seg, "JFIF", 5) == 0) jfif = 1;
+            if (m == 0xEE && body >= 12 && memcmp(seg, "Adobe", 5) == 0) { adobe = 1; transform = seg[11]; }
+            if (m == 0xE1 && body >= 6 && memcmp(seg, "Exif\0", 6) == 0 && !exif) { /* the first Exif segment counts */
+                exif = 1;
+                int o = exif_orientation(seg + 6, body - 6);
+                if (o >= 2 && o <= 8) { rc = -5; goto done; }
+            }
+        } else if (m == 0xDB) { /* DQT */
             for (size_t k = 0; k + 1 < len - 2;) {
                 int pq = seg[k] >> 4, tq = seg[k] & 15;
                 k++;
@@ -414,6 +469,8 @@ int orc_jpeg_decode_rgb(const uint8_t *data, size_t n, uint8_t *rgb, int cap_w, 
             scan_hdr sh;
             sh.nc = seg[0];
             if (ncomp == 0 || sh.nc < 1 || sh.nc > ncomp || len < (size_t)(6 + 2 * sh.nc)) goto done;
+            if (first_scan && ncomp == 3 && coded_as_rgb(jfif, adobe, transform, comp)) { rc = -4; goto done; }
+            first_scan = 0;
             for (int s2 = 0; s2 < sh.nc; s2++) {
                 int cid = seg[1 + 2 * s2], c = 0;
                 while (c < ncomp && comp[c].id != cid) c++;
@@ -432,6 +489,7 @@ int orc_jpeg_decode_rgb(const uint8_t *data, size_t n, uint8_t *rgb, int cap_w, 
             continue;
         } else if (m == 0xDA) { /* SOS: one interleaved scan holding every component */
             if (ncomp == 0 || seg[0] != ncomp) { rc = -2; goto done; }
+            if (ncomp == 3 && coded_as_rgb(jfif, adobe, transform, comp)) { rc = -4; goto done; }
             for (int s = 0; s < ncomp; s++) {
                 int cid = seg[1 + 2 * s], c = 0;
                 while (c < ncomp && comp[c].id != cid) c++;
@@ -456,9 +514,7 @@ int orc_jpeg_decode_rgb(const uint8_t *data, size_t n, uint8_t *rgb, int cap_w, 
             for (int my = 0; my < mcuy; my++)
                 for (int mx = 0; mx < mcux; mx++) {
                     if (restart && mcus > 0 && mcus % restart == 0) { /* RSTn: byte-align, skip the marker, reset the predictors */
-                        br.bits = 0;
-                        if (br.marker >= 0xD0 && br.marker <= 0xD7) { br.p += 2; br.marker = 0; br.insufficient = 0; } /* already met by the bit reader */
-                        else if (br.marker == 0 && br.p + 1 < br.end && br.p[0] == 0xFF && br.p[1] >= 0xD0 && br.p[1] <= 0xD7) { br.p += 2; br.insufficient = 0; }
+                        restart_marker(&br);
                         for (int c = 0; c < ncomp; c++) comp[c].pred = 0;
                     }
                     mcus++;

@@ -248,5 +248,6 @@ def jpeg_decode_rgb(data: bytes):
     out = np.zeros((h.value, w.value, 3), np.uint8)
     rc = L.orc_jpeg_decode_rgb(data, len(data), out.ctypes.data, w.value, h.value)
     if rc != 0:
-        raise ValueError("jpeg decode failed (%d)" % rc)
+        why = {-3: ": incomplete progressive stream", -4: ": RGB-coded JPEG", -5: ": EXIF orientation other than 1"}.get(rc, "")
+        raise ValueError("jpeg decode failed (%d)%s" % (rc, why))
     return out

@@ -59,9 +59,12 @@ struct Bits {
                 byte = *p++;
                 real += 8;
                 if (byte == 0xFF) {
-                    unsigned nx = p < end ? *p : 0xD9u;
-                    if (nx == 0) p++;
-                    else { hit_marker = true; byte = 0; p--; real -= 8; }
+                    // jdhuff.c jpeg_fill_bit_buffer: "Loop here to discard any padding FF's on terminating marker", then a zero is
+                    // the stuffed byte of a data FF, anything else a marker.  p is left on the last FF, so that p[1] is the marker's code.
+                    const uint8_t* q = p;
+                    while (q < end && *q == 0xFF) q++;
+                    if (q < end && *q == 0) p = q + 1;
+                    else { hit_marker = true; byte = 0; p = q - 1; real -= 8; }
                 }
             }
             buf |= static_cast<uint64_t>(byte) << (56 - n);
@@ -98,8 +101,12 @@ struct Bits {
     }
     void restart() {  // byte-align and step over RSTn; data found again ends the run of skipped MCUs (jdhuff.c process_restart)
         n = 0; buf = 0; real = 0;
-        if (hit_marker) { if (p + 1 < end && p[1] >= 0xD0 && p[1] <= 0xD7) { p += 2; hit_marker = false; insufficient = false; } }
-        else if (p + 1 < end && p[0] == 0xFF && p[1] >= 0xD0 && p[1] <= 0xD7) { p += 2; insufficient = false; }
+        const uint8_t* q = p;  // the FF in front of the marker's code: fill() stopped there, or the reader has not looked at it yet
+        if (!hit_marker) {
+            if (q >= end || *q != 0xFF) return;
+            while (q + 1 < end && q[1] == 0xFF) q++;  // fill bytes (T.81 B.1.1.2)
+        }
+        if (q + 1 < end && q[1] >= 0xD0 && q[1] <= 0xD7) { p = q + 2; hit_marker = false; insufficient = false; }
     }
 };
 
@@ -118,6 +125,44 @@ struct Parser {
     Huff dc[4], ac[4];
     int restart_interval = 0;
     bool have_frame = false;
+    // what libjpeg / imdecode take from the application segments in front of the first scan
+    bool saw_jfif = false, saw_adobe = false, saw_exif = false, in_scans = false;
+    int adobe_transform = 0;
+
+    // jdapimin.c default_decompress_parms, three components: JFIF means YCbCr; else Adobe's transform byte decides (0 = RGB); else the
+    // component ids R, G, B mean RGB.  libjpeg then skips the colour conversion; the kernels always convert, so such a file is refused.
+    void refuse_rgb() const {
+        if (f->ncomp != 3 || saw_jfif) return;
+        const bool rgb = saw_adobe ? adobe_transform == 0 : (f->comp[0].id == 'R' && f->comp[1].id == 'G' && f->comp[2].id == 'B');
+        if (rgb) bad("RGB-coded JPEG (libjpeg skips the colour conversion, which is not implemented)");
+    }
+
+    // imdecode(IMREAD_COLOR) turns the picture by the EXIF orientation (OpenCV's documentation; not run against OpenCV): IFD0 of the first
+    // Exif segment, tag 0x0112, SHORT, count 1.  Values 2..8 are refused; absent, 1, out of range or malformed: the picture is decoded.
+    static int exif_orientation(const uint8_t* t, size_t tn) {  // t: the TIFF header behind "Exif\0\0"
+        if (tn < 8) return 0;
+        const bool le = t[0] == 'I' && t[1] == 'I';
+        if (!le && !(t[0] == 'M' && t[1] == 'M')) return 0;
+        auto u16 = [&](size_t o) { return le ? unsigned(t[o]) | unsigned(t[o + 1]) << 8 : unsigned(t[o]) << 8 | unsigned(t[o + 1]); };
+        auto u32 = [&](size_t o) { return le ? u16(o) | u16(o + 2) << 16 : u16(o) << 16 | u16(o + 2); };
+        if (u16(2) != 42) return 0;
+        const size_t ifd = u32(4);
+        if (ifd > tn - 2) return 0;
+        const size_t count = u16(ifd);
+        for (size_t e = 0, o = ifd + 2; e < count && o + 12 <= tn; e++, o += 12)
+            if (u16(o) == 0x0112) return u16(o + 2) == 3 && u32(o + 4) == 1 ? static_cast<int>(u16(o + 8)) : 0;
+        return 0;
+    }
+
+    void application_segment(int m, const uint8_t* seg, size_t body) {
+        if (m == 0xE0 && body >= 14 && std::memcmp(seg, "JFIF\0", 5) == 0) saw_jfif = true;  // jdmarker.c examine_app0
+        if (m == 0xEE && body >= 12 && std::memcmp(seg, "Adobe", 5) == 0) { saw_adobe = true; adobe_transform = seg[11]; }  // examine_app14
+        if (m == 0xE1 && body >= 6 && std::memcmp(seg, "Exif\0\0", 6) == 0 && !saw_exif) {
+            saw_exif = true;
+            const int o = exif_orientation(seg + 6, body - 6);
+            if (o >= 2 && o <= 8) bad(("EXIF orientation " + std::to_string(o) + " (imdecode turns the picture, which is not implemented)").c_str());
+        }
+    }
 
     // walks the markers from `start` up to SOS; returns the offset of the entropy-coded data (0 when stop_at_frame and a frame header
     // was found, or — behind the first scan of a progressive frame, `sh` given — when EOI / the end of the data comes first)
@@ -133,7 +178,9 @@ struct Parser {
             if (len < 2 || i + 2 + len > n) bad("truncated segment");
             const uint8_t* seg = d + i + 4;
             const size_t body = len - 2;
-            if (m == 0xDB) {
+            if (m >= 0xE0 && m <= 0xEF) {
+                if (!in_scans) application_segment(m, seg, body);
+            } else if (m == 0xDB) {
                 for (size_t k = 0; k < body;) {
                     const int pq = seg[k] >> 4, tq = seg[k] & 15;
                     k++;
@@ -182,7 +229,7 @@ struct Parser {
                     if (!ok) bad("unsupported chroma sampling (h1v1, h2v1, h2v2)");
                 }
                 have_frame = true;
-                if (stop_at_frame) return 0;
+                if (stop_at_frame) { refuse_rgb(); return 0; }  // (by the segments in front of the frame header; the decode call sees them all)
             } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
                 bad("unsupported coding process (baseline / extended sequential / progressive Huffman only)");
             } else if (m == 0xDD) {
@@ -190,6 +237,7 @@ struct Parser {
                 restart_interval = (seg[0] << 8) | seg[1];
             } else if (m == 0xDA && f->progressive) {
                 if (!have_frame || !sh) bad("scan before frame header");
+                if (!in_scans) { refuse_rgb(); in_scans = true; }
                 sh->nc = body >= 1 ? seg[0] : 0;
                 if (sh->nc < 1 || sh->nc > f->ncomp || body < 4 + 2 * static_cast<size_t>(sh->nc)) bad("bad scan header");
                 for (int s = 0; s < sh->nc; s++) {
@@ -215,6 +263,7 @@ struct Parser {
                 return i + 2 + len;
             } else if (m == 0xDA) {
                 if (!have_frame) bad("scan before frame header");
+                if (!in_scans) { refuse_rgb(); in_scans = true; }
                 if (body < 1 || seg[0] != f->ncomp || body < 1 + 2 * static_cast<size_t>(f->ncomp)) bad("unsupported scan layout (one interleaved scan)");
                 for (int s = 0; s < f->ncomp; s++) {
                     int c = 0;
