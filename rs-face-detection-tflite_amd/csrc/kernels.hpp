@@ -1,4 +1,4 @@
-// kernels.hpp — launch descriptors shared between the planner (host) and the HIP kernels (kernels.hip).
+// kernels.hpp — launch descriptors shared between the planner (host) and the HIP kernels (the *_kernels.hip files), and their launchers.
 // Activations are f32 NHWC; every tensor is addressed as base + frame * frame_stride (+ pixel * C + c), so that
 // RESHAPE is a view and CONCATENATION is done by producers writing straight into the concatenated buffer.
 #pragma once
@@ -307,10 +307,31 @@ int launch_tail(const TailLaunch& a, void* stream);
 bool tail_stage_ok(int kind, int K, int S, int src_C, int Kv, int Co, bool dst_lds);
 unsigned tail_magic(int d);
 
-// ---- launchers (kernels.hip). All enqueue on `stream` and return hipError_t as int (0 = success).
+// ---- launchers, by file. All enqueue on `stream` and return hipError_t as int (0 = success).
+// kernels.hip: the general kernels, and launch_conv's choice among every convolution kernel
 int launch_conv(const ConvArgs& a, void* stream);
 const char* conv_kernel_label(const ConvArgs& a);
 bool conv_takes_u8(const ConvArgs& a);  // the specialised stem kernel: the only convolution with a u8 input form
+int launch_dw(const DwArgs& a, void* stream);
+int launch_add(const EltArgs& a, void* stream);
+int launch_act(const EltArgs& a, void* stream);
+int launch_affine(const EltArgs& a, void* stream);
+int launch_maxpool(const EltArgs& a, void* stream);
+int launch_padc(const EltArgs& a, void* stream);
+int launch_resize2x(const EltArgs& a, void* stream);
+int launch_depth_to_space(const EltArgs& a, void* stream);
+int launch_copy_strided(const EltArgs& a, void* stream);
+int launch_spin(long long ticks, int max_iters, int* sink, void* stream);   // one idle wave for `ticks` of the 100 MHz wall clock (bounded)
+// stem_kernels.hip: the first convolution (stem_mfma_applicable: one of the two MFMA forms of the 5 x 5 stem takes it; launch_stem_conv chooses by KH / Co and that)
+bool stem_applicable(const ConvArgs& a);
+bool stem_mfma_applicable(const ConvArgs& a);
+int launch_stem_conv(const ConvArgs& a, void* stream);
+// head_kernels.hip: whole-frame convolutions as a product over the batch
+int launch_head_gemm(const HeadGemmArgs& a, void* stream);
+bool head_gemm_supports(int K, int N);
+// post_kernels.hip: SSD post-processing and landmark projection
+int launch_postprocess(const PostArgs& a, void* stream);
+int launch_project(const ProjArgs& a, void* stream);
 // conv_mfma_kernels.hip: implicit-GEMM dense convolution on v_mfma_f32_32x32x2_f32.  conv_mfma_shape_ok: the graph's side of the rule (the constants
 // packer keeps a [Co][K] copy of the filter for such a node); conv_mfma_supports: this launch takes the kernel (launch_conv and conv_kernel_label ask it)
 bool conv_mfma_shape_ok(int C, int KH, int KW, int Co);
@@ -321,7 +342,6 @@ int launch_conv_mfma(const ConvArgs& a, void* stream);
 // conv_kernel_label ask it first
 bool conv_bf16_supports(const ConvArgs& a);
 int launch_conv_bf16(const ConvArgs& a, void* stream);
-int launch_dw(const DwArgs& a, void* stream);
 int launch_block(const BlockArgs& a, void* stream);
 bool block_kernel_supports(const BlockArgs& a);
 const char* block_kernel_label(const BlockArgs& a, char* buf, size_t cap);  // instantiation name as rocprofv3 prints it
@@ -464,13 +484,7 @@ bool mbneck_kernel_supports(const BneckArgs& a);
 int launch_mbneck(const BneckArgs& a, void* stream);
 int bneck_const_floats(int C, int Cm);
 int launch_bneck(const BneckArgs& a, void* stream);
-int launch_head_gemm(const HeadGemmArgs& a, void* stream);
-bool head_gemm_supports(int K, int N);
 bool chain_kernel_supports(const ChainArgs& a);
-int launch_add(const EltArgs& a, void* stream);
-int launch_act(const EltArgs& a, void* stream);
-int launch_affine(const EltArgs& a, void* stream);
-int launch_maxpool(const EltArgs& a, void* stream);
 // embed_ops_kernels.hip — the operators of pooled-head and ONNX-exported embedding graphs, each one k-ordered f32 chain per output element
 int launch_avgpool(const EltArgs& a, void* stream);      // AVERAGE_POOL_2D / MEAN over H and W: p0 = filter_h, p1 = filter_w, p2 = stride_h, p3 = stride_w (pads as launch_maxpool)
 int launch_l2norm_rows(const EltArgs& a, void* stream);  // L2_NORMALIZATION over C of the H * W rows of a frame
@@ -483,13 +497,6 @@ inline bool transpose_takes_tiled(const EltArgs& a) {
 }
 // thread-per-row form of l2norm_rows_kernel from this many rows on (below: a wave per row, lane 0 sums, every lane divides)
 constexpr long kL2NormLaneRows = 2048;
-int launch_padc(const EltArgs& a, void* stream);
-int launch_resize2x(const EltArgs& a, void* stream);
-int launch_depth_to_space(const EltArgs& a, void* stream);
-int launch_copy_strided(const EltArgs& a, void* stream);
-int launch_postprocess(const PostArgs& a, void* stream);
-int launch_project(const ProjArgs& a, void* stream);
-int launch_spin(long long ticks, int max_iters, int* sink, void* stream);   // one idle wave for `ticks` of the 100 MHz wall clock (bounded)
 
 // ---- bandnet_kernels.hip: a whole BlazeBlock network behind its first convolution as ONE launch, for the handful of frames of a
 // single-image call (face_detection.rs:205: one Mat per call).  NW workgroups per frame; every stage (one BlazeBlock or one 1x1

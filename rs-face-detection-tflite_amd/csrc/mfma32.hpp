@@ -1,6 +1,7 @@
 // mfma32.hpp — the quad-level vocabulary of the frame-resident MFMA kernels (block, dblock, bneck, chain, resident, xc, bandnet and
-// head_gemm on v_mfma_f32_32x32x2_f32, tail on 16x16x4) in the "operand layout": lane = pixel x k-half, the depthwise result of four
+// head_kernels.hip's head_gemm on v_mfma_f32_32x32x2_f32, tail on 16x16x4) in the "operand layout": lane = pixel x k-half, the depthwise result of four
 // channels is the B operand of four MFMAs, and a quad of the result D is four consecutive output channels of the lane's pixel.
+// (stem_kernels.hip and head_dot_kernel take the one-value activation act1 from here and nothing else.)
 // Nothing here is a schedule or a layout: 16-byte loads and stores, the four-wide FMA / add / max, the four MFMAs of an (A, B) float4
 // pair, the plain nine-tap depthwise chunk, the activation with and without the bias + skip in front of it, the ragged store of output
 // heads with Co % 4 != 0, the stage programs' tensor reference and magic division, and the s_memtime stamp of the diagnostic builds.
@@ -66,6 +67,8 @@ __device__ __forceinline__ float4 act4(const float4& v, const float4& slope, flo
     return make_float4(fminf(fmaxf(v.x, 0.f) + slope.x * fminf(v.x, 0.f), hi), fminf(fmaxf(v.y, 0.f) + slope.y * fminf(v.y, 0.f), hi),
                        fminf(fmaxf(v.z, 0.f) + slope.z * fminf(v.z, 0.f), hi), fminf(fmaxf(v.w, 0.f) + slope.w * fminf(v.w, 0.f), hi));
 }
+// the same for one value (the first convolution's and the whole-frame heads' epilogues)
+__device__ __forceinline__ float act1(float v, float slope, float hi) { return fminf(fmaxf(v, 0.f) + slope * fminf(v, 0.f), hi); }
 // act((D + bias) + skip), in this order
 __device__ __forceinline__ float4 bias_skip_act4(const float4& Dq, const float4& bias, const float4& skip, const float4& slope, float hi) {
     return act4(add4(add4(Dq, bias), skip), slope, hi);

@@ -1,4 +1,4 @@
-// roi_dev.hpp — ROI maths on the device, shared by preproc.hip (face_roi_kernel / iris_roi_kernel) and kernels.hip (the post-processing kernel
+// roi_dev.hpp — ROI maths on the device, shared by preproc.hip (face_roi_kernel / iris_roi_kernel) and post_kernels.hip (the post-processing kernel
 // of the batched pipeline computes faces[0]'s ROI itself).
 #pragma once
 

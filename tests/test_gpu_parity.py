@@ -564,7 +564,7 @@ def test_single_launch_plan_vs_oracle_and_batched_plan(gpu, oracle, name, frames
                     np.testing.assert_array_equal(o, o2)
     m.set_option("graph", 1)
     labels = [r["kernel"] for r in m.profile(torch.from_numpy(x[:1]).cuda(), reps=1)]
-    behind = {"landmark": ["head_dot_kernel"] * 2,     # (the whole-frame convolutions of one to four frames: a wave per output, kernels.hip)
+    behind = {"landmark": ["head_dot_kernel"] * 2,     # (the whole-frame convolutions of one to four frames: a wave per output, head_kernels.hip)
               "iris": ["head_dot_kernel"] * 2}.get(name, [])
     if name in ("full", "sparse"):
         assert "bandnet_kernel" in labels[:4] and labels.count("bandnet_kernel") == 1, labels

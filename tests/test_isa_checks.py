@@ -27,6 +27,9 @@ CASES = {
     # the strip kernels and the row pipelines of BASELINE config 2 (four stages, 24 channels, plain and with either stride-2 tail), all four
     # forms: they share the frame functions of strip_kernels.hip, so a change to one of those is a change to every kernel
     "strip_kernels.hip": (["-DMI_DEV_ONE"], [""]),
+    # the first convolution, all three forms: the two MFMA forms share what a wave holds and does per picture row (StemWave), so a change to
+    # that is a change to both
+    "stem_kernels.hip": ([], [""]),
 }
 
 
@@ -59,5 +62,7 @@ def test_register_limit_kernels_do_not_spill():
                     assert k["vgpr"] + k["agpr"] <= 168, (name, k["pretty"], k["vgpr"])   # the face mesh's block pair (with and without the first convolution in front): three waves per SIMD, four workgroups per CU
                 if k["pretty"].startswith(("strip_kernel<4,", "strip_kernel<6,")):
                     assert k["vgpr"] + k["agpr"] <= 168, (name, k["pretty"], k["vgpr"])   # their launch bound: three waves per SIMD
+                if k["pretty"].startswith("mi::stem_mfma_kernel<"):
+                    assert k["vgpr"] + k["agpr"] <= 256, (name, k["pretty"], k["vgpr"], k["agpr"])   # launch_stem_mfma runs it at two workgroups of four waves per CU: two waves per SIMD
                 if "tail_kernel<false>" in k["pretty"]:
                     assert k["vgpr"] + k["agpr"] <= 128, (name, k["pretty"], k["vgpr"])   # four waves per SIMD
